@@ -19,10 +19,18 @@ A "step" is what the reference's run.py::train() does per snapshot: forward, mea
 accumulating (run.py:178-191); the optimiser (RMSprop, run.py:145) steps once per epoch, here once at the end of the K timed
 steps, inside the timed region.
 
+A plain run sets up, warms up, times the K steps and prints the result line (``value``, ``ms_per_step`` = one timed step).
+Everything else is measured only with ``--full`` (the ``--no-*`` options then leave out single parts):
 ``value`` is timed without per-stage events; the stage table and ``roofline`` come from a second pass of the same K steps with
 the library's HIP events on (dominant kernel; events recorded on the stream each kernel is launched on: regt_profile_*; ``traffic`` from the tracked rocprofv3 PMC summary named in ``traffic_source`` when that file holds the
-kernel this run launched, else null) and ``cpu_baseline`` (the oracle's eager-faithful CPU path on this box's host cores,
-rank 0, N = 1 only, bounded sample).
+kernel this run launched, else null), the other GEMM arithmetics, the TPIMS-size and configs[4] legs, and ``cpu_baseline`` (the
+oracle's eager-faithful CPU path on this box's host cores, rank 0, N = 1 only, bounded sample).
+
+``--dump-outputs DIR`` writes what the timed steps computed, from rank 0, as DIR/<name>.npy (float32): ``pred``, ``hidden`` and
+``loss`` of the last timed step, ``grad.<parameter>`` = the gradients accumulated over the K timed steps (copied once, right before
+the optimiser step that closes the timed region) and ``param.<parameter>`` = the parameters after that step.  An array of more
+than 2^20 elements is written as a fixed sample of them (seeded indices into the flattened array, the same in every run), so
+that the files stay well under 64 MB.  The inputs are seeded: the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -90,7 +98,37 @@ def parse():
                     help="skip the secondary cfg5shard leg (one rank's share of BASELINE configs[4], bf16 arithmetic, run as a child process)")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-stage HIP events")
     ap.add_argument("--cpu-baseline-only", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-stage events and roofline, the other GEMM arithmetics, the TPIMS-size and "
+                         "configs[4] legs, cpu_baseline (the --no-* options leave parts out); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the timed steps as DIR/<name>.npy (module docstring)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_ELEMENTS = 1 << 20        # per array; larger outputs are written as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> tensor (any device / float dtype); written as float32 .npy, a seeded sample of the flattened array when it
+    holds more than DUMP_MAX_ELEMENTS elements (same indices in every run: they depend on the element count only)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        if n > DUMP_MAX_ELEMENTS:
+            idx = np.unique(np.random.default_rng(n).integers(0, n, DUMP_MAX_ELEMENTS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs wrote {total / 2**20:.1f} MiB, more than the 64 MiB budget")
+    return total
 
 
 def host_info():
@@ -313,7 +351,7 @@ def cfg5shard_leg(args):
     with the roofline of ITS dominant kernel.  Secondary leg: never the headline value."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "cfg5shard", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--no-cpu-baseline", "--no-split-leg", "--no-tpims-leg"]
+           "--full", "--no-cpu-baseline", "--no-split-leg", "--no-tpims-leg"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -331,7 +369,7 @@ def cfg5full_leg(args):
     of its scaling curve, as a child process (own library state, own peak-memory figure).  Secondary leg: never the headline value."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "cfg5full", "--steps", str(min(args.steps, 10)), "--warmup", str(min(args.warmup, 2)),
-           "--no-cpu-baseline", "--no-split-leg", "--no-tpims-leg", "--no-cfg5-leg"]
+           "--full", "--no-cpu-baseline", "--no-split-leg", "--no-tpims-leg", "--no-cfg5-leg"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -560,20 +598,25 @@ def main():
     counter = [0]                             # ONE monotonically increasing step index over warm-up, timed loop and extra legs
     if pipe is not None:
         pipe.submit(0, xs[0])
+    dump = args.dump_outputs is not None and rank == 0
+    last = {}                                 # --dump-outputs: pred / hidden of the last timed step
+    with_grad, grad_copy = [], []             # --dump-outputs: (name, parameter) with a gradient, and its copy
 
-    def step():
+    def step(keep=False):
         i = counter[0]
         counter[0] += 1
         x, y = xs[i % n_snap], ys[i % n_snap]
         if shard is None:
-            pred, _ = model.forward_prepared(x, graph)
+            pred, hidden = model.forward_prepared(x, graph)
         elif pipe is None:
-            pred, _ = model.forward_packed(ext[i % n_snap], graph)
+            pred, hidden = model.forward_packed(ext[i % n_snap], graph)
         else:
             # the halo rows of snapshot i were exchanged while step i-1 computed; start snapshot i+1's exchange now
             xp_ext = pipe.acquire(i % 2)
             pipe.submit((i + 1) % 2, xs[(i + 1) % n_snap])
-            pred, _ = model.forward_packed(xp_ext, graph)
+            pred, hidden = model.forward_packed(xp_ext, graph)
+        if keep:
+            last["pred"], last["hidden"] = pred.detach(), hidden.detach()
         loss = R.functional.mse_loss(pred, y, gnodes * O)   # mean over the GLOBAL graph (run.py:180): value + gradient in one kernel
         loss.backward()
         if pipe is not None:
@@ -582,7 +625,7 @@ def main():
 
     ar_events = []
 
-    def epoch_end():
+    def epoch_end(keep=False):
         if world > 1 or force_shard:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -591,6 +634,8 @@ def main():
             ar_events.append((e0, e1))
         else:
             R.dist.allreduce_gradients(params)
+        if keep:                              # --dump-outputs: the accumulated gradients the optimiser step consumes
+            torch._foreach_copy_(grad_copy, [p.grad for _, p in with_grad])
         opt.step()
         opt.zero_grad(set_to_none=False)
 
@@ -600,15 +645,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(k):
+    def timed(k, keep=False):
         # the caller holds no loss / autograd graph at this point: both pooled activation workspaces are free, the loop
         # alternates between them exactly as the warm-up did (a third one would be an 11 GB hipMalloc inside the region)
         loss = None
         fence()
         t0 = time.perf_counter()
-        for _ in range(k):
-            loss = step()
-        epoch_end()
+        for j in range(k):
+            loss = step(keep and j == k - 1)
+        epoch_end(keep)
         fence()
         return time.perf_counter() - t0, loss
 
@@ -619,16 +664,26 @@ def main():
     epoch_end()
     fence()
     alloc0 = torch.cuda.memory_stats().get("num_device_alloc", 0)
-    profile = not args.no_profile
+    profile = args.full and not args.no_profile
     loss = None
+    if dump:                                  # (the reference's unused attention parameters never receive a gradient)
+        with_grad = [(n, p) for n, p in model.named_parameters() if p.grad is not None]
+        grad_copy = [torch.empty_like(p.grad) for _, p in with_grad]
     if pipe is not None:
         pipe.timed = True
     # the headline: K steps WITHOUT per-stage events (they cost ~1.5 % of a step); the stage durations come from a second pass of the
     # same K steps with the library's events on (regt_profile_*), timed too and reported as `ms_per_step_with_stage_events`
-    dt, loss = timed(args.steps)
+    dt, loss = timed(args.steps, keep=dump)
     if pipe is not None:
         pipe.timed = False
     allocs_timed = torch.cuda.memory_stats().get("num_device_alloc", 0) - alloc0
+    if dump:
+        outs = {"pred": last["pred"], "hidden": last["hidden"], "loss": loss}
+        outs.update({"grad." + n: g for (n, _), g in zip(with_grad, grad_copy)})
+        outs.update({"param." + n: p for n, p in model.named_parameters()})
+        dump_outputs(args.dump_outputs, outs)
+        outs, grad_copy = None, []
+        last.clear()
     stages = {}
     dt_profiled = None
     if profile:
@@ -646,7 +701,7 @@ def main():
     # Secondary, opt-in arithmetics (never the headline): the same K steps in the other GEMM modes.  N = 1 only, after the
     # timed region.
     other_modes = {}
-    if world == 1 and not args.no_split_leg and not force_shard and not rows_bf16:     # (bf16 input rows exist in mode 2 only)
+    if args.full and world == 1 and not args.no_split_leg and not force_shard and not rows_bf16:     # (bf16 input rows exist in mode 2 only)
         for m2 in (1, 2):
             if m2 == mode:
                 continue
@@ -661,7 +716,7 @@ def main():
             other_modes[m2] = d2
         lib.regt_set_gemm_mode(mode)
     tpims = None
-    if world == 1 and not args.no_tpims_leg and args.workload == "cfg3":
+    if args.full and world == 1 and not args.no_tpims_leg and args.workload == "cfg3":
         lib.regt_set_gemm_mode(0)
         tpims = tpims_leg(dev, with_cpu=not args.no_cpu_baseline)
         lib.regt_set_gemm_mode(mode)
@@ -769,10 +824,10 @@ def main():
                                 + ("; passes the same 1e-5 parity suite" if m2 == 1 else "; reduced precision, tolerance in tests/test_gpu_bf16.py")}
         if tpims is not None:
             out["tpims_configs1"] = tpims
-        if world == 1 and args.workload == "cfg3" and not args.no_cfg5_leg and not force_shard:
+        if args.full and world == 1 and args.workload == "cfg3" and not args.no_cfg5_leg and not force_shard:
             out["cfg5shard_configs4"] = cfg5shard_leg(args)
             out["cfg5full_configs4_one_gpu"] = cfg5full_leg(args)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if shard_of_8:
                 # the reference formulation materialises an (N, R*C) concat: 8.2 GB per period at 125k nodes x 64 regions, so
                 # the bounded sample is ONE of the rank's 8 regions (its nodes and intra-region edges) with the 64-region model

@@ -1,7 +1,8 @@
 """TPIMS ETL counterpart (regt-gcn_amd/etl.py): a synthetic dataset directory in the reference's layout, the processed
-13-tuple round trip, and -- when the reference tree is mounted -- agreement with the committed fixture, which an
-independent script (oracle/make_fixtures.py) built from the same files."""
+13-tuple round trip, and agreement with the committed fixture, which an independent script (oracle/make_fixtures.py) built
+from the same raw files (tests/golden/tpims_dataset_subset.tar.xz: the reference's dataset files it read, oracle/make_dataset_subset.py)."""
 import os
+import tarfile
 
 import numpy as np
 import pytest
@@ -10,7 +11,7 @@ import torch
 import regtgcn_amd as R
 from conftest import GOLDEN
 
-REF_DATASET = "/root/reference/dataset"
+DATASET_SUBSET = os.path.join(GOLDEN, "tpims_dataset_subset.tar.xz")
 
 
 def _write_dataset(root):
@@ -89,11 +90,13 @@ def test_processed_tuple_round_trip(tmp_path):
     assert len(xs) == 1 and xs[0].shape == (6, 8, 2) and ys[0].shape == (6, 1)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATASET), reason="reference dataset directory not mounted")
-def test_etl_agrees_with_committed_fixture():
+def test_etl_agrees_with_committed_fixture(tmp_path):
+    with tarfile.open(DATASET_SUBSET) as tf:
+        tf.extractall(tmp_path, filter="data")
     fx = np.load(os.path.join(GOLDEN, "tpims_fixture.npz"))
     steps = fx["node_data"].shape[2]
-    d = R.etl.load_tpims(REF_DATASET, max_steps=steps)
+    assert len(os.listdir(tmp_path / "nodes" / "0322")) == steps
+    d = R.etl.load_tpims(str(tmp_path), max_steps=steps)
     assert d.node_data.shape == fx["node_data"].shape
     np.testing.assert_allclose(d.node_data.numpy(), fx["node_data"], atol=1e-7)
     n_union = int(fx["n_union_edges"])                                              # the fixture appends synthetic cross edges

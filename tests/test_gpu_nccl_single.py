@@ -90,7 +90,7 @@ def test_bench_shard_path_with_one_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_PORT=str(_free_port()))
     res = subprocess.run([sys.executable, "bench.py", "--force-shard-path", "--workload", "small", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-split-leg", "--no-tpims-leg"], cwd=root, env=env, capture_output=True, text=True,
+                          "--full", "--no-cpu-baseline", "--no-split-leg", "--no-tpims-leg"], cwd=root, env=env, capture_output=True, text=True,
                          timeout=400)
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads(res.stdout.strip().splitlines()[-1])

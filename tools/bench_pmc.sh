@@ -6,7 +6,7 @@
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 mkdir -p gpurun_out
-common="--no-cpu-baseline --no-split-leg --no-tpims-leg --no-cfg5-leg"
+common="--full --no-cpu-baseline --no-split-leg --no-tpims-leg --no-cfg5-leg"
 python3 bench.py "$@" --steps 20 --warmup 3 $common > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err || { echo "plain bench failed"; tail -5 gpurun_out/${tag}_bench.err; exit 1; }
 echo "bench done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_kt -- python3 bench.py "$@" --steps 12 --warmup 3 $common > gpurun_out/${tag}_kt.log 2>&1 || { echo "kernel-trace pass failed"; tail -5 gpurun_out/${tag}_kt.log; exit 1; }
