@@ -24,7 +24,7 @@ extern "C" {
 
 typedef void* regt_stream_t;
 
-#define REGT_ABI_VERSION 7
+#define REGT_ABI_VERSION 8
 
 int32_t regt_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). */
@@ -309,6 +309,24 @@ int32_t regt_gat_forward(const int32_t* rowptr, const int32_t* col, const float*
 int32_t regt_gat_backward(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col,
                           const float* x, const float* u_src, float slope, int32_t num_nodes, int32_t periods,
                           int32_t num_features, const float* dout, float* stats, float* dsd, regt_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * SpatialGCN (models/SpatialGCN.py): its first ChebConv(K=2, 64 channels), ReLU and dropout, summed over the periods
+ * (the second ChebConv is linear and its outputs are summed over the periods, so it runs once, on this sum):
+ *   S[n, :] = sum_{t = 0..T-1} keep_t * 2 * relu(x[n,t,:] W0^T + lx[n,t,:] W1^T + bias)      (eval: keep = NULL, no scale)
+ * x_packed (N, T, F) from regt_pack_x, lx_packed = L~ x_packed at width T*F (regt_spmm_csr over the ChebConv operator);
+ * w0 / w1 (64, F) = gcn.lins.{0,1}.weight, bias (64) = gcn.bias; S (N, 64).  keep: uint32 (N*T, 2), row node*T + t, bit j
+ * of word w keeps channel 32w + j; NULL = eval mode.  F % 4 == 0, 4 <= F <= 64, 1 <= T <= 255; x, lx, bias, S, dS 16-byte
+ * aligned.  The backward recomputes the pre-activation and writes dw0, dw1 (64, F) and dbias (64) from dS (N, 64); it needs
+ * `slab` of regt_spatial_embed_slab_floats(N, T, F) floats (0 = invalid dims).  Sums run in a fixed order: bit-reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+size_t regt_spatial_embed_slab_floats(int32_t num_nodes, int32_t periods, int32_t num_features);
+int32_t regt_spatial_embed_forward(const float* x_packed, const float* lx_packed, const float* w0, const float* w1, const float* bias,
+                                   const uint32_t* keep, int32_t num_nodes, int32_t periods, int32_t num_features, float* s_out,
+                                   regt_stream_t stream);
+int32_t regt_spatial_embed_backward(const float* x_packed, const float* lx_packed, const float* w0, const float* w1,
+                                    const float* bias, const uint32_t* keep, const float* ds, int32_t num_nodes, int32_t periods,
+                                    int32_t num_features, float* dw0, float* dw1, float* dbias, float* slab, regt_stream_t stream);
 
 /* Arithmetic of the dense contractions.  0 (default): fp32 MFMA (v_mfma_f32_32x32x2_f32).  1: every fp32 operand is
  * split exactly into three bf16 pieces and the six leading partial products run on the bf16 MFMA with fp32

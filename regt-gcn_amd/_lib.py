@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # REGT_LIB_DIR: a developer build of the same library in another directory (build.py honours the same variable), e.g. the
 # workgroup-trace build of tools/wg_trace.py; never a different implementation
 LIB_PATH = os.path.join(os.environ.get("REGT_LIB_DIR") or os.path.join(HERE, "lib"), "libregtgcn_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 f32p = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int32)
@@ -117,6 +117,9 @@ SIGNATURES = {
     "regt_debug_trace": (C.c_int64, [C.POINTER(C.c_int64), C.c_int64]),
     "regt_profile_enable": (C.c_int32, [C.c_int32]),
     "regt_profile_collect": (C.c_int32, [C.c_char_p, C.c_size_t]),
+    "regt_spatial_embed_slab_floats": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "regt_spatial_embed_forward": (C.c_int32, [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+    "regt_spatial_embed_backward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]),
     "regt_mse_loss_grad": (C.c_int32, [vp, vp, vp, vp, C.c_int64, C.c_int64, vp]),
 }
 

@@ -1637,6 +1637,34 @@ int32_t regt_mean_csr(const int64_t* ei, int64_t E, int32_t N, int32_t* rowptr, 
     return graph_mean_csr(ei, (long)E, N, rowptr, col, val, flags_dev, ws, ws_bytes, (hipStream_t)st);
 }
 
+size_t regt_spatial_embed_slab_floats(int32_t N, int32_t T, int32_t F) { return T > 255 ? 0 : spatial_slab_floats(N, T, F); }
+
+static int spatial_check_dims(const char* what, int32_t N, int32_t T, int32_t F) {
+    REGT_CHECK_ARG(N >= 1, "%s: num_nodes must be >= 1, got %d", what, N);
+    REGT_CHECK_ARG(T >= 1 && T <= 255, "%s: periods must be in [1, 255], got %d", what, T);
+    REGT_CHECK_ARG(F >= 4 && F <= 64 && F % 4 == 0, "%s: num_features must be a multiple of 4 in [4, 64], got %d", what, F);
+    return REGT_OK;
+}
+
+int32_t regt_spatial_embed_forward(const float* x, const float* lx, const float* w0, const float* w1, const float* b, const uint32_t* keep,
+                                   int32_t N, int32_t T, int32_t F, float* s_out, regt_stream_t st) {
+    REGT_CHECK_ARG(x && lx && w0 && w1 && b && s_out, "regt_spatial_embed_forward: NULL pointer");
+    if (int rc = spatial_check_dims("regt_spatial_embed_forward", N, T, F)) return rc;
+    REGT_CHECK_ARG(al16(x) && al16(lx) && al16(b) && al16(s_out) && (!keep || (reinterpret_cast<uintptr_t>(keep) & 7) == 0),
+                   "regt_spatial_embed_forward: x, lx, bias, s_out must be 16-byte aligned, keep 8-byte aligned");
+    return launch_spatial_fwd(x, lx, w0, w1, b, keep, N, T, F, s_out, (hipStream_t)st);
+}
+
+int32_t regt_spatial_embed_backward(const float* x, const float* lx, const float* w0, const float* w1, const float* b,
+                                    const uint32_t* keep, const float* ds, int32_t N, int32_t T, int32_t F, float* dw0, float* dw1,
+                                    float* db, float* slab, regt_stream_t st) {
+    REGT_CHECK_ARG(x && lx && w0 && w1 && b && ds && dw0 && dw1 && db && slab, "regt_spatial_embed_backward: NULL pointer");
+    if (int rc = spatial_check_dims("regt_spatial_embed_backward", N, T, F)) return rc;
+    REGT_CHECK_ARG(al16(x) && al16(lx) && al16(ds) && (!keep || (reinterpret_cast<uintptr_t>(keep) & 7) == 0),
+                   "regt_spatial_embed_backward: x, lx, ds must be 16-byte aligned, keep 8-byte aligned");
+    return launch_spatial_bwd(x, lx, w0, w1, b, keep, ds, N, T, F, dw0, dw1, db, slab, (hipStream_t)st);
+}
+
 int64_t regt_debug_trace(int64_t* out_host, int64_t capacity) { return fused_trace_fetch(reinterpret_cast<long*>(out_host), (long)capacity); }
 
 int32_t regt_profile_enable(int32_t on) {

@@ -350,6 +350,13 @@ bool embed_fp32_ok(long M, int C, int F, int T);
 int launch_embed_fp32(const float* X, const float* LX, const float* A0, const float* Aall, const int* node_region, const float* bias,
                       float* out, long M, int T, int act, float slope, hipStream_t st);
 
+// first ChebConv of SpatialGCN + ReLU + dropout mask + period sum (spatial.hip): S (N, 64); backward -> dW0, dW1 (64, F), db (64)
+size_t spatial_slab_floats(int N, int T, int F);
+int launch_spatial_fwd(const float* x, const float* lx, const float* w0, const float* w1, const float* b, const uint32_t* keep, int N,
+                       int T, int F, float* S, hipStream_t st);
+int launch_spatial_bwd(const float* x, const float* lx, const float* w0, const float* w1, const float* b, const uint32_t* keep,
+                       const float* dS, int N, int T, int F, float* dw0, float* dw1, float* db, float* slab, hipStream_t st);
+
 // hipFuncSetAttribute is a (slow, host-synchronous) driver call: do it once per kernel, not per launch.
 template <class K>
 static int set_lds_once(K kernel, int bytes, bool* done) {

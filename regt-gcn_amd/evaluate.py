@@ -79,17 +79,21 @@ def load_processed_pickle(path: str) -> Dict[str, torch.Tensor]:
     return out
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="RegT-GCN evaluation (reference predict.py metrics)")
     ap.add_argument("--fixture", help=".npz in the layout of tests/golden/tpims_fixture.npz")
     ap.add_argument("--pickle", help="the reference's processed tpims_data_small.pkl")
     ap.add_argument("--checkpoint", required=True)
-    ap.add_argument("--model", default="RegionalTemporalGCN", choices=["RegionalTemporalGCN", "TemporalGCN"])
+    ap.add_argument("--model", default="RegionalTemporalGCN", choices=["RegionalTemporalGCN", "TemporalGCN", "SpatialGCN"])   # predict.py:110-114
     ap.add_argument("--num_timesteps_in", default=6, type=int)
     ap.add_argument("--num_timesteps_out", default=1, type=int)
     ap.add_argument("--tr", "--train_ratio", default=0.2, type=float, dest="tr")
     ap.add_argument("--snap_batch", type=int, default=1, help="test snapshots per forward (block-diagonal graph of B copies; same metrics)")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     if a.pickle:
         d = load_processed_pickle(a.pickle)
     elif a.fixture:
@@ -105,6 +109,9 @@ def main(argv=None):
         model = rnn.RegionalTemporalGCN(f, n, a.num_timesteps_in, a.num_timesteps_out).to(dev)
         graph = model.prepare_graph(d["edge_index"].to(dev), [d[f"edge_{r}_index"].to(dev) for r in REGIONS],
                                     [d[f"edge_{r}_attr"].to(dev) for r in REGIONS])
+    elif a.model == "SpatialGCN":
+        model = rnn.SpatialGCN(f, a.num_timesteps_in, a.num_timesteps_out).to(dev)
+        graph = model.prepare_graph(d["edge_index"].to(dev), d["edge_attr"].to(dev), n)
     else:
         model = rnn.TemporalGCN(f, a.num_timesteps_in, a.num_timesteps_out).to(dev)
         graph = model.prepare_graph(d["edge_index"].to(dev), d["edge_attr"].to(dev), n)

@@ -583,6 +583,25 @@ class GatAggregateFunction(torch.autograd.Function):
         return None, du[0].contiguous(), du[1].contiguous(), None, None
 
 
+class SpatialEmbedFunction(torch.autograd.Function):
+    """(x_packed, lx_packed (N,T,F) data, W0, W1 (64,F), b (64), keep (N*T,2) int32 | None) -> S (N,64) = sum_t dropout(relu(ChebConv_t))
+    (regt_spatial_embed_forward / regt_spatial_embed_backward: the backward recomputes the pre-activation; x is data, no dx)."""
+
+    @staticmethod
+    def forward(ctx, xp, lxp, w0, w1, b, keep):
+        from . import ops
+        ctx.save_for_backward(xp, lxp, w0, w1, b)
+        ctx.keep = keep
+        return ops.spatial_embed_forward(xp, lxp, w0, w1, b, keep)
+
+    @staticmethod
+    def backward(ctx, ds):
+        from . import ops
+        xp, lxp, w0, w1, b = ctx.saved_tensors
+        dw0, dw1, db = ops.spatial_embed_backward(xp, lxp, w0, w1, b, ctx.keep, ds.contiguous())
+        return None, None, dw0, dw1, db, None
+
+
 class ZeroGradAnchor(torch.autograd.Function):
     """Identity on ``(pred, hidden)`` that gives ``dead`` parameters an all-zero gradient: in the reference's GraphSAGE / GAT models
     the reset gate is computed and multiplied by the zero hidden state, so autograd hands its parameters zeros, not None --

@@ -336,6 +336,20 @@ def prepare_gcn_operator(edge_index: torch.Tensor, edge_weight: Optional[torch.T
     return GcnOperator(num_nodes, rp, col, val, t[0], t[1], t[2])
 
 
+def prepare_cheb_operator(edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor], num_nodes: int, copies: int = 1) -> GcnOperator:
+    """The scaled Laplacian L~ of ChebConv(K=2, 'sym', lambda_max=None) of one static graph (models/SpatialGCN.py:12-21) as a
+    destination-sorted CSR plus the CSR of its transpose, under the field names of :class:`GcnOperator` (so that
+    ``AggregateFunction`` runs it unchanged).  ``copies`` > 1: the block-diagonal operator of that many disjoint copies
+    (ChebConv's normalisation is degree-local, :func:`replicate_edges`)."""
+    if copies > 1:
+        edge_index, edge_weight = replicate_edges(edge_index, edge_weight, copies, num_nodes)
+        num_nodes *= copies
+    w = cheb_edge_weights(edge_index, edge_weight, num_nodes)
+    rp, col, val = raw_csr(edge_index, w, num_nodes)
+    t = transpose_csr(rp, col, val, num_nodes, num_nodes)
+    return GcnOperator(num_nodes, rp, col, val, t[0], t[1], t[2])
+
+
 def replicate_edges(edge_index: torch.Tensor, weight: Optional[torch.Tensor], copies: int, num_nodes: int):
     """``copies`` disjoint copies of one graph: copy b holds the nodes [b*N, (b+1)*N).  Both normalisations of the path are
     degree-local (gcn_norm, ChebConv.__norm__ with lambda_max = 2), so the operators of the replicated graph are block diagonal

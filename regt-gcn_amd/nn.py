@@ -8,6 +8,7 @@ unchanged:
 * :class:`TemporalGCN`          <-> models/TemporalGCN.py:7-32          (+ A3TGCN :35-91)
 * :class:`ConvStackedTemporalGCN` <-> models/ConvStackedTemporalGCN.py:8-33 (+ ConvStackedA3TGCN :35-126)
 * :class:`TGCN`                 <-> models/utils.py:69-203 (parameter container of the GRU cell)
+* :class:`SpatialGCN`           <-> models/SpatialGCN.py:8-49
 
 The modules only *hold* parameters; all arithmetic runs in libregtgcn_hip.so through
 :class:`regt-gcn_amd.functional.RegTGCNFunction`.  There is no CPU implementation here: calling
@@ -24,9 +25,9 @@ import torch.nn as nn
 from . import _lib
 from . import ops
 from .functional import (HEAD_HIDDEN, PARAM_NAMES_CELL, AggregateFunction, Cell0Function, CellFunction, GatAggregateFunction,
-                         LinearFunction, RegTGCNFunction, ZeroGradAnchor, param_names)
+                         LinearFunction, RegTGCNFunction, SpatialEmbedFunction, ZeroGradAnchor, param_names)
 from .graph import (AttentionPattern, GcnOperator, MeanOperator, PreparedGraph, fingerprint, prepare_attention_pattern,
-                    prepare_gcn_operator, prepare_graph, prepare_mean_operator)
+                    prepare_cheb_operator, prepare_gcn_operator, prepare_graph, prepare_mean_operator)
 
 HIDDEN = 256          # out_channels=256, models/RegionalTemporalGCN.py:14 / models/TemporalGCN.py:12
 LEAKY_SLOPE = 0.01    # F.leaky_relu default, models/RegionalTemporalGCN.py:143
@@ -585,3 +586,68 @@ class GATTemporal(_ZeroHiddenModel):
         n = x.shape[0]
         pat = self._graphs.get([edge_index, None], n, lambda: prepare_attention_pattern(edge_index, n))
         return self.forward_prepared(x, pat)
+
+
+# ---- SpatialGCN (models/SpatialGCN.py) ---------------------------------------------------------------------------------------
+
+def draw_keep_mask(rows: int, device) -> torch.Tensor:
+    """F.dropout(p = 0.5) keep bits for ``rows`` (node*T + t) rows of 64 channels: (rows, 2) int32, bit j of word w keeps channel
+    32w + j.  Random bytes viewed as int32 (``int32.random_()`` never sets the top bit, which would always drop channel 31 of a word)."""
+    return torch.randint(0, 256, (rows, 8), dtype=torch.uint8, device=device).view(torch.int32)
+
+
+class SpatialGCN(nn.Module):
+    """Two ChebConv(K=2) layers with ReLU and dropout between them, summed over the periods, and a 256 -> 128 -> O head
+    (models/SpatialGCN.py:8-49).  ``forward(x, edge_index, edge_attr)`` -> ``(prediction (N, output_dim), H (N, 256))``, H being
+    the period sum itself (the reference's ``relu(H_accum)`` on :45 is never used).
+
+    gcn2 is linear and its outputs are summed over the periods, so H = S V0^T + (L~ S) V1^T + T c with S = sum_t dropout(relu(
+    gcn(x_t))) (N, 64): the first layer is one kernel pair (regt_spatial_embed_forward / _backward, which folds ReLU, the dropout
+    mask and the period sum), the second is one aggregation at width 64 and one (N x 128) . (128 x 256) GEMM.  Dropout follows
+    ``self.training``: in training mode one fresh mask is drawn on the device per call, unless ``forward_prepared`` is given
+    ``keep`` ((N*T, 2) int32 mask bits, see :func:`draw_keep_mask`)."""
+
+    CHANNELS = 64         # models/SpatialGCN.py:14
+    HIDDEN = 256          # :19
+    DROPOUT = 0.5         # F.dropout default, :41
+
+    def __init__(self, node_features: int, periods: int, output_dim: int):
+        super().__init__()
+        self.gcn = _ChebConvParams(node_features, self.CHANNELS)
+        self.gcn2 = _ChebConvParams(self.CHANNELS, self.HIDDEN)
+        self.periods = periods
+        self.output_dim = output_dim
+        self.linear1 = nn.Linear(self.HIDDEN, HEAD_HIDDEN)
+        self.linear2 = nn.Linear(HEAD_HIDDEN, output_dim)
+        self.relu = nn.ReLU()
+        self.leakyRelu = nn.LeakyReLU()
+        self._graphs = _GraphCache()
+
+    def prepare_graph(self, edge_index, edge_attr, num_nodes: int, copies: int = 1) -> GcnOperator:
+        return prepare_cheb_operator(edge_index, edge_attr, num_nodes, copies)
+
+    def forward_prepared(self, x: torch.Tensor, op: GcnOperator, keep: Optional[torch.Tensor] = None):
+        _need_cuda(x)
+        if x.shape[2] != self.periods:
+            raise ValueError(f"x has {x.shape[2]} periods, the model {self.periods}")
+        x, fpad = _pad_features(x)            # the kernels read 16-byte feature rows: zero columns for x and for the weights
+        n, f, t = x.shape
+        if self.training:
+            keep = draw_keep_mask(n * t, x.device) if keep is None else keep
+        else:
+            keep = None                       # F.dropout(training=False) is the identity
+        xp = ops.pack_x(x)                                                              # (N, T, F)
+        lxp = ops.spmm_csr(op.rowptr, op.col, op.val, xp.view(n, t * f)).view(n, t, f)  # L~ x: input data, no backward
+        s = SpatialEmbedFunction.apply(xp, lxp, _pad_cols(self.gcn.lins[0].weight, fpad), _pad_cols(self.gcn.lins[1].weight, fpad),
+                                       self.gcn.bias, keep)                            # (N, 64)
+        ls = AggregateFunction.apply(s, op)                                             # L~ S
+        v = torch.cat([self.gcn2.lins[0].weight, self.gcn2.lins[1].weight], dim=1)     # (256, 128)
+        h = LinearFunction.apply(torch.cat([s, ls], dim=1), v, self.gcn2.bias * t)     # H = S V0^T + (L~ S) V1^T + T c
+        z = torch.relu(LinearFunction.apply(h, self.linear1.weight, self.linear1.bias))
+        return LinearFunction.apply(z, self.linear2.weight, self.linear2.bias), h
+
+    def forward(self, x, edge_index, edge_attr):
+        _need_cuda(x)
+        n = x.shape[0]
+        op = self._graphs.get([edge_index, edge_attr], n, lambda: prepare_cheb_operator(edge_index, edge_attr, n))
+        return self.forward_prepared(x, op)

@@ -145,3 +145,52 @@ def gat_backward(rowptr, col, t_rowptr, t_col, xp: torch.Tensor, u_src: torch.Te
                                              _lib.ptr(u_src), slope, n, t, f, _lib.ptr(dout), _lib.ptr(stats), _lib.ptr(dsd), _stream()),
                "regt_gat_backward")
     return dsd
+
+
+SPATIAL_CHANNELS = 64        # out_channels of SpatialGCN's first ChebConv (models/SpatialGCN.py:14)
+
+
+def _keep_ptr(keep: Optional[torch.Tensor], rows: int, dev):
+    if keep is None:
+        return None
+    if keep.dtype != torch.int32 or not keep.is_cuda or keep.device != dev or tuple(keep.shape) != (rows, 2) or not keep.is_contiguous():
+        raise ValueError(f"keep must be a contiguous int32 ({rows}, 2) tensor on {dev}")
+    return _lib.ptr(keep)
+
+
+def spatial_embed_forward(xp: torch.Tensor, lxp: torch.Tensor, w0: torch.Tensor, w1: torch.Tensor, bias: torch.Tensor,
+                          keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """S (N, 64) = sum_t keep_t * 2 * relu(x_t W0^T + lx_t W1^T + b) from packed rows xp, lxp (N, T, F); keep (N*T, 2) int32 mask
+    bits (row node*T + t, bit j of word w keeps channel 32w + j) or None (eval: no mask, no scale)."""
+    xp, lxp = _f32c(xp, "x_packed"), _f32c(lxp, "lx_packed")
+    w0, w1, bias = _f32c(w0, "w0"), _f32c(w1, "w1"), _f32c(bias, "bias")
+    n, t, f = xp.shape
+    if tuple(lxp.shape) != (n, t, f) or tuple(w0.shape) != (SPATIAL_CHANNELS, f) or tuple(w1.shape) != (SPATIAL_CHANNELS, f) \
+            or bias.numel() != SPATIAL_CHANNELS:
+        raise ValueError("spatial_embed_forward: inconsistent shapes")
+    s = torch.empty(n, SPATIAL_CHANNELS, dtype=torch.float32, device=xp.device)
+    _lib.check(_lib.load().regt_spatial_embed_forward(_lib.ptr(xp), _lib.ptr(lxp), _lib.ptr(w0), _lib.ptr(w1), _lib.ptr(bias),
+                                                      _keep_ptr(keep, n * t, xp.device), n, t, f, _lib.ptr(s), _stream()),
+               "regt_spatial_embed_forward")
+    return s
+
+
+def spatial_embed_backward(xp: torch.Tensor, lxp: torch.Tensor, w0: torch.Tensor, w1: torch.Tensor, bias: torch.Tensor,
+                           keep: Optional[torch.Tensor], ds: torch.Tensor):
+    """(dW0, dW1, db) of :func:`spatial_embed_forward` given dL/dS (N, 64)."""
+    xp, lxp = _f32c(xp, "x_packed"), _f32c(lxp, "lx_packed")
+    w0, w1, bias, ds = _f32c(w0, "w0"), _f32c(w1, "w1"), _f32c(bias, "bias"), _f32c(ds, "ds")
+    n, t, f = xp.shape
+    if tuple(ds.shape) != (n, SPATIAL_CHANNELS):
+        raise ValueError(f"ds must be ({n}, {SPATIAL_CHANNELS})")
+    lib = _lib.load()
+    nslab = lib.regt_spatial_embed_slab_floats(n, t, f)
+    if nslab == 0:
+        raise _lib.RegtError(f"regt_spatial_embed_slab_floats: unsupported dims N={n} T={t} F={f}")
+    slab = torch.empty(nslab, dtype=torch.float32, device=xp.device)
+    dw0, dw1 = torch.empty_like(w0), torch.empty_like(w1)
+    db = torch.empty(SPATIAL_CHANNELS, dtype=torch.float32, device=xp.device)
+    _lib.check(lib.regt_spatial_embed_backward(_lib.ptr(xp), _lib.ptr(lxp), _lib.ptr(w0), _lib.ptr(w1), _lib.ptr(bias),
+                                               _keep_ptr(keep, n * t, xp.device), _lib.ptr(ds), n, t, f, _lib.ptr(dw0), _lib.ptr(dw1),
+                                               _lib.ptr(db), _lib.ptr(slab), _stream()), "regt_spatial_embed_backward")
+    return dw0, dw1, db

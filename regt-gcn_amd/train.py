@@ -191,9 +191,11 @@ def split(xs, ys, ratio: float):
     return (xs[:k], ys[:k]), (xs[k:], ys[k:])
 
 
-# models of run.py:115-136 that are built on the TGCN cell (the hot path and the SURVEY 8(f) baselines); the others
-# (SpatialGCN, TemporalGConvLSTM, StackedGRU, STAEformer, STID, STNorm) are out of scope
-MODELS = ("RegionalTemporalGCN", "RandomTemporalGCN", "TemporalGCN", "ConvStackedTemporalGCN", "GraphSAGETemporalGCN", "GAT", "GATTemporal")
+# graph models of run.py:115-136: those built on the TGCN cell (the hot path and the SURVEY 8(f) baselines) and SpatialGCN (two
+# ChebConv layers, run.py:117-118); TemporalGConvLSTM (which run.py:122 cannot construct), StackedGRU, STAEformer, STID and STNorm
+# are out of scope
+MODELS = ("RegionalTemporalGCN", "RandomTemporalGCN", "TemporalGCN", "ConvStackedTemporalGCN", "GraphSAGETemporalGCN", "GAT", "GATTemporal",
+          "SpatialGCN")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -287,6 +289,9 @@ def main(argv=None):
     elif a.model == "ConvStackedTemporalGCN":                               # run.py:125-126
         model = rnn.ConvStackedTemporalGCN(f, a.num_timesteps_in, a.num_timesteps_out).to(dev)
         graph = model.prepare_graph(ei, ea, n)
+    elif a.model == "SpatialGCN":                                           # run.py:117-118
+        model = rnn.SpatialGCN(f, a.num_timesteps_in, a.num_timesteps_out).to(dev)
+        graph = model.prepare_graph(ei, ea, n)
     elif a.model == "GraphSAGETemporalGCN":                                 # run.py:127-128
         model = rnn.GraphSAGETemporalGCN(f, n, a.num_timesteps_in, a.num_timesteps_out).to(dev)
         graph = model.prepare_graph(ei, n)
@@ -309,7 +314,7 @@ def main(argv=None):
             raise SystemExit("--snap_batch and --fused_step are alternatives (both remove per-snapshot host work)")
         # every operator of these models is local to a node's in-neighbours (gcn_norm, ChebConv.__norm__, SAGE mean, GAT softmax), so
         # B disjoint copies of the graph are B independent snapshots
-        if a.model in ("TemporalGCN", "ConvStackedTemporalGCN"):
+        if a.model in ("TemporalGCN", "ConvStackedTemporalGCN", "SpatialGCN"):
             graphs = BatchedGraphs(lambda b: model.prepare_graph(ei, ea, n, copies=b))
         elif a.model in ("GraphSAGETemporalGCN", "GAT", "GATTemporal"):
             graphs = BatchedGraphs(lambda b: model.prepare_graph(ei, n, copies=b))
