@@ -328,6 +328,31 @@ int32_t regt_spatial_embed_backward(const float* x_packed, const float* lx_packe
                                     const float* bias, const uint32_t* keep, const float* ds, int32_t num_nodes, int32_t periods,
                                     int32_t num_features, float* dw0, float* dw1, float* dbias, float* slab, regt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * STNorm (models/STNorm.py) with channels = 16, kernel_size = 2: start_conv, blocks * layers gated dilated-conv layers on
+ * [x | TNorm(x) | SNorm(x)] with residual and skip connections, and the two-conv head.
+ *   x (batch, seq_len, num_nodes, in_dim) -- the reference's forward input; out (batch, out_dim, num_nodes, L_out) with
+ *   L_out = max(seq_len, RF) - RF + 1, RF = 1 + blocks * (2^layers - 1).
+ *   params: device pointers, 6 head entries (start_conv.weight, .bias, end_conv_1.weight, .bias, end_conv_2.weight, .bias),
+ *   then 12 per layer i (filter_convs.i.weight, .bias, gate_convs.i.*, residual_convs.i.*, skip_convs.i.*, tn.i.gamma,
+ *   tn.i.beta, sn.i.gamma, sn.i.beta; NULL where tnorm / snorm is 0).  running: tn.i.running_mean, tn.i.running_var per
+ *   layer (NULL table when tnorm is 0).  grads: the layout of params.
+ *   tnorm_group: TNorm statistics pool groups of that many consecutive batch elements (batch for the module call); in
+ *   training mode the forward updates the running buffers group by group, in order.  The forward writes the layer inputs
+ *   and statistics the backward reads into `workspace`; the backward alone uses `scratch`.  Sizes in floats from
+ *   regt_stnorm_sizes (REGT_ERR_ARG for invalid dims).  num_nodes >= 2; 1 <= in_dim, out_dim <= 256; layers <= 8;
+ *   blocks * layers <= 64 (in_dim / out_dim: the LDS rows of the start-conv / head backward).  Every table entry
+ *   must be a contiguous fp32 device tensor of the reference's shape (regtgcn_amd.ops checks that before the call).  Sums run in a fixed order without float atomics: bit-reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t num_nodes, batch, tnorm_group, seq_len, in_dim, out_dim, blocks, layers, tnorm, snorm, training;
+} regt_stnorm_dims;
+int32_t regt_stnorm_sizes(const regt_stnorm_dims* dims, size_t* workspace_floats, size_t* scratch_floats);
+int32_t regt_stnorm_forward(const regt_stnorm_dims* dims, const float* x, const float* const* params, float* const* running,
+                            float* out, float* workspace, regt_stream_t stream);
+int32_t regt_stnorm_backward(const regt_stnorm_dims* dims, const float* x, const float* const* params, float* const* running,
+                             const float* dout, float* const* grads, const float* workspace, float* scratch, regt_stream_t stream);
+
 /* Arithmetic of the dense contractions.  0 (default): fp32 MFMA (v_mfma_f32_32x32x2_f32).  1: every fp32 operand is
  * split exactly into three bf16 pieces and the six leading partial products run on the bf16 MFMA with fp32
  * accumulation -- fp32-level rounding error (dropped terms <= 3 * 2^-24 of a product), ~2x the matrix-pipe rate.

@@ -46,6 +46,11 @@ def arith_code(arith) -> int:
         raise ValueError(f"arithmetic must be one of {sorted(k for k in ARITH_NAMES if k)} or None, got {arith!r}") from None
 
 
+class StnormDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_nodes", "batch", "tnorm_group", "seq_len", "in_dim", "out_dim", "blocks", "layers",
+                                         "tnorm", "snorm", "training")]
+
+
 class Graph(C.Structure):
     _fields_ = [("rowptr", vp), ("col", vp), ("val", vp), ("node_region", vp), ("chunk_tab", vp),
                 ("chunk_region", vp), ("n_chunks", C.c_int32),
@@ -120,6 +125,9 @@ SIGNATURES = {
     "regt_spatial_embed_slab_floats": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "regt_spatial_embed_forward": (C.c_int32, [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
     "regt_spatial_embed_backward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]),
+    "regt_stnorm_sizes": (C.c_int32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "regt_stnorm_forward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp]),
+    "regt_stnorm_backward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "regt_mse_loss_grad": (C.c_int32, [vp, vp, vp, vp, C.c_int64, C.c_int64, vp]),
 }
 

@@ -1665,6 +1665,65 @@ int32_t regt_spatial_embed_backward(const float* x, const float* lx, const float
     return launch_spatial_bwd(x, lx, w0, w1, b, keep, ds, N, T, F, dw0, dw1, db, slab, (hipStream_t)st);
 }
 
+static int stnorm_check(const char* what, const regt_stnorm_dims* d, regt::StnDims* s) {
+    REGT_CHECK_ARG(d != nullptr, "%s: dims is NULL", what);
+    REGT_CHECK_ARG(d->num_nodes >= 2, "%s: num_nodes must be >= 2 (SNorm's unbiased variance), got %d", what, d->num_nodes);
+    REGT_CHECK_ARG(d->batch >= 1 && d->seq_len >= 1, "%s: batch and seq_len must be >= 1, got %d, %d", what, d->batch, d->seq_len);
+    REGT_CHECK_ARG(d->tnorm_group >= 1 && d->batch % d->tnorm_group == 0, "%s: tnorm_group %d must divide batch %d", what,
+                   d->tnorm_group, d->batch);
+    REGT_CHECK_ARG(d->in_dim >= 1 && d->in_dim <= regt::ST_MAX_CH && d->out_dim >= 1 && d->out_dim <= regt::ST_MAX_CH,
+                   "%s: in_dim and out_dim must be in [1, %d], got %d, %d", what, regt::ST_MAX_CH, d->in_dim, d->out_dim);
+    REGT_CHECK_ARG(d->blocks >= 1 && d->layers >= 1 && d->layers <= 8 && (long)d->blocks * d->layers <= 64,
+                   "%s: need 1 <= layers <= 8 and 1 <= blocks * layers <= 64, got blocks %d layers %d", what, d->blocks, d->layers);
+    *s = regt::StnDims{d->num_nodes, d->batch, d->tnorm_group, d->seq_len, d->in_dim, d->out_dim, d->blocks, d->layers,
+                       d->tnorm ? 1 : 0, d->snorm ? 1 : 0, d->training ? 1 : 0};
+    return REGT_OK;
+}
+
+static int stnorm_check_params(const char* what, const regt::StnDims& s, const void* const* p, const void* const* run, bool need_run) {
+    REGT_CHECK_ARG(p != nullptr, "%s: parameter table is NULL", what);
+    for (int k = 0; k < regt::ST_HEAD_PARAMS; ++k) REGT_CHECK_ARG(p[k] != nullptr, "%s: head entry %d is NULL", what, k);
+    for (int i = 0; i < s.blocks * s.layers; ++i) {
+        const void* const* q = p + regt::ST_HEAD_PARAMS + regt::ST_LAYER_PARAMS * i;
+        for (int k = 0; k < 8; ++k) REGT_CHECK_ARG(q[k] != nullptr, "%s: layer %d entry %d is NULL", what, i, k);
+        if (s.tnorm) REGT_CHECK_ARG(q[8] && q[9], "%s: layer %d TNorm gamma / beta is NULL", what, i);
+        if (s.snorm) REGT_CHECK_ARG(q[10] && q[11], "%s: layer %d SNorm gamma / beta is NULL", what, i);
+        if (s.tnorm && run) REGT_CHECK_ARG(run[2 * i] && run[2 * i + 1], "%s: layer %d running buffers are NULL", what, i);
+    }
+    if (s.tnorm && need_run) REGT_CHECK_ARG(run != nullptr, "%s: running-buffer table is NULL", what);
+    return REGT_OK;
+}
+
+int32_t regt_stnorm_sizes(const regt_stnorm_dims* d, size_t* ws, size_t* scratch) {
+    regt::StnDims s;
+    if (int rc = stnorm_check("regt_stnorm_sizes", d, &s)) return rc;
+    REGT_CHECK_ARG(regt::stnorm_sizes(s, ws, scratch), "regt_stnorm_sizes: unsupported dims");
+    return REGT_OK;
+}
+
+int32_t regt_stnorm_forward(const regt_stnorm_dims* d, const float* x, const float* const* params, float* const* running, float* out,
+                            float* ws, regt_stream_t st) {
+    regt::StnDims s;
+    if (int rc = stnorm_check("regt_stnorm_forward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && out && ws, "regt_stnorm_forward: NULL pointer");
+    if (int rc = stnorm_check_params("regt_stnorm_forward", s, reinterpret_cast<const void* const*>(params),
+                                     reinterpret_cast<const void* const*>(running), true))
+        return rc;
+    return regt::launch_stnorm_fwd(s, x, params, running, out, ws, (hipStream_t)st);
+}
+
+int32_t regt_stnorm_backward(const regt_stnorm_dims* d, const float* x, const float* const* params, float* const* running,
+                             const float* dout, float* const* grads, const float* ws, float* scratch, regt_stream_t st) {
+    regt::StnDims s;
+    if (int rc = stnorm_check("regt_stnorm_backward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && dout && grads && ws && scratch, "regt_stnorm_backward: NULL pointer");
+    if (int rc = stnorm_check_params("regt_stnorm_backward", s, reinterpret_cast<const void* const*>(params),
+                                     reinterpret_cast<const void* const*>(running), true))
+        return rc;
+    if (int rc = stnorm_check_params("regt_stnorm_backward (grads)", s, reinterpret_cast<const void* const*>(grads), nullptr, false)) return rc;
+    return regt::launch_stnorm_bwd(s, x, params, running, dout, grads, ws, scratch, (hipStream_t)st);
+}
+
 int64_t regt_debug_trace(int64_t* out_host, int64_t capacity) { return fused_trace_fetch(reinterpret_cast<long*>(out_host), (long)capacity); }
 
 int32_t regt_profile_enable(int32_t on) {

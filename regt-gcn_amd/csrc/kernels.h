@@ -357,6 +357,16 @@ int launch_spatial_fwd(const float* x, const float* lx, const float* w0, const f
 int launch_spatial_bwd(const float* x, const float* lx, const float* w0, const float* w1, const float* b, const uint32_t* keep,
                        const float* dS, int N, int T, int F, float* dw0, float* dw1, float* db, float* slab, hipStream_t st);
 
+// STNorm (stnorm.hip): the whole model, one launch per layer plus the SNorm seams.  Parameter / gradient pointer tables: the
+// ST_HEAD_PARAMS head entries (start_conv w, b, end_conv_1 w, b, end_conv_2 w, b), then ST_LAYER_PARAMS per layer (filter w, b,
+// gate w, b, residual w, b, skip w, b, tn gamma, beta, sn gamma, beta; NULL where TNorm / SNorm is off).  run: 2 per layer.
+struct StnDims { int num_nodes, batch, tnorm_group, seq_len, in_dim, out_dim, blocks, layers, tnorm, snorm, training; };
+constexpr int ST_MAX_CH = 256, ST_HEAD_PARAMS = 6, ST_LAYER_PARAMS = 12;
+bool stnorm_sizes(const StnDims& s, size_t* ws_floats, size_t* scratch_floats);
+int launch_stnorm_fwd(const StnDims& s, const float* x, const float* const* P, float* const* run, float* out, float* ws, hipStream_t st);
+int launch_stnorm_bwd(const StnDims& s, const float* x, const float* const* P, float* const* run, const float* dout, float* const* G,
+                      const float* ws, float* scratch, hipStream_t st);
+
 // hipFuncSetAttribute is a (slow, host-synchronous) driver call: do it once per kernel, not per launch.
 template <class K>
 static int set_lds_once(K kernel, int bytes, bool* done) {

@@ -602,6 +602,48 @@ class SpatialEmbedFunction(torch.autograd.Function):
         return None, None, dw0, dw1, db, None
 
 
+class STNormFunction(torch.autograd.Function):
+    """(x (B, L, N, C_in), dims, running, *params) -> out (B, O, N, L_out): the whole STNorm forward and backward in HIP
+    (regt_stnorm_forward / regt_stnorm_backward; ``params`` in their table order, None where TNorm / SNorm is off).  The forward
+    keeps the layer inputs and SNorm statistics in its workspace for the backward, which allocates its own scratch and recomputes
+    the rest; in training mode the
+    forward updates ``running`` in place.  x is data: no dx.  Honours :func:`set_grad_accumulation_in_backward`."""
+
+    @staticmethod
+    def forward(ctx, x, dims, running, *params):
+        from . import ops
+        out, ws = ops.stnorm_forward(dims, x, params, running)
+        ctx.dims, ctx.running, ctx.ws = dims, running, ws
+        ctx.leaf_params = params
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import ops
+        (x,) = ctx.saved_tensors
+        params = ctx.leaf_params
+        grads = ops.stnorm_backward(ctx.dims, x, [None if p is None else p.detach() for p in params], ctx.running,
+                                    dout.contiguous(), ctx.ws)
+        ctx.ws = None
+        # the last layer's residual conv feeds nothing: None, as autograd gives the reference module (no weight decay step either)
+        last = ops.STNORM_HEAD + ops.STNORM_PER_LAYER * (ctx.dims.blocks * ctx.dims.layers - 1)
+        grads[last + 4] = grads[last + 5] = None
+        live = [(p, g) for p, g in zip(params, grads) if p is not None and g is not None]
+        if _ACCUMULATE_IN_BACKWARD and all(p.is_leaf and p.requires_grad for p, _ in live):
+            have, new = [], []
+            for p, g in live:
+                if p.grad is None:
+                    p.grad = g
+                else:
+                    have.append(p.grad)
+                    new.append(g)
+            if have:
+                torch._foreach_add_(have, new)
+            return (None, None, None) + (None,) * len(params)
+        return (None, None, None) + tuple(grads)
+
+
 class ZeroGradAnchor(torch.autograd.Function):
     """Identity on ``(pred, hidden)`` that gives ``dead`` parameters an all-zero gradient: in the reference's GraphSAGE / GAT models
     the reset gate is computed and multiplied by the zero hidden state, so autograd hands its parameters zeros, not None --

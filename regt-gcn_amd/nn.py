@@ -9,6 +9,7 @@ unchanged:
 * :class:`ConvStackedTemporalGCN` <-> models/ConvStackedTemporalGCN.py:8-33 (+ ConvStackedA3TGCN :35-126)
 * :class:`TGCN`                 <-> models/utils.py:69-203 (parameter container of the GRU cell)
 * :class:`SpatialGCN`           <-> models/SpatialGCN.py:8-49
+* :class:`STNorm`               <-> models/STNorm.py:6-185
 
 The modules only *hold* parameters; all arithmetic runs in libregtgcn_hip.so through
 :class:`regt-gcn_amd.functional.RegTGCNFunction`.  There is no CPU implementation here: calling
@@ -25,7 +26,7 @@ import torch.nn as nn
 from . import _lib
 from . import ops
 from .functional import (HEAD_HIDDEN, PARAM_NAMES_CELL, AggregateFunction, Cell0Function, CellFunction, GatAggregateFunction,
-                         LinearFunction, RegTGCNFunction, SpatialEmbedFunction, ZeroGradAnchor, param_names)
+                         LinearFunction, RegTGCNFunction, SpatialEmbedFunction, STNormFunction, ZeroGradAnchor, param_names)
 from .graph import (AttentionPattern, GcnOperator, MeanOperator, PreparedGraph, fingerprint, prepare_attention_pattern,
                     prepare_cheb_operator, prepare_gcn_operator, prepare_graph, prepare_mean_operator)
 
@@ -651,3 +652,106 @@ class SpatialGCN(nn.Module):
         n = x.shape[0]
         op = self._graphs.get([edge_index, edge_attr], n, lambda: prepare_cheb_operator(edge_index, edge_attr, n))
         return self.forward_prepared(x, op)
+
+
+# ---- STNorm (models/STNorm.py) ---------------------------------------------------------------------------------------------------------
+
+class _SNormParams(nn.Module):
+    """SNorm's parameters (models/STNorm.py:6-19): beta, gamma (channels,)."""
+
+    def __init__(self, channels: int):
+        super().__init__()
+        self.beta = nn.Parameter(torch.zeros(channels))
+        self.gamma = nn.Parameter(torch.ones(channels))
+
+
+class _TNormParams(nn.Module):
+    """TNorm's parameters and running statistics (models/STNorm.py:22-57): beta, gamma, running_mean, running_var (1, C, N, 1)."""
+
+    def __init__(self, num_nodes: int, channels: int, momentum: float = 0.1):
+        super().__init__()
+        self.beta = nn.Parameter(torch.zeros(1, channels, num_nodes, 1))
+        self.gamma = nn.Parameter(torch.ones(1, channels, num_nodes, 1))
+        self.register_buffer("running_mean", torch.zeros(1, channels, num_nodes, 1))
+        self.register_buffer("running_var", torch.ones(1, channels, num_nodes, 1))
+        self.momentum = momentum
+
+
+class STNorm(nn.Module):
+    """STNorm (models/STNorm.py:60-185): the reference's constructor, ``forward(input (B, L, N, C_in)) -> (B, out_dim, N, L_out)`` and
+    state_dict.  All arithmetic runs in regt_stnorm_forward / regt_stnorm_backward; ``nn.Conv2d`` modules only hold the weights, and
+    are created in the reference's order so that a seeded construction draws the same initial values.
+
+    ``tnorm_group`` (forward keyword): TNorm pools its statistics over groups of that many consecutive batch elements.  The default,
+    the whole batch, is the reference's semantics; ``tnorm_group=1`` makes a batch of B snapshots equal to B sequential calls with
+    B = 1 (the running buffers are updated once per snapshot, in order) -- what snapshot batching in ``train.py`` uses."""
+
+    def __init__(self, num_nodes, tnorm_bool=True, snorm_bool=True, in_dim=1, out_dim=12, channels=16, kernel_size=2, blocks=4, layers=2):
+        super().__init__()
+        if channels != ops.STNORM_CHANNELS or kernel_size != 2:
+            raise ValueError(f"STNorm runs with channels={ops.STNORM_CHANNELS} and kernel_size=2 only, got {channels}, {kernel_size}")
+        if not 1 <= in_dim <= ops.STNORM_MAX_DIM or not 1 <= out_dim <= ops.STNORM_MAX_DIM:
+            raise ValueError(f"STNorm runs with 1 <= in_dim, out_dim <= {ops.STNORM_MAX_DIM}, got {in_dim}, {out_dim}")
+        self.num_nodes, self.in_dim, self.out_dim = num_nodes, in_dim, out_dim
+        self.blocks, self.layers = blocks, layers
+        self.snorm_bool, self.tnorm_bool = snorm_bool, tnorm_bool
+        self.filter_convs = nn.ModuleList()
+        self.gate_convs = nn.ModuleList()
+        self.residual_convs = nn.ModuleList()
+        self.skip_convs = nn.ModuleList()
+        if snorm_bool:
+            self.sn = nn.ModuleList()
+        if tnorm_bool:
+            self.tn = nn.ModuleList()
+        wide = (1 + int(tnorm_bool) + int(snorm_bool)) * channels
+        self.start_conv = nn.Conv2d(in_dim, channels, kernel_size=(1, 1))
+        rf = 1
+        for _ in range(blocks):
+            scope, dilation = kernel_size - 1, 1
+            for _ in range(layers):
+                if tnorm_bool:
+                    self.tn.append(_TNormParams(num_nodes, channels))
+                if snorm_bool:
+                    self.sn.append(_SNormParams(channels))
+                self.filter_convs.append(nn.Conv2d(wide, channels, kernel_size=(1, kernel_size), dilation=dilation))
+                self.gate_convs.append(nn.Conv2d(wide, channels, kernel_size=(1, kernel_size), dilation=dilation))
+                self.residual_convs.append(nn.Conv2d(channels, channels, kernel_size=(1, 1)))
+                self.skip_convs.append(nn.Conv2d(channels, channels, kernel_size=(1, 1)))
+                dilation *= 2
+                rf += scope
+                scope *= 2
+        self.end_conv_1 = nn.Conv2d(channels, channels, kernel_size=(1, 1), bias=True)
+        self.end_conv_2 = nn.Conv2d(channels, out_dim, kernel_size=(1, 1), bias=True)
+        self.receptive_field = rf
+
+    def param_table(self):
+        """The parameters in the table order of regt_stnorm_forward (None where TNorm / SNorm is off)."""
+        t = [self.start_conv.weight, self.start_conv.bias, self.end_conv_1.weight, self.end_conv_1.bias, self.end_conv_2.weight,
+             self.end_conv_2.bias]
+        for i in range(self.blocks * self.layers):
+            t += [self.filter_convs[i].weight, self.filter_convs[i].bias, self.gate_convs[i].weight, self.gate_convs[i].bias,
+                  self.residual_convs[i].weight, self.residual_convs[i].bias, self.skip_convs[i].weight, self.skip_convs[i].bias]
+            t += [self.tn[i].gamma, self.tn[i].beta] if self.tnorm_bool else [None, None]
+            t += [self.sn[i].gamma, self.sn[i].beta] if self.snorm_bool else [None, None]
+        return t
+
+    def running_table(self):
+        r = []
+        if self.tnorm_bool:
+            for m in self.tn:
+                r += [m.running_mean, m.running_var]
+        return r
+
+    def forward(self, input: torch.Tensor, tnorm_group: Optional[int] = None) -> torch.Tensor:
+        _need_cuda(input)
+        if input.dim() != 4 or input.shape[2] != self.num_nodes or input.shape[3] != self.in_dim:
+            raise ValueError(f"input must be (B, L, {self.num_nodes}, {self.in_dim}), got {tuple(input.shape)}")
+        b, l = input.shape[0], input.shape[1]
+        group = b if tnorm_group is None else int(tnorm_group)
+        dims = ops.stnorm_dims(self.num_nodes, b, group, l, self.in_dim, self.out_dim, self.blocks, self.layers, self.tnorm_bool,
+                               self.snorm_bool, self.training)
+        params = self.param_table()
+        ops.stnorm_check_tables(dims, input.device, params, self.running_table())   # raw pointers: device, dtype, shape, layout
+        if input.dtype != torch.float32:
+            raise _lib.RegtError(f"STNorm input must be float32, got {input.dtype}")
+        return STNormFunction.apply(input.contiguous(), dims, self.running_table(), *params)

@@ -2,6 +2,7 @@
 reference-side binding shown in INTEGRATION.md).  No arithmetic happens in Python."""
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -194,3 +195,100 @@ def spatial_embed_backward(xp: torch.Tensor, lxp: torch.Tensor, w0: torch.Tensor
                                                _keep_ptr(keep, n * t, xp.device), _lib.ptr(ds), n, t, f, _lib.ptr(dw0), _lib.ptr(dw1),
                                                _lib.ptr(db), _lib.ptr(slab), _stream()), "regt_spatial_embed_backward")
     return dw0, dw1, db
+
+
+# ---- STNorm (models/STNorm.py) -------------------------------------------------------------------------------------------------------
+
+STNORM_CHANNELS = 16         # channels the kernels are built for (models/STNorm.py default)
+STNORM_HEAD, STNORM_PER_LAYER = 6, 12
+STNORM_MAX_DIM = 256         # in_dim / out_dim: the LDS rows of the start-conv and head backward kernels (include/regtgcn.h)
+
+
+def stnorm_dims(n: int, batch: int, tnorm_group: int, seq_len: int, in_dim: int, out_dim: int, blocks: int, layers: int,
+                tnorm: bool, snorm: bool, training: bool) -> _lib.StnormDims:
+    return _lib.StnormDims(n, batch, tnorm_group, seq_len, in_dim, out_dim, blocks, layers, int(bool(tnorm)), int(bool(snorm)),
+                           int(bool(training)))
+
+
+def stnorm_sizes(dims: _lib.StnormDims):
+    """(workspace floats, scratch floats) of regt_stnorm_forward / _backward."""
+    ws, sc = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(_lib.load().regt_stnorm_sizes(ctypes.byref(dims), ctypes.byref(ws), ctypes.byref(sc)), "regt_stnorm_sizes")
+    return ws.value, sc.value
+
+
+def _ptr_table(tensors):
+    return (ctypes.c_void_p * max(1, len(tensors)))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def stnorm_out_len(seq_len: int, blocks: int, layers: int) -> int:
+    rf = 1 + blocks * ((1 << layers) - 1)
+    return max(seq_len, rf) - rf + 1
+
+
+def stnorm_table_shapes(dims: _lib.StnormDims):
+    """Expected shapes of the parameter table (None where the entry must be None) and of the running-buffer table."""
+    c, n, k = STNORM_CHANNELS, dims.num_nodes, (1 + bool(dims.tnorm) + bool(dims.snorm)) * STNORM_CHANNELS
+    shapes = [(c, dims.in_dim, 1, 1), (c,), (c, c, 1, 1), (c,), (dims.out_dim, c, 1, 1), (dims.out_dim,)]
+    running = []
+    for _ in range(dims.blocks * dims.layers):
+        shapes += [(c, k, 1, 2), (c,), (c, k, 1, 2), (c,), (c, c, 1, 1), (c,), (c, c, 1, 1), (c,)]
+        shapes += [(1, c, n, 1)] * 2 if dims.tnorm else [None, None]
+        shapes += [(c,)] * 2 if dims.snorm else [None, None]
+        running += [(1, c, n, 1)] * 2 if dims.tnorm else []
+    return shapes, running
+
+
+def stnorm_check_tables(dims: _lib.StnormDims, device, params, running, what: str = "STNorm"):
+    """RegtError unless every parameter and running buffer is a contiguous float32 tensor of its reference shape on ``device``:
+    the kernels read them through raw device pointers."""
+    shapes, rshapes = stnorm_table_shapes(dims)
+    if len(params) != len(shapes) or len(running) != len(rshapes):
+        raise _lib.RegtError(f"{what}: expected {len(shapes)} parameter and {len(rshapes)} buffer entries, got {len(params)}, {len(running)}")
+    for kind, tabs, exp in (("parameter", params, shapes), ("running buffer", running, rshapes)):
+        for i, (t, shape) in enumerate(zip(tabs, exp)):
+            if shape is None:
+                if t is not None:
+                    raise _lib.RegtError(f"{what}: {kind} entry {i} must be None (TNorm / SNorm off)")
+                continue
+            if t is None or not isinstance(t, torch.Tensor):
+                raise _lib.RegtError(f"{what}: {kind} entry {i} is missing")
+            if t.dtype != torch.float32 or t.device != torch.device(device) or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise _lib.RegtError(f"{what}: {kind} entry {i} must be a contiguous float32 {shape} tensor on {device}, got "
+                                     f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else " (not contiguous)"))
+
+
+def stnorm_forward(dims: _lib.StnormDims, x: torch.Tensor, params, running):
+    """out (B, O, N, L_out) of STNorm for x (B, L, N, C_in); ``params`` in the table order of regt_stnorm_forward (None where TNorm /
+    SNorm is off), ``running`` [rm_0, rv_0, rm_1, ...] (updated in place in training mode).  Returns (out, workspace): the workspace
+    holds what regt_stnorm_backward reads."""
+    x = _f32c(x, "x")
+    if tuple(x.shape) != (dims.batch, dims.seq_len, dims.num_nodes, dims.in_dim):
+        raise ValueError(f"x must be ({dims.batch}, {dims.seq_len}, {dims.num_nodes}, {dims.in_dim}), got {tuple(x.shape)}")
+    stnorm_check_tables(dims, x.device, params, running, "regt_stnorm_forward")
+    ws_n, _ = stnorm_sizes(dims)
+    out = torch.empty(dims.batch, dims.out_dim, dims.num_nodes, stnorm_out_len(dims.seq_len, dims.blocks, dims.layers),
+                      dtype=torch.float32, device=x.device)
+    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
+    pt, rt = _ptr_table(params), _ptr_table(running)
+    _lib.check(_lib.load().regt_stnorm_forward(ctypes.byref(dims), _lib.ptr(x), pt, rt if dims.tnorm else None, _lib.ptr(out),
+                                               _lib.ptr(ws), _stream()), "regt_stnorm_forward")
+    return out, ws
+
+
+def stnorm_backward(dims: _lib.StnormDims, x: torch.Tensor, params, running, dout: torch.Tensor, ws: torch.Tensor):
+    """Gradients of every entry of ``params`` (None where the entry is None) from dL/dout; ``ws`` is the forward's workspace."""
+    x, dout = _f32c(x, "x"), _f32c(dout, "dout")
+    stnorm_check_tables(dims, x.device, params, running, "regt_stnorm_backward")
+    ws_n, sc_n = stnorm_sizes(dims)
+    out_shape = (dims.batch, dims.out_dim, dims.num_nodes, stnorm_out_len(dims.seq_len, dims.blocks, dims.layers))
+    if tuple(dout.shape) != out_shape or dout.device != x.device:
+        raise ValueError(f"dout must be {out_shape} on {x.device}, got {tuple(dout.shape)} on {dout.device}")
+    if ws.dtype != torch.float32 or ws.device != x.device or ws.numel() != ws_n or not ws.is_contiguous():
+        raise ValueError("ws must be the workspace stnorm_forward returned for these dims")
+    sc = torch.empty(sc_n, dtype=torch.float32, device=x.device)
+    grads = [None if p is None else torch.empty_like(p) for p in params]
+    pt, rt, gt = _ptr_table(params), _ptr_table(running), _ptr_table(grads)
+    _lib.check(_lib.load().regt_stnorm_backward(ctypes.byref(dims), _lib.ptr(x), pt, rt if dims.tnorm else None, _lib.ptr(dout), gt,
+                                                _lib.ptr(ws), _lib.ptr(sc), _stream()), "regt_stnorm_backward")
+    return grads

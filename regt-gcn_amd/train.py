@@ -191,11 +191,59 @@ def split(xs, ys, ratio: float):
     return (xs[:k], ys[:k]), (xs[k:], ys[k:])
 
 
-# graph models of run.py:115-136: those built on the TGCN cell (the hot path and the SURVEY 8(f) baselines) and SpatialGCN (two
-# ChebConv layers, run.py:117-118); TemporalGConvLSTM (which run.py:122 cannot construct), StackedGRU, STAEformer, STID and STNorm
-# are out of scope
+# models of run.py:115-136: those built on the TGCN cell (the hot path and the SURVEY 8(f) baselines), SpatialGCN (two ChebConv
+# layers, run.py:117-118) and STNorm (gated dilated convolutions with temporal / spatial normalisation, no graph, run.py:135-136);
+# TemporalGConvLSTM (which run.py:122 cannot construct), StackedGRU, STAEformer and STID are out of scope
 MODELS = ("RegionalTemporalGCN", "RandomTemporalGCN", "TemporalGCN", "ConvStackedTemporalGCN", "GraphSAGETemporalGCN", "GAT", "GATTemporal",
-          "SpatialGCN")
+          "SpatialGCN", "STNorm")
+
+
+# ---- STNorm (run.py:181-184, 217-221) -------------------------------------------------------------------------------------------------
+# run.py feeds STNorm batch.x.permute(2, 0, 1).unsqueeze(0) -- (1, T, N, F) -- and takes mean((out - y)**2) with out (1, O, N, L_out)
+# and y (N, O): for O > 1 that broadcasts to (1, O, N, O), kept as it is.  test() compares out[0][0] (N, L_out) with y (N, O).  A
+# batch of B snapshots runs as one (B, T, N, F) call with tnorm_group = 1: TNorm's statistics and running-buffer updates stay per
+# snapshot, in snapshot order, so the losses, the accumulated gradients and the buffers are those of B sequential run.py steps.
+
+def stnorm_batch(store: "WindowStore", i: int, b: int):
+    """Snapshots i .. i+b-1 as STNorm's input (b, T, N, F) and their targets (b, N, O)."""
+    return store.X[i:i + b].permute(0, 3, 1, 2), store.Y[i:i + b]
+
+
+def train_epoch_stnorm(model, store: "WindowStore", optimizer, snap_batch: int) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """run.py::train() for STNorm; returns (last snapshot's loss, all per-snapshot losses)."""
+    model.train()
+    losses = []
+    prev = F_.set_grad_accumulation_in_backward(True)
+    try:
+        for i in range(0, len(store), snap_batch):
+            b = min(snap_batch, len(store) - i)
+            x, y = stnorm_batch(store, i, b)
+            out = model(x, tnorm_group=1)
+            per = ((out - y.unsqueeze(1)) ** 2).mean(dim=(1, 2, 3))       # run.py:184 per snapshot
+            per.sum().backward()
+            losses.append(per.detach())
+    finally:
+        F_.set_grad_accumulation_in_backward(prev)
+    optimizer.step()
+    optimizer.zero_grad()
+    all_l = torch.cat(losses)
+    return all_l[-1], list(all_l.unbind(0))
+
+
+@torch.no_grad()
+def evaluate_stnorm(model, store: "WindowStore", snap_batch: int) -> Tuple[float, float]:
+    """run.py::test() for STNorm: (rmse, mse) of out[0][0] against y."""
+    model.eval()
+    se = torch.zeros((), dtype=torch.float64, device=store.X.device)
+    count = 0
+    for i in range(0, len(store), snap_batch):
+        b = min(snap_batch, len(store) - i)
+        x, y = stnorm_batch(store, i, b)
+        e = (model(x, tnorm_group=1)[:, 0] - y) ** 2
+        se += e.sum(dtype=torch.float64)
+        count += e.numel()
+    m = float(se) / float(max(count, 1))
+    return m ** 0.5, m
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -292,6 +340,14 @@ def main(argv=None):
     elif a.model == "SpatialGCN":                                           # run.py:117-118
         model = rnn.SpatialGCN(f, a.num_timesteps_in, a.num_timesteps_out).to(dev)
         graph = model.prepare_graph(ei, ea, n)
+    elif a.model == "STNorm":                                               # run.py:135-136 (in_dim = F of the data)
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("STNorm runs on one GPU: SNorm normalises over all nodes in every layer, and sharding the nodes would "
+                             "need one all-reduce per layer")
+        if a.fused_step:
+            raise SystemExit("--fused_step covers RegionalTemporalGCN (regional decomposition) / TemporalGCN")
+        model = rnn.STNorm(num_nodes=n, in_dim=f, out_dim=a.num_timesteps_out).to(dev)
+        graph = None
     elif a.model == "GraphSAGETemporalGCN":                                 # run.py:127-128
         model = rnn.GraphSAGETemporalGCN(f, n, a.num_timesteps_in, a.num_timesteps_out).to(dev)
         graph = model.prepare_graph(ei, n)
@@ -309,6 +365,13 @@ def main(argv=None):
         os.makedirs("logs", exist_ok=True)
         log = open(os.path.join("logs", datetime.datetime.now().strftime("%y-%m-%d_%H-%M") + ".txt"), "a")
     batched = None
+    if a.model == "STNorm":
+        from_store = (WindowStore(tx, ty), WindowStore(vx, vy))
+        for epoch in range(a.epochs + 1):
+            last, _ = train_epoch_stnorm(model, from_store[0], opt, max(1, a.snap_batch))
+            rmse, mse = evaluate_stnorm(model, from_store[1], max(1, a.snap_batch))
+            _report(a, log, out_dir, model, epoch, last, rmse, mse)
+        return
     if a.snap_batch > 1:
         if a.fused_step:
             raise SystemExit("--snap_batch and --fused_step are alternatives (both remove per-snapshot host work)")
@@ -334,14 +397,18 @@ def main(argv=None):
         else:
             last, _ = train_epoch(model, tx, ty, graph, opt, stepper)
             rmse, mse = evaluate(model, vx, vy, graph)
-        line = "Train Loss: {:.4f}, Test RMSE: {:.4f}, MAE: {:.4f}".format(float(last), rmse, mse)   # run.py:236 format
-        print(line)
-        if log:
-            log.write(line + "\n")
-            log.flush()
-        if epoch % 10 == 0:
-            torch.save(model.state_dict(), os.path.join(out_dir, "model_in{}_out{}_epoch{}.pt".format(
-                a.num_timesteps_in, a.num_timesteps_out, int(a.pretrained_model_epoch) + epoch)))
+        _report(a, log, out_dir, model, epoch, last, rmse, mse)
+
+
+def _report(a, log, out_dir, model, epoch, last, rmse, mse):
+    line = "Train Loss: {:.4f}, Test RMSE: {:.4f}, MAE: {:.4f}".format(float(last), rmse, mse)   # run.py:236 format
+    print(line)
+    if log:
+        log.write(line + "\n")
+        log.flush()
+    if epoch % 10 == 0:
+        torch.save(model.state_dict(), os.path.join(out_dir, "model_in{}_out{}_epoch{}.pt".format(
+            a.num_timesteps_in, a.num_timesteps_out, int(a.pretrained_model_epoch) + epoch)))
 
 
 if __name__ == "__main__":

@@ -1,0 +1,294 @@
+"""STNorm on the GPU: the reference module's goldens (training forward / backward with the running buffers, eval with the updated
+buffers, a three-snapshot RMSprop trajectory), the kernels against the float64 restatement over lengths, batch pooling, node counts
+and switches, bit-reproducible gradients, snapshot batching and the command lines.
+
+Tolerances, all absolute.  Against the reference goldens: 1e-5 on outputs, losses, gradients and buffers (the fp32-vs-float64 gap
+of the restatement on the goldens is below GRAD_GAP = 4e-6, tests/test_stnorm_cpu.py) and 1e-3 on MAPE, which predict.py scales by
+100.  After the RMSprop step: the bound of test_three_snapshot_trajectory_matches_reference_golden.  Against the float64
+restatement: 1e-5 + 4 x the fp32-vs-float64 gap of the same restatement evaluated in fp32 on the same inputs, per tensor.  That
+gap is what a normalisation amplifies: where left padding gives every node the same start_conv bias, SNorm's spread is 0 and its
+1/sqrt(1e-5) multiplies rounding by 316, and the start_conv bias gradient is then a sum that cancels to ~0.  The factor 4 is the
+summation-order allowance: torch reduces in pairwise blocks (error growth ~log n), while the kernels add each thread's columns
+and each wave's partials in sequence (growth up to ~n over those short runs); at T = 3, B = 2 the kernels' start_conv.bias error
+is 1.5e-4 against a fp32 restatement gap between 3.5e-5 and 7e-5: 2x is too tight for it, 4x holds."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_npz
+from stnorm_math import stnorm
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TAGS = ["in6_out1", "in12_out3"]
+DEV = "cuda:0"
+GRAD_GAP = 4e-6
+
+
+def _golden(tag):
+    g = load_npz(f"golden_stnorm_{tag}.npz")
+    return g, [str(k) for k in g["state_dict_keys"]]
+
+
+def _module(g, keys, **kw):
+    import regtgcn_amd as R
+    mod = R.STNorm(num_nodes=g["x"].shape[2], in_dim=8, out_dim=int(g["t_out"]), **kw)
+    mod.load_state_dict({k: torch.from_numpy(g[f"p__{k}"]) for k in keys})
+    return mod.to(DEV)
+
+
+def _close(a, b, atol=1e-5, rtol=0.0, what=""):
+    a = a.detach().cpu().double().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64)
+    np.testing.assert_allclose(a, np.asarray(b, dtype=np.float64), atol=atol, rtol=rtol, err_msg=what)
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_train_mode_matches_reference_golden(tag):
+    g, keys = _golden(tag)
+    mod = _module(g, keys).train()
+    x, y = torch.from_numpy(g["x"]).to(DEV), torch.from_numpy(g["y"]).to(DEV)
+    out = mod(x)
+    loss = torch.mean((out - y) ** 2)
+    loss.backward()
+    _close(out, g["train__out"], what="out")
+    _close(loss, g["train__loss"][0], what="loss")
+    gnone = {str(k) for k in g["train__gnone"]}
+    for k, p in mod.named_parameters():
+        if k in gnone:
+            assert p.grad is None, k
+        else:
+            _close(p.grad, g[f"train__g__{k}"], what=k)
+    for k, b in mod.named_buffers():
+        _close(b, g[f"train__b__{k}"], what=k)
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_eval_mode_and_metrics_match_reference_golden(tag):
+    from regtgcn_amd.evaluate import predict_metrics_stnorm
+    g, keys = _golden(tag)
+    mod = _module(g, keys)
+    mod.load_state_dict({**{k: torch.from_numpy(g[f"p__{k}"]) for k in keys},
+                         **{k: torch.from_numpy(g[f"train__b__{k}"]) for k, _ in mod.named_buffers()}})
+    mod.eval()
+    x, y = torch.from_numpy(g["x"]).to(DEV), torch.from_numpy(g["y"]).to(DEV)
+    with torch.no_grad():
+        out = mod(x)
+    _close(out, g["eval__out"], what="eval out")
+    _close(((out[0][0] - y) ** 2).mean(), g["eval__test_mse"][0])
+    xs = [torch.from_numpy(g["x"][0]).permute(1, 2, 0).to(DEV)]              # back to the (N, F, T) snapshot
+    mae, rmse, mape = predict_metrics_stnorm(mod, xs, [y])
+    _close(mae, g["eval__mae"][0])
+    _close(rmse, np.sqrt(g["eval__mse"][0]))
+    _close(mape, g["eval__mape"][0], atol=1e-3)
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_three_snapshot_trajectory_matches_reference_golden(tag, tpims):
+    from regtgcn_amd import functional as F_
+    g, keys = _golden(tag)
+    mod = _module(g, keys).train()
+    t_in, t_out, w, n = int(g["t_in"]), int(g["t_out"]), int(g["window"]), int(g["nodes"])
+    opt = torch.optim.RMSprop(mod.parameters(), lr=1e-3, weight_decay=1e-4)
+    losses = []
+    prev = F_.set_grad_accumulation_in_backward(True)
+    try:
+        for k in range(3):
+            x = tpims["node_data"][:n, :, w + k:w + k + t_in].permute(2, 0, 1).unsqueeze(0).contiguous().to(DEV)
+            y = tpims["node_data"][:n, -1, w + k + t_in:w + k + t_in + t_out].contiguous().to(DEV)
+            loss = torch.mean((mod(x) - y) ** 2)
+            loss.backward()
+            losses.append(float(loss.detach()))
+    finally:
+        F_.set_grad_accumulation_in_backward(prev)
+    opt.step()
+    _close(losses, g["traj__loss"])
+    # RMSprop's first step is -lr g' / (sqrt(0.01 g'^2) + 1e-8), g' = g + wd p: where g' is tiny it amplifies a gradient error dg by
+    # lr 1e-8 / (0.1 |g'| + 1e-8)^2.  The bound per element takes g' from the float64 restatement and dg = GRAD_GAP, the largest
+    # fp32-vs-float64 gradient gap of the restatement on the goldens (tests/test_stnorm_cpu.py)
+    ref = {k: torch.from_numpy(g[f"p__{k}"]).double() for k in keys}
+    for k in ref:
+        if "running" not in k:
+            ref[k].requires_grad_(True)
+    for k in range(3):
+        x = tpims["node_data"][:n, :, w + k:w + k + t_in].permute(2, 0, 1).unsqueeze(0).contiguous()
+        y = tpims["node_data"][:n, -1, w + k + t_in:w + k + t_in + t_out].double()
+        ro, rb = stnorm(ref, x)
+        torch.mean((ro - y) ** 2).backward()
+        for name, v in rb.items():
+            ref[name] = v
+    # the golden stores the step as an fp16 delta: half an fp16 ulp of each stored value joins the bound
+    for k, p in mod.named_parameters():
+        dp = g[f"traj__dp__{k}"]
+        half_ulp = np.spacing(np.abs(dp)).astype(np.float64) / 2
+        target = g[f"p__{k}"].astype(np.float64) + dp.astype(np.float64)
+        err = np.abs(p.detach().cpu().double().numpy() - target)
+        if ref[k].grad is None:
+            assert (err <= 1e-5 + half_ulp).all(), (k, float(err.max()))
+            continue
+        gp = (ref[k].grad + 1e-4 * ref[k].detach()).abs().numpy()
+        bound = 1e-5 + half_ulp + 1e-3 * 1e-8 * GRAD_GAP / (0.1 * gp + 1e-8) ** 2
+        assert (err <= bound).all(), (k, float(err.max()))
+    for k, b in mod.named_buffers():
+        _close(b, g[f"traj__b__{k}"], what=k)
+
+
+def _random_params(mod, seed):
+    gen = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, p in mod.named_parameters():
+            if name.endswith("bias") or name.endswith("beta"):
+                p.copy_((torch.rand(p.shape, generator=gen) - 0.5) * 0.4)
+            elif name.endswith("gamma"):
+                p.copy_(1 + (torch.rand(p.shape, generator=gen) - 0.5) * 0.4)
+        for name, b in mod.named_buffers():
+            b.copy_(torch.rand(b.shape, generator=gen) * 0.5 + (0.75 if name.endswith("var") else -0.25))
+
+
+def _against_restatement(n, b, t, c_in, o, seed=0, training=True, tnorm_group=None, **kw):
+    import regtgcn_amd as R
+    torch.manual_seed(seed)
+    mod = R.STNorm(num_nodes=n, in_dim=c_in, out_dim=o, **kw)
+    _random_params(mod, seed)
+    ref = {k: v.detach().clone().double() for k, v in mod.state_dict().items()}
+    for k in ref:
+        if "running" not in k:
+            ref[k].requires_grad_(True)
+    x = torch.randn(b, t, n, c_in, generator=torch.Generator().manual_seed(seed + 1))
+    mod = mod.to(DEV).train(training)
+    out = mod(x.to(DEV), tnorm_group=tnorm_group)
+    w = torch.randn(out.shape, generator=torch.Generator().manual_seed(seed + 2))
+    (out * w.to(DEV)).sum().backward()
+    opts = dict(training=training, tnorm_group=tnorm_group, blocks=kw.get("blocks", 4), layers=kw.get("layers", 2),
+                tnorm_bool=kw.get("tnorm_bool", True), snorm_bool=kw.get("snorm_bool", True))
+    ro, rb = stnorm(ref, x, **opts)
+    (ro * w.double()).sum().backward()
+    # the same restatement in fp32 gives the per-tensor gap of the bound (module docstring)
+    r32 = {k: (v.detach().float().requires_grad_(True) if v.requires_grad else v.float()) for k, v in ref.items()}
+    o32, b32 = stnorm(r32, x, dtype=torch.float32, **opts)
+    (o32 * w).sum().backward()
+    assert out.shape == ro.shape
+    _close(out, ro.detach(), atol=1e-5 + 4 * float((o32.detach().double() - ro.detach()).abs().max()), what="out")
+    last = f"residual_convs.{mod.blocks * mod.layers - 1}."
+    for k, p in mod.named_parameters():
+        if k.startswith(last):
+            assert p.grad is None
+            continue
+        gap = float((r32[k].grad.double() - ref[k].grad).abs().max())
+        _close(p.grad, ref[k].grad, atol=1e-5 + 4 * gap, what=k)
+    for k, v in rb.items():
+        gap = float((b32[k].double() - v).abs().max())
+        _close(dict(mod.named_buffers())[k], v, atol=1e-5 + 4 * gap, what=k)
+    return mod
+
+
+@pytest.mark.parametrize("t", [3, 6, 12, 13, 16])
+def test_kernels_match_restatement_over_lengths_pooled_batch(t):
+    _against_restatement(104, 2, t, 8, 3, seed=t)
+
+
+@pytest.mark.parametrize("n", [2, 130])
+def test_small_and_ragged_node_counts(n):
+    _against_restatement(n, 1, 12, 5, 2, seed=n)
+
+
+@pytest.mark.parametrize("kw", [dict(tnorm_bool=False), dict(snorm_bool=False), dict(tnorm_bool=False, snorm_bool=False),
+                                dict(blocks=2), dict(layers=3, blocks=1)])
+def test_switches_and_block_counts(kw):
+    _against_restatement(70, 2, 9, 3, 1, seed=3, **kw)
+
+
+def test_eval_mode_and_snapshot_groups():
+    _against_restatement(90, 3, 12, 4, 2, seed=5, training=False)
+    _against_restatement(90, 3, 12, 4, 2, seed=6, tnorm_group=1)
+
+
+def test_host_module_or_wrong_dtype_is_refused_before_launch():
+    import regtgcn_amd as R
+    mod = R.STNorm(num_nodes=50, in_dim=4, out_dim=1)
+    x = torch.randn(1, 6, 50, 4, device=DEV)
+    with pytest.raises(R.RegtError):
+        mod(x)                                                   # parameters still on the host
+    mod = mod.to(DEV)
+    with pytest.raises(R.RegtError):
+        mod.double()(x.double())
+    mod = mod.float()
+    mod.tn[0].running_var = mod.tn[0].running_var.half()
+    with pytest.raises(R.RegtError):
+        mod(x)
+
+
+def test_backward_is_bit_reproducible():
+    import regtgcn_amd as R
+    torch.manual_seed(0)
+    mod = R.STNorm(num_nodes=1000, in_dim=8, out_dim=3).to(DEV)
+    x = torch.randn(2, 12, 1000, 8, device=DEV)
+    grads = []
+    for _ in range(2):
+        with torch.no_grad():
+            for b in mod.buffers():
+                b.fill_(0.5)
+        mod.zero_grad()
+        (mod(x) ** 2).mean().backward()
+        grads.append([p.grad.clone() for p in mod.parameters() if p.grad is not None])
+    for a, b in zip(*grads):
+        assert torch.equal(a, b)
+
+
+def test_snapshot_batching_equals_sequential_calls():
+    """(B, T, N, F) with tnorm_group = 1 == B sequential calls with B = 1: losses, accumulated gradients, running buffers."""
+    import regtgcn_amd as R
+    from regtgcn_amd.train import WindowStore, train_epoch_stnorm
+    torch.manual_seed(1)
+    base = R.STNorm(num_nodes=104, in_dim=8, out_dim=2)
+    _random_params(base, 1)
+    xs = [torch.randn(104, 8, 6, device=DEV) for _ in range(8)]
+    ys = [torch.randn(104, 2, device=DEV) for _ in range(8)]
+    res = []
+    for sb in (1, 4):
+        mod = R.STNorm(num_nodes=104, in_dim=8, out_dim=2)
+        mod.load_state_dict(base.state_dict())
+        mod = mod.to(DEV)
+        opt = torch.optim.SGD(mod.parameters(), lr=0.0)
+        grads = {}
+        orig = opt.step
+
+        def step(orig=orig, mod=mod, grads=grads):
+            grads.update({k: p.grad.clone() for k, p in mod.named_parameters() if p.grad is not None})
+            return orig()
+        opt.step = step
+        _, losses = train_epoch_stnorm(mod, WindowStore(xs, ys), opt, sb)
+        res.append((torch.stack(losses), grads, {k: b.clone() for k, b in mod.named_buffers()}))
+    # each snapshot runs the same per-node code either way; only the gradient sums over snapshots change order
+    _close(res[0][0], res[1][0].cpu(), atol=1e-6)
+    for k in res[0][1]:
+        _close(res[0][1][k], res[1][1][k].cpu(), atol=1e-5, what=k)
+    for k in res[0][2]:
+        _close(res[0][2][k], res[1][2][k].cpu(), atol=1e-6, what=k)
+
+
+def test_cfg3_shape_against_restatement():
+    """The cfg-3 shape: N = 100 000 nodes, F = 32, T = 12 (forward and gradients)."""
+    _against_restatement(100_000, 1, 12, 32, 1, seed=9)
+
+
+@pytest.mark.parametrize("t_out", [1, 3])
+def test_train_and_evaluate_command_lines(tmp_path, t_out):
+    fx = os.path.join(ROOT, "tests", "golden", "tpims_fixture.npz")
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    cmd = [sys.executable, "-m", "regtgcn_amd.train", "--model", "STNorm", "--num_timesteps_in", "6", "--num_timesteps_out", str(t_out),
+           "--tr", "0.2", "--tf", "occrate", "--fixture", fx, "--epochs", "1", "--snap_batch", "16", "--out_dir", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("Train Loss:")]
+    assert len(lines) == 2 and all("nan" not in l for l in lines)
+    ck = os.path.join(tmp_path, "occrate", "STNorm", f"model_in6_out{t_out}_epoch0.pt")
+    assert os.path.exists(ck)
+    r = subprocess.run([sys.executable, "-m", "regtgcn_amd.evaluate", "--model", "STNorm", "--fixture", fx, "--checkpoint", ck,
+                        "--num_timesteps_in", "6", "--num_timesteps_out", str(t_out), "--tr", "0.2", "--snap_batch", "8"],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.strip().splitlines()[-1].startswith("MAE:")
