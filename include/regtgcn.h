@@ -359,20 +359,35 @@ int32_t regt_stnorm_backward(const regt_stnorm_dims* dims, const float* x, const
  * Also selectable with REGT_GEMM_MODE=bf16x3 before the first call.  Returns the previous mode. */
 int32_t regt_set_gemm_mode(int32_t mode);
 
-/* Developer switches (A/B timing and the bit-for-bit comparisons of tests/test_gpu_fused.py); returns the previous value, -1 for
- * an unknown name.  "xbf" (default 1): under REGT_GEMM_MODE=bf16, bf16 rows of x / A_hat x / L~ x and the fused forward kernel
- * where the shape allows; 0 = the three-launch forward on fp32 rows.  "fused_bwd" (default 1): the three data-gradient launches of that
- * arithmetic as one kernel.  "spmm_rows" (default 0 -- opt-in, measured slower): the row-block aggregation kernel (CSR entries of a
- * workgroup's rows held in LDS) instead of the column-panel kernels.  "dgrad1_gen" (default 1): fp32 arithmetic, the candidate data gradient
- * forms its left operand dhp from Z, H~, dOH while staging it and its epilogue writes dzp and the attention dots (no separate
- * cell-backward pass); 0 = the two launches.  "tgcn_collapse" (default 1): regional = 0 (TemporalGCN), fp32 / bf16x3: the gates' linear use of
- * the activation-free hidden input folded into x and L~ x (gate GEMM at K = 3F, no K = 2C gate data gradient); 0 = uncollapsed.
- * Weight gradients of the bf16-row layout (both operands stored as bf16): "wgrad_ring" (default 6): 16-row half slabs requested ahead
- * through a register ring (4 | 6 | 8); 0 = the one-ahead kernel, same partial sums bit for bit.  "wgrad_tile" (default 256): output
- * rows per tile (128 | 256); "wgrad_ring256" (default 2): ring depth of the 256-row tile (2 | 4).  "wgrad_pairs" (default 2 = on with the ring kernel; 0 | 1): the two gradients of each left operand as
- * one launch.  "wgrad_wave" (default 1): row chunks of those launches sized so that all their workgroups are resident at once
- * (another summation order over chunk boundaries than 0, the fixed ~128 chunks).  "wgrad_bnw64" (default 1): fp32 rows, a 33..64-wide
- * right-hand side ([x | L~ x] at F = 32) as one 64-column tile instead of two of 32 (bit-identical).  "xbf" / "fused_bwd" also exist per call: regt_dims.flags. */
+/* Developer switches (A/B timing and the bit-for-bit comparisons of tests/test_gpu_fused.py): stores the value as the switch
+ * normalises it and returns the previous value; -1 for an unknown name.  Host state only (one table, csrc/options.hip); the five
+ * switches that name a variable start from it when it is set in the environment at their first use (any non-zero value reads as 1).
+ *   "xbf" (REGT_XBF; 0 | 1, default 1): under REGT_GEMM_MODE=bf16, bf16 rows of x / A_hat x / L~ x and the fused forward kernel
+ *     where the shape allows; 0 = the three-launch forward on fp32 rows.
+ *   "fused_bwd" (REGT_FUSED_BWD; 0 | 1, default 1): the three data-gradient launches of that arithmetic as one kernel.
+ *   "fused_rows" (0 | 1 | 2, default 1): the row-owning fused forward where it applies; 0 = the 64-row kernel everywhere, 2 = the
+ *     row-owning kernel as two workgroups of four waves (a test form).
+ *   "embed_kernel" (0 | 1, default 1): fp32 arithmetic, the regional embedding as its own kernel; 0 = through the general GEMM core.
+ *   "spmm_rows" (REGT_SPMM_ROWS; 0 | 1, default 0 -- opt-in, measured slower): the row-block aggregation kernel (CSR entries of a
+ *     workgroup's rows held in LDS) instead of the column-panel kernels.
+ *   "dgrad1_gen" (REGT_DGRAD1_GEN; 0 | 1, default 1): fp32 arithmetic, the candidate data gradient forms its left operand dhp from
+ *     Z, H~, dOH while staging it and its epilogue writes dzp and the attention dots (no separate cell-backward pass); 0 = the two
+ *     launches.
+ *   "tgcn_collapse" (REGT_TGCN_COLLAPSE; 0 | 1, default 1): regional = 0 (TemporalGCN), fp32 / bf16x3: the gates' linear use of the
+ *     activation-free hidden input folded into x and L~ x (gate GEMM at K = 3F, no K = 2C gate data gradient); 0 = uncollapsed.
+ * Weight gradients of the bf16-row layout (both operands stored as bf16):
+ *   "wgrad_ring" (any depth >= 0, negative = 0; default 6): 16-row half slabs requested ahead through a register ring (4 | 6 | 8);
+ *     0 = the one-ahead kernel, same partial sums bit for bit.
+ *   "wgrad_tile" (256, anything else = 128; default 256): output rows per tile.
+ *   "wgrad_ring256" (4, anything else = 2; default 2): ring depth of the 256-row tile.
+ *   "wgrad_pairs" (0 | 1 | 2, anything else = 2; default 2 = on with the ring kernel): the two gradients of each left operand as one
+ *     launch.
+ *   "wgrad_wave" (0 | 1, default 1): row chunks of those launches sized so that all their workgroups are resident at once (another
+ *     summation order over chunk boundaries than 0, the fixed ~128 chunks).
+ *   "wgrad_bnw64" (0 | 1, default 1): fp32 rows, a 33..64-wide right-hand side ([x | L~ x] at F = 32) as one 64-column tile instead
+ *     of two of 32 (bit-identical).
+ * The first two also exist per call: regt_dims.flags.  Environment only, read at first use: REGT_GEMM_MODE (above), REGT_FP32_CORE=wide,
+ * REGT_GEMM_DESC=table, REGT_HIPGRAPH=1|2, REGT_SIDE_STREAM=0, REGT_SPMM_PL=8|16, REGT_FUSED_TRACE=1|2. */
 int32_t regt_set_option(const char* name, int32_t value);
 
 /* Developer hook (REGT_FUSED_TRACE=1, tools/fused_trace.py): shader-clock stamps of the last fused forward launch, 8 per 64-row

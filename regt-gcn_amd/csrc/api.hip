@@ -73,7 +73,6 @@ struct GraphCache {
 static GraphCache g_fwd_graphs, g_bwd_graphs;
 static hipStream_t g_graph_stream = nullptr;
 static hipEvent_t g_ev_in = nullptr, g_ev_out = nullptr;
-static int g_graph_mode = -1;          // REGT_HIPGRAPH: 0 (default) off, 1 small problems only, 2 always
 static const long GRAPH_MAX_ROWS = 1L << 15;   // N*T rows below which a step is launch-bound
 
 static unsigned long long hash_bytes(const void* p, size_t n, unsigned long long h) {
@@ -82,14 +81,12 @@ static unsigned long long hash_bytes(const void* p, size_t n, unsigned long long
     return h;
 }
 
+// REGT_HIPGRAPH: 0 (default) off, 1 small problems only, 2 always.  Opt-in: measured 1.05 vs 0.89 ms/step at TPIMS size (the step
+// is bound by the latency of many tiny dependent kernels, not by their launches)
 static bool graphs_wanted(long rows) {
-    if (g_graph_mode < 0) {
-        const char* e = getenv("REGT_HIPGRAPH");
-        g_graph_mode = e ? atoi(e) : 0;     // opt-in: measured 1.05 vs 0.89 ms/step at TPIMS size (the step is bound
-                                            // by the latency of many tiny dependent kernels, not by their launches)
-    }
-    if (g_prof_on || g_graph_mode == 0) return false;
-    return g_graph_mode == 2 || rows <= GRAPH_MAX_ROWS;
+    const int mode = option(OPT_HIPGRAPH);
+    if (g_prof_on || mode == 0) return false;
+    return mode == 2 || rows <= GRAPH_MAX_ROWS;
 }
 
 // Runs `enqueue(stream)` either eagerly on `st` or as a cached graph replay ordered after / before `st`.
@@ -163,18 +160,8 @@ int q_format(const void* ws) {
 // REGT_XBF=0 keeps them fp32 and the three-launch forward (A/B timing; tests/test_gpu_fused.py compares the two bit for bit).
 // per-call switches (regt_dims.flags) of the entry point running on this thread; the process-wide options are the defaults
 thread_local unsigned t_call_flags = 0;
-int g_opt_fused_bwd = -1;
-bool fused_bwd_wanted() {
-    if (t_call_flags & REGT_DIMS_NO_FUSED_BWD) return false;
-    if (g_opt_fused_bwd < 0) { const char* e = getenv("REGT_FUSED_BWD"); g_opt_fused_bwd = e ? atoi(e) : 1; }
-    return g_opt_fused_bwd != 0;
-}
-int g_opt_xbf = -1;
-bool xbf_wanted() {
-    if (t_call_flags & REGT_DIMS_NO_BF16_ROWS) return false;
-    if (g_opt_xbf < 0) { const char* e = getenv("REGT_XBF"); g_opt_xbf = e ? atoi(e) : 1; }
-    return g_opt_xbf != 0;
-}
+bool fused_bwd_wanted() { return !(t_call_flags & REGT_DIMS_NO_FUSED_BWD) && option(OPT_FUSED_BWD); }      // REGT_FUSED_BWD
+bool xbf_wanted() { return !(t_call_flags & REGT_DIMS_NO_BF16_ROWS) && option(OPT_XBF); }
 // regt_dims.arith / .flags hold for the duration of one entry point on the calling thread
 struct CallScope {
     int prev_mode;
@@ -197,16 +184,7 @@ enum : int { FMT_QBF = 1, FMT_XBF = 2, FMT_XCALLER = 4, FMT_TCOLLAPSE = 8 };
 // ever fed weight gradients of that linear map) and the (2C x C) weight gradient dzr^T h become (2C x F) contractions on x and L~ x
 // plus tiny compositions.  h itself is still formed: the reset gate multiplies it (q = h * R) and the blend reads it.
 // REGT_TGCN_COLLAPSE=0 / regt_set_option("tgcn_collapse", 0): the uncollapsed form (A/B, tests).
-int g_opt_wgrad_pairs = -1;
-int wgrad_pairs_setting() {
-    if (g_opt_wgrad_pairs < 0) g_opt_wgrad_pairs = 2;
-    return g_opt_wgrad_pairs;
-}
-int g_opt_tcollapse = -1;
-bool tcollapse_wanted() {
-    if (g_opt_tcollapse < 0) { const char* e = getenv("REGT_TGCN_COLLAPSE"); g_opt_tcollapse = e ? atoi(e) : 1; }
-    return g_opt_tcollapse != 0;
-}
+bool tcollapse_wanted() { return option(OPT_TGCN_COLLAPSE) != 0; }
 inline const float* byte_off(const float* p, long bytes) { return reinterpret_cast<const float*>(reinterpret_cast<const char*>(p) + bytes); }
 
 // bf16 mode with bf16-stored activations: the GEMM weights get per-step bf16 copies in MFMA fragment order (SEG_B_FRAG: every
@@ -230,11 +208,9 @@ bool xbf_ok(const regt_dims& d, const regt_graph& g, bool h_ext, int x_rows, boo
 // The three-launch path of the same arithmetic follows with its per-node sums (CandArgs::node_sum_rows), whichever forward runs:
 // the forms stay bit-identical (tests/test_gpu_fused.py).  regt_set_option("fused_rows", 0): the 64-row kernel everywhere; 2: the
 // row-owning kernel as two workgroups of four waves per CU (a test variant, see kernels.h).
-static int g_opt_fused_rows = 1;
 // regt_set_option("embed_kernel", 0): the regional embedding of the fp32 path through the general GEMM core instead of embed.hip (A/B)
-static int g_opt_embed_kernel = 1;
 bool fused_rows_form(const regt_dims& d, const regt_graph& g) {
-    return g_opt_fused_rows && fused_forward_rows_ok(d.C, d.F, d.T) && d.regional && !g.overlap && (d.R == 1 || g.region_sorted);
+    return option(OPT_FUSED_ROWS) && fused_forward_rows_ok(d.C, d.F, d.T) && d.regional && !g.overlap && (d.R == 1 || g.region_sorted);
 }
 struct WbPtrs { const float *U[3], *UT[3], *Gzr, *Gh, *A0, *Aall; long ar_stride; };
 WbPtrs wb_ptrs(const float* Wb, long C, long F, long R) {
@@ -555,7 +531,7 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
             a.M = M; a.T = T; a.slope = d.lrelu_slope; a.act_lrelu = 1; a.tile_ctr = L.tile_ctr;
             PROF("fused_forward", st);
             TRY(launch_zero_f32(hidden, (long)N * C, st));
-            if (fused_rows_form(d, g)) TRY(launch_fused_forward_rows(a, C, F, g_opt_fused_rows == 2 ? 4 : 8, st));
+            if (fused_rows_form(d, g)) TRY(launch_fused_forward_rows(a, C, F, option(OPT_FUSED_ROWS) == 2 ? 4 : 8, st));
             else TRY(launch_fused_forward(a, C, F, st));
         }
         return head_forward(d, p, hidden, L.y1, pred, st);
@@ -617,7 +593,7 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
         e.out_bf16 = abf;
         PROF("gemm_regional", st);
         // fp32 at C = 256, F = 32 with node-sorted region ids: the kernel written for this shape (embed.hip); everything else: the general core
-        if (!wfr && !abf && gemm_mode() == 0 && !fp32_core_wide() && !gemm_desc_table_forced() && g_opt_embed_kernel && d.regional && !g.overlap &&
+        if (!wfr && !abf && gemm_mode() == 0 && !fp32_core_wide() && !gemm_desc_table_forced() && option(OPT_EMBED_KERNEL) && d.regional && !g.overlap &&
             (R == 1 || g.region_sorted) && embed_fp32_ok(M, C, F, T)) {
             TRY(launch_embed_fp32(Xp, L.LX, A0, Aall, R > 1 ? g.node_region : nullptr, bpr, L.h, M, T, ACT_LRELU, d.lrelu_slope, st));
         } else {
@@ -733,13 +709,11 @@ struct SideStream {
 // only enqueue.
 static std::mutex g_side_mu;
 static std::map<std::pair<int, hipStream_t>, SideStream> g_sides;
-static int g_side_enabled = -1;
 static const size_t SIDE_MAX_STREAMS = 64;
 static hipStream_t side_fork(hipStream_t st) {       // returns the stream to launch on (st itself when the side stream is off)
     if (t_call_flags & REGT_DIMS_NO_SIDE_STREAM) return st;
+    if (!option(OPT_SIDE_STREAM) || option(OPT_HIPGRAPH) > 0) return st;        // REGT_SIDE_STREAM=0; never inside a captured graph
     std::lock_guard<std::mutex> lk(g_side_mu);
-    if (g_side_enabled < 0) { const char* e = getenv("REGT_SIDE_STREAM"); g_side_enabled = e ? atoi(e) : 1; }
-    if (!g_side_enabled || g_graph_mode > 0) return st;
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return st; }
     const auto key = std::make_pair(dev, st);
@@ -972,18 +946,17 @@ int backward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p,
     }
     }
     // The (C x F)-sized gradients (Gh, Gzr, A0 | A_r) are HBM-bound -- they stream dhp / dzp|drp / ds for a K = F..2F product --
-    // while the two big ones (Uh, Uzr) sit on the matrix pipe: REGT_SIDE_WGRADS=1 issues the former on the side stream so that
-    // the two kinds overlap (A/B switch; see DESIGN.md section 6 for the measurement).
-    hipStream_t sw = st;        // (the skinny weight gradients on the side stream: measured noise, round 3 -- the switch is gone)
+    // while the two big ones (Uh, Uzr) sit on the matrix pipe.  (Issuing the former on the side stream so that the two kinds
+    // overlap: measured noise, round 3 -- see DESIGN.md section 6; they run on the launch stream.)
     // ---- weight gradients of the K=C contractions and of the composed (C,F) weights -----------------
     // bf16 rows (fused kernels' layout): dUh | dGh = dhp^T [q | A_hat x] and dUzr | dGzr = dzr^T [h | A_hat x] as ONE launch each -- the
     // A_hat x part is a third column tile of the same row chunk on the same XCD, so dhp / dzp|drp cross HBM once instead of twice.
     // (Round 3 measured this form slower, 1.86 vs 1.44 ms for the four: every tile issued the loads of BOTH right-hand operands.
-    // Since round 4 a column tile that lies entirely in one operand issues one load, wgrad_split_kernel q_tile.)  REGT_WGRAD_PAIRS=0/1.
+    // Since round 4 a column tile that lies entirely in one operand issues one load, wgrad_split_kernel q_tile.)
     // With the ring kernel (round 4) the paired form wins (0.64 + 0.43 against 0.54 + 0.35 + 0.29 + 0.18 ms at the cfg-5 shard) and is
-    // the default whenever that kernel is on; REGT_WGRAD_PAIRS / regt_set_option("wgrad_pairs", 0 | 1 | 2 = follow the ring kernel).
-    const int pairs_opt = wgrad_pairs_setting();
-    const bool pairs = (pairs_opt == 2 ? wgrad_ring_active() : pairs_opt == 1) && ibf && qbf && abf && xbf && !h_ext && !tcol && C % 128 == 0 && F % 8 == 0 && sw == st;
+    // the default whenever that kernel is on: regt_set_option("wgrad_pairs", 0 | 1 | 2 = follow the ring kernel).
+    const int pairs_opt = option(OPT_WGRAD_PAIRS);
+    const bool pairs = (pairs_opt == 2 ? wgrad_ring_active() : pairs_opt == 1) && ibf && qbf && abf && xbf && !h_ext && !tcol && C % 128 == 0 && F % 8 == 0;
     if (pairs) {
         int kc = L.kchunk, nc = L.nchunks;
         wgrad_ring_chunking(C, C + F, M, &kc, &nc);          // one wave of workgroups (ring kernel), else the layout's chunks
@@ -1012,7 +985,7 @@ int backward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p,
     {
         int kc = L.kchunk_s, nc = L.nchunks_s;
         if (!ibf && !xbf && F <= 32) wgrad_skinny_chunking(C, M, &kc, &nc);
-        TRY(wgrad_full(rq, "wgrad_Gh", L.dhp, C, C, L.AX, F, F, 0, M, kc, nc, L.dGh, F, nullptr, sw, ibf, xbf));
+        TRY(wgrad_full(rq, "wgrad_Gh", L.dhp, C, C, L.AX, F, F, 0, M, kc, nc, L.dGh, F, nullptr, st, ibf, xbf));
     }
     }
     if (pairs) {
@@ -1083,7 +1056,7 @@ int backward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p,
     if (!pairs) {
         int kc = L.kchunk_s, nc = L.nchunks_s;
         if (!ibf && !xbf && F <= 32) wgrad_skinny_chunking(2 * C, M, &kc, &nc);
-        TRY(wgrad_full(rq, "wgrad_Gzr", L.dzr, 2L * C, 2 * C, L.AX, F, F, 0, M, kc, nc, L.dGzr, F, nullptr, sw, ibf, xbf));
+        TRY(wgrad_full(rq, "wgrad_Gzr", L.dzr, 2L * C, 2 * C, L.AX, F, F, 0, M, kc, nc, L.dGzr, F, nullptr, st, ibf, xbf));
     }
     float* dA0 = d.regional ? L.dA0 : gr.cheb_w0;
     float* dAall = d.regional ? L.dAall : gr.cheb_w1;
@@ -1098,8 +1071,8 @@ int backward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p,
         a.p_bf16 = abf; a.q_bf16 = xbf;
         TRY(rq.take((long)g.n_chunks * wgrad_slab_stride(a), &a.slab));
         {
-            PROF("wgrad_A0_Ar", sw);
-            TRY(launch_wgrad(a, sw));
+            PROF("wgrad_A0_Ar", st);
+            TRY(launch_wgrad(a, st));
         }
         WgradReduceArgs r0{};
         r0.slab = a.slab; r0.nchunks = g.n_chunks; r0.slab_stride = wgrad_slab_stride(a); r0.elem_offset = 0; r0.slab_ld = 2 * F;
@@ -1223,29 +1196,15 @@ extern "C" {
 int32_t regt_abi_version(void) { return REGT_ABI_VERSION; }
 
 int32_t regt_set_gemm_mode(int32_t mode) {
-    const int prev = gemm_mode();
-    set_gemm_mode(mode);
+    const int prev = gemm_mode();       // (as the calling thread sees it)
+    set_option(OPT_GEMM_MODE, mode);
     return prev;
 }
 const char* regt_last_error(void) { return g_err; }
 
 int32_t regt_set_option(const char* name, int32_t value) {
     REGT_CHECK_ARG(name != nullptr, "regt_set_option: name is NULL");
-    if (!strcmp(name, "xbf")) { const int prev = xbf_wanted() ? 1 : 0; g_opt_xbf = value ? 1 : 0; return prev; }
-    if (!strcmp(name, "fused_rows")) { const int prev = g_opt_fused_rows; g_opt_fused_rows = value == 2 ? 2 : (value ? 1 : 0); return prev; }
-    if (!strcmp(name, "embed_kernel")) { const int prev = g_opt_embed_kernel; g_opt_embed_kernel = value ? 1 : 0; return prev; }
-    if (!strcmp(name, "fused_bwd")) { const int prev = fused_bwd_wanted() ? 1 : 0; g_opt_fused_bwd = value ? 1 : 0; return prev; }
-    if (!strcmp(name, "spmm_rows")) return spmm_rows_option(value);
-    if (!strcmp(name, "dgrad1_gen")) return dgrad1_gen_option(value);
-    if (!strcmp(name, "wgrad_ring")) return wgrad_ring_option(value);
-    if (!strcmp(name, "wgrad_tile")) return wgrad_tile_option(value);
-    if (!strcmp(name, "wgrad_ring256")) return wgrad_ring256_option(value == 4 ? 4 : 2);
-    if (!strcmp(name, "wgrad_bnw64")) return wgrad_bnw64_option(value ? 1 : 0);
-    if (!strcmp(name, "wgrad_wave")) return wgrad_wave_option(value ? 1 : 0);
-    if (!strcmp(name, "wgrad_pairs")) { const int prev = wgrad_pairs_setting(); g_opt_wgrad_pairs = value < 0 || value > 2 ? 2 : value; return prev; }
-    if (!strcmp(name, "tgcn_collapse")) { const int prev = tcollapse_wanted() ? 1 : 0; g_opt_tcollapse = value ? 1 : 0; return prev; }
-    set_error("regt_set_option: unknown option '%s'", name);
-    return -1;
+    return set_option(name, value);
 }
 
 size_t regt_graph_workspace_bytes(int64_t E, int32_t N) { return graph_workspace_bytes((long)E, N); }

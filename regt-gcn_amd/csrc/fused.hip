@@ -498,9 +498,7 @@ static long* g_fused_trace = nullptr;
 static long g_fused_trace_n = 0;
 // REGT_FUSED_TRACE = 1: stamps of the forward kernel, 2: of the backward kernel (8 per tile); nullptr when tracing is off
 long* fused_trace_buffer(int which, long tiles) {
-    static int tr = -1;
-    if (tr < 0) { const char* e = getenv("REGT_FUSED_TRACE"); tr = e ? atoi(e) : 0; }
-    if (tr != which) return nullptr;
+    if (option(OPT_FUSED_TRACE) != which) return nullptr;
     if (!g_fused_trace || g_fused_trace_n < FT_TRACE_SLOTS * tiles) {
         if (g_fused_trace) (void)hipFree(g_fused_trace);
         g_fused_trace = nullptr;

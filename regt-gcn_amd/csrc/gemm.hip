@@ -19,7 +19,7 @@
 
 namespace regt {
 
-// Developer build (REGT_HIPCC_FLAGS=-DREGT_WG_TRACE, tools/wg_trace.py): the flat GEMM kernels with N == REGT_WG_TRACE_N record,
+// Developer build (-DREGT_WG_TRACE, tools/wg_trace.py): the flat GEMM kernels with N == REGT_WG_TRACE_N record,
 // per workgroup, the 100 MHz wall clock at the start of the K loop, at its end and after the epilogue, plus HW_ID / XCC_ID
 // (which CU it ran on) -- the data behind DESIGN.md's "who overlaps with whom on a CU" analysis.
 #ifdef REGT_WG_TRACE
@@ -916,36 +916,17 @@ __global__ __launch_bounds__(256, 4) void gemm_flat_small_kernel(GemmSegs S, lon
 
 // 0: fp32 MFMA (default).  1: exact 3-way bf16 split of both operands, six partial products on the bf16 matrix pipe
 // (gemm_split.h) for the GEMMs whose B operand is stored [N][K].  2: plain bf16 operands (one product), fp32 accumulate --
-// reduced precision, the arithmetic BASELINE configs[4] names.
-static int g_gemm_mode = -1;
+// reduced precision, the arithmetic BASELINE configs[4] names.  The process default is OPT_GEMM_MODE (REGT_GEMM_MODE, regt_set_gemm_mode).
 // per-call override (regt_dims.arith, set for the duration of one entry point on the calling thread by CallScope): two models of
 // one process can run different arithmetics without touching the process default
 static thread_local int t_gemm_mode = -1;
 int gemm_mode_override(int mode) { const int prev = t_gemm_mode; t_gemm_mode = mode; return prev; }
-int gemm_mode() {
-    if (t_gemm_mode >= 0) return t_gemm_mode;
-    if (g_gemm_mode < 0) {
-        const char* e = getenv("REGT_GEMM_MODE");
-        g_gemm_mode = 0;
-        if (e && (!strcmp(e, "bf16x3") || !strcmp(e, "1"))) g_gemm_mode = 1;
-        if (e && (!strcmp(e, "bf16") || !strcmp(e, "2"))) g_gemm_mode = 2;
-    }
-    return g_gemm_mode;
-}
-void set_gemm_mode(int m) { g_gemm_mode = (m == 1 || m == 2) ? m : 0; }
+int gemm_mode() { return t_gemm_mode >= 0 ? t_gemm_mode : option(OPT_GEMM_MODE); }
 // REGT_FP32_CORE=wide: fp32 GEMMs on the 2-workgroup-per-CU core (gemm_fast.h) instead of the 3-workgroup one, for A/B timing
-bool fp32_core_wide() {
-    static int wide = -1;
-    if (wide < 0) { const char* e = getenv("REGT_FP32_CORE"); wide = e && !strcmp(e, "wide") ? 1 : 0; }
-    return wide == 1;
-}
+bool fp32_core_wide() { return option(OPT_FP32_CORE) == 1; }
 
 // the K loop may keep its slab descriptors in scalar registers (SplitCore::run_u): every K a multiple of the 32-k slab, byte offsets of a tile's rows within 31 bits.  REGT_GEMM_DESC=table forces the LDS table.
-bool gemm_desc_table_forced() {
-    static int force_table = -1;
-    if (force_table < 0) { const char* e = getenv("REGT_GEMM_DESC"); force_table = e && !strcmp(e, "table") ? 1 : 0; }
-    return force_table == 1;
-}
+bool gemm_desc_table_forced() { return option(OPT_GEMM_DESC) == 1; }
 // 0: LDS table; 1: scalar descriptors; 2: scalar descriptors and every segment's weights in fragment order (SEG_B_FRAG)
 static int uniform_ok(const GemmSegs& S, long M) {
     if (gemm_desc_table_forced()) return 0;
@@ -1111,16 +1092,7 @@ int launch_gemm_dgrad1(const GemmSegs& S, long M, int N, const EpiDgrad1& e, hip
 }
 // REGT_DGRAD1_GEN=0: keep cell_bwd + dgrad_candidate as two launches (A/B timing; same dhp / dzp / drp / dh to the bit, the
 // attention gradient in another fixed summation order)
-static int g_dgrad1_gen = -1;
-static bool dgrad1_gen_wanted() {
-    if (g_dgrad1_gen < 0) { const char* e = getenv("REGT_DGRAD1_GEN"); g_dgrad1_gen = e ? atoi(e) : 1; }
-    return g_dgrad1_gen != 0;
-}
-int dgrad1_gen_option(int value) {       // regt_set_option("dgrad1_gen", v): returns the previous setting
-    const int prev = dgrad1_gen_wanted() ? 1 : 0;
-    g_dgrad1_gen = value ? 1 : 0;
-    return prev;
-}
+static bool dgrad1_gen_wanted() { return option(OPT_DGRAD1_GEN) != 0; }
 bool gemm_dgrad1_gen_ok(long M, int C, int num_nodes) {
     return dgrad1_gen_wanted() && (gemm_mode() == 0 || gemm_mode() == 1) && !fp32_core_wide() && !gemm_desc_table_forced() && C % GBN == 0 && C % GBK == 0 &&
            (long)cdiv(M, GBM) * (C / GBN) >= SMALL_TILE_LIMIT && M < (1L << 31) && (long)num_nodes * C * 4 < (1L << 31) &&
@@ -1838,7 +1810,7 @@ int launch_small_gemm_multi(SgBatch& b, hipStream_t st) {
         // eight lanes per output (strided k + xor tree) only pay off for long sums; a K = F product is one lane's work;
         // matrix-sized outputs take the tiled form (split = 0)
         // (sums longer than 256 over few tiles -- d cheb_w1 = sum over the owned regions, K = R C -- stay on the 8-lane form: 16
-        // workgroups walking 64 chunks each were slower, 0.25 vs 0.15 ms for the launch; REGT_SG_TILED_MAXK: developer switch)
+        // workgroups walking 64 chunks each were slower, 0.25 vs 0.15 ms for the launch)
         constexpr long tiled_maxk = 256;
         if (task.m >= 16 && task.n >= 16 && ksum >= 16 && ksum <= tiled_maxk) {
             task.split = 0;

@@ -2,6 +2,7 @@
 // for the C ABI).  Every launcher enqueues on the given stream and returns REGT_OK / error code.
 #pragma once
 #include "gemm_core.h"
+#include "options.h"
 
 namespace regt {
 // developer build (-DREGT_WG_TRACE, tools/wg_trace.py): per-workgroup wall-clock marks inside the GEMM cores
@@ -105,17 +106,11 @@ int launch_gemm_gates(const GemmSegs& S, long M, int N, const EpiGates& e, hipSt
 int launch_gemm_dgrad1(const GemmSegs& S, long M, int N, const EpiDgrad1& e, hipStream_t st);
 // cell_bwd + dgrad_candidate in one launch (fp32 arithmetic, C % 128 == 0, big-tile regime): see EpiDgrad1's last fields
 bool gemm_dgrad1_gen_ok(long M, int C, int num_nodes);
-int wgrad_bnw64_option(int value);   // fp32 rows: one 64-column tile for a 33..64-wide right-hand side (regt_set_option "wgrad_bnw64")
-int wgrad_ring256_option(int value);  // ring depth of the 256-row tile (2 | 4)
-int wgrad_tile_option(int value);    // 128 | 256 output rows per tile of the ring kernel (regt_set_option "wgrad_tile")
-int wgrad_wave_option(int value);    // one-wave row chunking of ring-kernel launches (regt_set_option "wgrad_wave"; -1 = query)
 bool wgrad_ring_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks);
 bool wgrad_skinny_chunking(int Nout, long M, int* kchunk, int* nchunks);            // skinny (Nin <= 32) fp32-MFMA kernel
 bool wgrad_wide_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks);   // wide fp32 / bf16x3 kernels (experiment)
 long wgrad_chunk_bound(int Nout, int Nin, long M);   // upper bound of what the three can return (slab sizing, api.hip make_layout)
 bool wgrad_ring_active();             // the ring kernel takes the bf16-stored weight gradients (pairs pay off with it)
-int wgrad_ring_option(int value);    // runtime A/B switch (regt_set_option "wgrad_ring"): ring depth of the bf16 weight gradient
-int dgrad1_gen_option(int value);    // runtime A/B switch (regt_set_option "dgrad1_gen")
 int launch_gemm_dgrad1_gen(const GemmSegs& S, long M, int N, const EpiDgrad1& e, hipStream_t st);
 int launch_gemm_dgrad2(const GemmSegs& S, long M, int N, const EpiDgrad2& e, hipStream_t st);
 int launch_gemm_mask_add(const GemmSegs& S, long M, int N, const EpiMaskAdd& e, hipStream_t st);
@@ -249,7 +244,6 @@ int launch_spmm_dual_x(const int* rowptr, const int* col, const float* val_a, co
 int launch_spmm_dual_bf16(const int* rowptr, const int* col, const float* val_a, const float* val_l, const void* X, void* YA, void* YL,
                           int nnodes, int x_rows, int W, hipStream_t st);
 
-int spmm_rows_option(int value);   // runtime A/B switch of the row-block aggregation kernel (regt_set_option "spmm_rows")
 int launch_pack_x_bf16(const float* x, void* xp, int N, int F, int T, hipStream_t st);        // (N,F,T) fp32 -> (N,T,F) bf16, F % 8 == 0
 int launch_cvt_rows_bf16(const float* src, void* dst, long n, hipStream_t st);                // n % 8 == 0 elements fp32 -> bf16
 
@@ -301,7 +295,6 @@ int launch_rowdot_reduce(const float* rowdot, float* dp_partial, int num_nodes, 
 // ---- cell backward head / small element-wise kernels -------------------------------------------
 // GEMM arithmetic: 0 = fp32 MFMA (default), 1 = exact 3-way bf16 split on the bf16 MFMA (gemm_split.h)
 int gemm_mode();
-void set_gemm_mode(int mode);
 int gemm_mode_override(int mode);   // thread-local override for one call (-1 = none); returns the previous override
 bool fp32_core_wide();   // REGT_FP32_CORE=wide (A/B timing of the two fp32 GEMM cores)
 

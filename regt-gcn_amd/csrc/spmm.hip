@@ -615,21 +615,11 @@ static int launch_spmm_rows(const int* rowptr, const int* col, const float* val_
 // 256-byte column panels (two cache lines per neighbour: half the passes over the CSR) while an XCD's slice of X (node chunk x 256 B)
 // stays around its 4 MiB L2, else 128-byte ones; REGT_SPMM_PL=8|16 forces one (tools/spmm_pmc.sh)
 static bool panel_wide(int nnodes) {
-    static int pl_env = -1;
-    if (pl_env < 0) { const char* e = getenv("REGT_SPMM_PL"); pl_env = e ? atoi(e) : 0; }
-    return pl_env ? pl_env == 16 : (long)cdiv(nnodes, 8) * 256 <= SP_WIDE_SLICE_MAX;
+    const int pl = option(OPT_SPMM_PL);
+    return pl ? pl == 16 : (long)cdiv(nnodes, 8) * 256 <= SP_WIDE_SLICE_MAX;
 }
 // REGT_SPMM_ROWS / regt_set_option("spmm_rows"): 1 = row-block kernel where eligible, 0 (default) = panel kernels
-static int g_rows_opt = -1;
-static bool rows_wanted() {
-    if (g_rows_opt < 0) { const char* e = getenv("REGT_SPMM_ROWS"); g_rows_opt = e ? atoi(e) : 0; }   // opt-in: measured slower
-    return g_rows_opt != 0;
-}
-int spmm_rows_option(int value) {       // regt_set_option("spmm_rows", v): returns the previous setting
-    const int prev = rows_wanted() ? 1 : 0;
-    g_rows_opt = value ? 1 : 0;
-    return prev;
-}
+static bool rows_wanted() { return option(OPT_SPMM_ROWS) != 0; }
 // eligible: rows are whole panels, every byte offset fits 32 bits, at most 256 rows per workgroup
 static bool rows_ok(int nnodes, long x_rows, long rowbytes, int PL) {
     return rows_wanted() && rowbytes % (PL * 16) == 0 && x_rows * rowbytes < (1L << 32) - 4096 && (long)nnodes * rowbytes < (1L << 32) - 4096 &&

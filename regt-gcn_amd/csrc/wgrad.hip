@@ -9,59 +9,23 @@
 
 namespace regt {
 
-// Depth of the register ring of wgrad_bf16_ring_kernel: REGT_WGRAD_RING / regt_set_option("wgrad_ring", d) = 0 (the one-half-slab-
-// ahead kernel wgrad_split_kernel<1, true, true>: same slabs bit for bit) | 4 | 6 | 8 half slabs of lead.
-static int g_wgrad_ring = -1;
-static int wgrad_ring_depth() {
-    if (g_wgrad_ring < 0) g_wgrad_ring = 6;
-    return g_wgrad_ring;
-}
-static int g_wgrad_ring256 = -1;
-int wgrad_ring256_option(int value) {      // ring depth of the 256-row tile variant: 2 (default) | 4; -1 = query
-    if (g_wgrad_ring256 < 0) g_wgrad_ring256 = 2;
-    const int prev = g_wgrad_ring256;
-    if (value >= 0) g_wgrad_ring256 = value == 4 ? 4 : 2;
-    return prev;
-}
-static int g_wgrad_bnw64 = -1;
-int wgrad_bnw64_option(int value) {      // regt_set_option("wgrad_bnw64", 0 | 1); -1 = query
-    if (g_wgrad_bnw64 < 0) g_wgrad_bnw64 = 1;
-    const int prev = g_wgrad_bnw64;
-    if (value >= 0) g_wgrad_bnw64 = value ? 1 : 0;
-    return prev;
-}
-static int g_wgrad_tile = -1;
-static int wgrad_tile_rows() {
-    if (g_wgrad_tile < 0) g_wgrad_tile = 256;
-    return g_wgrad_tile;
-}
-int wgrad_tile_option(int value) {
-    const int prev = wgrad_tile_rows();
-    g_wgrad_tile = value == 256 ? 256 : 128;
-    return prev;
-}
+// Depth of the register ring of wgrad_bf16_ring_kernel: regt_set_option("wgrad_ring", d) = 0 (the one-half-slab-ahead kernel
+// wgrad_split_kernel<1, true, true>: same slabs bit for bit) | 4 | 6 (default) | 8 half slabs of lead.
+static int wgrad_ring_depth() { return option(OPT_WGRAD_RING); }
+static int wgrad_tile_rows() { return option(OPT_WGRAD_TILE); }       // 128 | 256 (default) output rows per tile of the ring kernel
 bool wgrad_ring_active() { return wgrad_ring_depth() > 0; }
 
 // Row chunking for a ring-kernel launch whose workgroups are ALL resident at once and fill every slot: chunks x tiles = CUs x
 // workgroups per CU.  The tiles of a chunk share their operands through L2 only while they walk the chunk in step; started
 // together they do, started as slots free up (1.5 waves of workgroups at 128 chunks x 6 tiles) they do not, and the half-filled
 // last wave costs as much as a full one.  Fewer, longer chunks also mean fewer slabs to write and reduce.
-// REGT_WGRAD_WAVE=0 / regt_set_option("wgrad_wave", 0): the layout's ~128 chunks.  false: not applicable, keep the caller's chunking.
-static int g_wgrad_wave = -1;
-int wgrad_wave_option(int value) {
-    if (g_wgrad_wave < 0) g_wgrad_wave = 1;
-    const int prev = g_wgrad_wave;
-    if (value >= 0) g_wgrad_wave = value ? 1 : 0;
-    return prev;
-}
+// regt_set_option("wgrad_wave", 0): the layout's ~128 chunks.  false: not applicable, keep the caller's chunking.
 // The same for the wide fp32 / bf16x3 kernels (wgrad3_kernel: three workgroups per CU; wgrad_split_kernel<3>: two): chunks x
 // (128 x 128 tiles) = one full wave of workgroups instead of ~128 chunks (768 instead of 1024 / 512 workgroups for dUzr / dUh at
 // C = 256).  These kernels are MFMA-bound, so it buys little: -0.05 ms of 4.0 at cfg-3, -0.01 ms at the W = 8 shard shape
-// (profiles/r04_wgrad_wave32_ab.txt).  REGT_WGRAD_WAVE32=0: the layout's chunks; =2: two waves (more slabs to reduce: slower).
-static int g_wgrad_wave32 = -1;
+// (profiles/r04_wgrad_wave32_ab.txt; two waves mean more slabs to reduce: slower).
 bool wgrad_wide_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks) {
-    if (g_wgrad_wave32 < 0) g_wgrad_wave32 = 1;
-    if (!g_wgrad_wave32 || gemm_mode() == 2 || fp32_core_wide() || Nin <= 32) return false;
+    if (gemm_mode() == 2 || fp32_core_wide() || Nin <= 32) return false;
     static int cus = 0;
     if (!cus) {
         int dev = 0;
@@ -69,7 +33,7 @@ bool wgrad_wide_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks) {
     }
     const int per_cu = gemm_mode() == 1 ? 2 : 3;
     const long tpc = (long)cdiv(Nout, 128) * cdiv(Nin, 128);
-    long nch = (long)cus * per_cu * g_wgrad_wave32 / tpc;       // g_wgrad_wave32 waves of workgroups
+    long nch = (long)cus * per_cu / tpc;       // one wave of workgroups
     if (nch < 1) return false;
     long kc = ((M + nch - 1) / nch + 31) / 32 * 32;
     if (kc < 512) return false;
@@ -81,7 +45,7 @@ bool wgrad_wide_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks) {
     *nchunks = (int)((M + kc - 1) / kc);
     return true;
 }
-// Skinny gradients (Nin <= 32: wgrad_kernel<32>, HBM-bound on their left operand): chunks x row tiles = REGT_WGRAD_SKINNY (default 2)
+// Skinny gradients (Nin <= 32: wgrad_kernel<32>, HBM-bound on their left operand): chunks x row tiles = two
 // workgroups per CU, all resident at once -- at cfg-3 the layout's 507 chunks are 1.3 (dGh) / 2.6 (dGzr) waves of workgroups.
 bool wgrad_skinny_chunking(int Nout, long M, int* kchunk, int* nchunks) {
     constexpr int per_cu = 2;
@@ -103,7 +67,7 @@ bool wgrad_skinny_chunking(int Nout, long M, int* kchunk, int* nchunks) {
     return true;
 }
 bool wgrad_ring_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks) {
-    if (!wgrad_ring_active() || !wgrad_wave_option(-1)) return false;
+    if (!wgrad_ring_active() || !option(OPT_WGRAD_WAVE)) return false;
     static int cus = 0;
     if (!cus) {
         int dev = 0;
@@ -147,11 +111,6 @@ long wgrad_chunk_bound(int Nout, int Nin, long M) {
         best = n > best ? n : best;
     }
     return best;
-}
-int wgrad_ring_option(int value) {
-    const int prev = wgrad_ring_depth();
-    g_wgrad_ring = value < 0 ? 0 : value;
-    return prev;
 }
 
 // ---- weight gradients: out[Nout x Nin] = P^T Q ----------------------------------------------------
@@ -1222,8 +1181,8 @@ static int launch_wgrad_impl(const WgradArgs& a, hipStream_t st) {
     const bool fast = a.ldp % 4 == 0 && a.ldq % 4 == 0 && a.Nout % 4 == 0 && a.Nin % 4 == 0 && a16(a.P) && a16(a.Q) &&
                       a.ldp < (1L << 20) && a.ldq < (1L << 20) && (a.chunk_tab || a.kchunk <= 65536) &&
                       (!a.Q2 || (a.ldq2 % 4 == 0 && a.ldq2 < (1L << 20) && a16(a.Q2) && a.nin_split % 32 == 0));
-    // (fp32 rows, 32 < Nin <= 64 -- the fused [x | L~ x] right-hand side at F = 32: one 64-column tile; REGT_WGRAD_BNW64=0: two of 32)
-    const int bnw64 = wgrad_bnw64_option(-1);
+    // (fp32 rows, 32 < Nin <= 64 -- the fused [x | L~ x] right-hand side at F = 32: one 64-column tile; regt_set_option("wgrad_bnw64", 0): two of 32)
+    const int bnw64 = option(OPT_WGRAD_BNW64);
     const bool mid = !wide && fast && bnw64 && !a.p_bf16 && !a.q_bf16 && a.Nin > 32 && a.Nin <= 64 && (!a.Q2 || a.nin_split < 64);
     const int bnw = wide ? 128 : (mid ? 64 : 32);
     long blocks = (long)cdiv(a.Nout, 128) * cdiv(a.Nin, bnw) * a.nchunks;
@@ -1252,13 +1211,13 @@ static int launch_wgrad_impl(const WgradArgs& a, hipStream_t st) {
                 hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3(256), bytes, st, a);
                 return REGT_OK;
             };
-            // 256-row tiles where the output has them (regt_set_option("wgrad_tile", 128 | 256) / REGT_WGRAD_TILE); ring of 2 there
-            // (REGT_WGRAD_RING256 / "wgrad_ring256" = 2 | 4; 6 half slabs of three 16-byte loads spill).  Two beats four, 0.585 + 0.350
+            // 256-row tiles where the output has them (regt_set_option("wgrad_tile", 128 | 256)); ring of 2 there
+            // ("wgrad_ring256" = 2 | 4; 6 half slabs of three 16-byte loads spill).  Two beats four, 0.585 + 0.350
             // against 0.63 + 0.383 ms at the cfg-5 shard: what is in flight (workgroups x slots x 12 KB per XCD) competes with the lines
             // the chunk's other tiles are about to ask for in the 4 MiB L2, and the tile that comes second finds its rows there anyway
             if (ring_ok && wgrad_tile_rows() == 256 && a.Nout % 256 == 0) {
                 const long blocks4 = (long)(a.Nout / 256) * cdiv(a.Nin, 128) * a.nchunks;
-                if (wgrad_ring256_option(-1) == 2) { if (int rc = launch_ring(&wgrad_bf16_ring_kernel<2, 4>, blocks4, 2 * 3 * WS_PLANE_B)) return rc; }
+                if (option(OPT_WGRAD_RING256) == 2) { if (int rc = launch_ring(&wgrad_bf16_ring_kernel<2, 4>, blocks4, 2 * 3 * WS_PLANE_B)) return rc; }
                 else if (int rc = launch_ring(&wgrad_bf16_ring_kernel<4, 4>, blocks4, 2 * 3 * WS_PLANE_B)) return rc;
             }
             else if (ring_ok && ring >= 8) { if (int rc = launch_ring(&wgrad_bf16_ring_kernel<8, 2>, blocks, lb)) return rc; }

@@ -164,3 +164,132 @@ def test_etl_target_column_follows_train_feature():
     assert etl.feature_columns("occrate")[:-1] == etl.feature_columns("available")[:-1]
     with pytest.raises(ValueError):
         etl.feature_columns("speed")
+
+
+# ---- the runtime switches (csrc/options.hip): defaults, clamping, environment, one list of names ---------------------------------
+# name -> (default, value stored for regt_set_option(name, v)); the next call reports the stored value as "previous"
+_BOOL = lambda v: 1 if v else 0
+OPTION_RULES = {
+    "xbf": (1, _BOOL), "fused_bwd": (1, _BOOL), "tgcn_collapse": (1, _BOOL), "dgrad1_gen": (1, _BOOL), "spmm_rows": (0, _BOOL),
+    "fused_rows": (1, lambda v: 2 if v == 2 else _BOOL(v)), "embed_kernel": (1, _BOOL),
+    "wgrad_ring": (6, lambda v: 0 if v < 0 else v), "wgrad_tile": (256, lambda v: 256 if v == 256 else 128),
+    "wgrad_ring256": (2, lambda v: 4 if v == 4 else 2), "wgrad_bnw64": (1, _BOOL), "wgrad_wave": (1, _BOOL),
+    "wgrad_pairs": (2, lambda v: 2 if v < 0 or v > 2 else v),
+}
+OPTION_ENV = {"REGT_XBF": "xbf", "REGT_FUSED_BWD": "fused_bwd", "REGT_TGCN_COLLAPSE": "tgcn_collapse", "REGT_DGRAD1_GEN": "dgrad1_gen",
+              "REGT_SPMM_ROWS": "spmm_rows"}
+PROBES = (-1, 0, 1, 2, 3, 4, 7, 128, 256)
+
+# runs in a fresh process (the options are process state): loads the library through regt-gcn_amd/_lib.py alone (no torch), applies
+# the environment assignments of argv[3] AFTER loading, then prints what every regt_set_option call of argv[2] returned
+_PROBE_SCRIPT = r"""
+import importlib.util, json, os, sys
+spec = importlib.util.spec_from_file_location("regt_lib", sys.argv[1])
+mod = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(mod)
+lib = mod.load()
+os.environ.update(json.loads(sys.argv[3]))
+print(json.dumps([lib.regt_set_option(n.encode(), v) for n, v in json.loads(sys.argv[2])]))
+"""
+
+
+def _probe(calls, env=None, late_env=None):
+    import json
+    import subprocess
+    import sys
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("REGT_") or k == "REGT_LIB_DIR"}
+    clean.update(env or {})
+    out = subprocess.run([sys.executable, "-c", _PROBE_SCRIPT, os.path.join(ROOT, "regt-gcn_amd", "_lib.py"), json.dumps(calls),
+                          json.dumps(late_env or {})], env=clean, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = json.loads(out.stdout.strip().splitlines()[-1])
+    assert len(got) == len(calls)
+    return got
+
+
+def test_option_defaults_and_clamping():
+    """With no switch variable set, the first regt_set_option of every name returns its default, and every call after one that
+    passed v returns the value the option's rule stores for v."""
+    calls = [(n, v) for n in OPTION_RULES for v in PROBES + (0,)]
+    got = iter(_probe(calls))
+    for n, (dflt, rule) in OPTION_RULES.items():
+        expect = dflt
+        for v in PROBES + (0,):
+            prev = next(got)
+            assert prev == expect, (n, v, prev, expect)
+            expect = rule(v)
+
+
+@pytest.mark.parametrize("var,value", [("REGT_XBF", 0), ("REGT_FUSED_BWD", 0), ("REGT_TGCN_COLLAPSE", 0), ("REGT_DGRAD1_GEN", 0),
+                                       ("REGT_SPMM_ROWS", 1), ("REGT_XBF", 3)])
+def test_option_environment_is_read_at_first_use(var, value):
+    """A switch variable of the process environment decides what the first regt_set_option of its name reports (non-zero reads as
+    1) and leaves every other name at its default."""
+    names = list(OPTION_RULES)
+    got = _probe([(n, 1) for n in names], env={var: str(value)})
+    for n, prev in zip(names, got):
+        assert prev == (_BOOL(value) if n == OPTION_ENV[var] else OPTION_RULES[n][0]), (var, n, prev)
+
+
+def test_option_environment_set_after_loading_still_counts():
+    """The variable is read at first use, not when the library is loaded (tools/fused_trace.py sets one after importing)."""
+    assert _probe([("xbf", 1), ("xbf", 1)], late_env={"REGT_XBF": "0"}) == [0, 1]
+
+
+def _csrc_files():
+    d = os.path.join(ROOT, "regt-gcn_amd", "csrc")
+    return {f: open(os.path.join(d, f)).read() for f in sorted(os.listdir(d)) if f.endswith((".hip", ".h"))}
+
+
+def _registry_rows():
+    """(name | None, env | None) of every row of the option table, one row per line in csrc/options.hip."""
+    src = open(os.path.join(ROOT, "regt-gcn_amd", "csrc", "options.hip")).read()
+    rows = re.findall(r'^\s*\{OPT_\w+,\s*(?:"(\w+)"|nullptr),\s*(?:"(\w+)"|nullptr),', src, flags=re.M)
+    assert len(rows) >= 20, rows
+    return [(n or None, e or None) for n, e in rows]
+
+
+def test_one_list_of_option_names():
+    """The table's names are exactly what regt_set_option accepts, what include/regtgcn.h documents and what
+    tests/test_gpu_switches.py holds defaults for."""
+    import ast
+    lib = R.load_library()
+    rows = _registry_rows()
+    names = {n for n, _ in rows if n}
+    assert names == set(OPTION_RULES)
+    for n, e in rows:
+        if n:                                                # accepted: returns the previous value, which is then restored
+            prev = lib.regt_set_option(n.encode(), 1)
+            assert prev >= 0, (n, lib.regt_last_error())
+            lib.regt_set_option(n.encode(), prev)
+        elif e:                                              # environment-only: no runtime name, in either spelling
+            assert lib.regt_set_option(e.encode(), 1) == -1 and lib.regt_set_option(e[5:].lower().encode(), 1) == -1
+    assert {e: n for n, e in rows if n and e} == OPTION_ENV
+    hdr = open(os.path.join(ROOT, "include", "regtgcn.h")).read()
+    doc = hdr[hdr.index("Developer switches"):hdr.index("int32_t regt_set_option")]
+    assert set(re.findall(r'"([a-z_0-9]+)"', doc)) == names
+    tree = ast.parse(open(os.path.join(ROOT, "tests", "test_gpu_switches.py")).read())
+    fn = next(f for f in tree.body if isinstance(f, ast.FunctionDef) and f.name == "test_every_runtime_option_is_known_and_restores")
+    dicts = [a.value for a in ast.walk(fn) if isinstance(a, ast.Assign) and a.targets[0].id == "defaults"]
+    defaults = ast.literal_eval(dicts[0])
+    assert {k.decode(): v for k, v in defaults.items()} == {n: d for n, (d, _) in OPTION_RULES.items()}
+
+
+def test_option_source_hygiene():
+    """getenv lives in the registry alone, and every REGT_* word in csrc/ is a macro / enumerator of the library, a -D build switch
+    or a variable the table reads: a comment cannot name a switch that no longer exists."""
+    files = _csrc_files()
+    assert [f for f, s in files.items() if "getenv" in s] == ["options.hip"]
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "regtgcn.h")).read(), flags=re.S)
+    known = set(re.findall(r"REGT_[A-Z0-9_]+", hdr))
+    for s in files.values():
+        known |= set(re.findall(r"^\s*#\s*define\s+(REGT_[A-Z0-9_]+)", s, flags=re.M))
+    known |= {"REGT_WG_TRACE", "REGT_WG_TRACE_N", "REGT_EPI_GENERIC", "REGT_FUSED_FINE", "REGT_FUSED_ABL", "REGT_FUSED_DBG"}   # -D
+    known |= {e for _, e in _registry_rows() if e}
+    stale = {}
+    for f, s in files.items():
+        for tok in set(re.findall(r"REGT_[A-Z0-9_]+", s)):
+            ok = tok in known or (tok.endswith("_") and any(k.startswith(tok) for k in known))      # "REGT_ARITH_*"
+            if not ok:
+                stale.setdefault(tok, []).append(f)
+    assert not stale, stale
