@@ -353,6 +353,33 @@ int32_t regt_stnorm_forward(const regt_stnorm_dims* dims, const float* x, const 
 int32_t regt_stnorm_backward(const regt_stnorm_dims* dims, const float* x, const float* const* params, float* const* running,
                              const float* dout, float* const* grads, const float* workspace, float* scratch, regt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * STID (models/STID.py) with if_time_in_day = if_day_in_week = False, as run.py:134 builds it: a per-node network.
+ *   x (batch, input_len, num_nodes, in_features) -- the reference's forward input; the kernels read the first input_dim
+ *   features of every time step in place.  out (batch, output_len, num_nodes, 1).
+ *   params: device pointers in state_dict order: node_emb (num_nodes, 32) (NULL when if_node is 0),
+ *   time_series_emb_layer.weight (32, input_dim * input_len, 1, 1), .bias, then per layer i encoder.i.fc1.weight
+ *   (hidden, hidden, 1, 1), .bias, encoder.i.fc2.weight, .bias, then regression_layer.weight (output_len, hidden, 1, 1),
+ *   .bias: 3 + 4 * num_layer + 2 entries, hidden = 32 + 32 * if_node.  grads: the layout of params.
+ *   keep: NULL (eval: no dropout) or int32 words (num_layer, batch, num_nodes, hidden / 32); bit j of word w keeps channel
+ *   32 w + j of the block's activation, kept values are scaled by 1 / (1 - dropout_p).  The backward takes the same words.
+ *   workspace: NULL (nothing is kept) or workspace_floats floats, which the forward fills with the block inputs and
+ *   activations that the backward reads; scratch is the backward's own.  Sizes from regt_stid_sizes (REGT_ERR_ARG for
+ *   invalid dims).  Limits: embed_dim == node_dim == 32; 1 <= num_layer <= 8; 1 <= input_len <= 255;
+ *   1 <= input_dim <= in_features <= 256; input_dim * input_len <= 192; 1 <= output_len <= 64; num_nodes, batch >= 1;
+ *   0 <= dropout_p < 1.  Every table entry must be a contiguous fp32 device tensor of the reference's shape
+ *   (regtgcn_amd.ops checks that before the call).  Sums run in a fixed order without float atomics: bit-reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t num_nodes, batch, input_len, in_features, input_dim, embed_dim, node_dim, num_layer, output_len, if_node;
+    float dropout_p;
+} regt_stid_dims;
+int32_t regt_stid_sizes(const regt_stid_dims* dims, size_t* workspace_floats, size_t* scratch_floats);
+int32_t regt_stid_forward(const regt_stid_dims* dims, const float* x, const float* const* params, const uint32_t* keep, float* out,
+                          float* workspace, regt_stream_t stream);
+int32_t regt_stid_backward(const regt_stid_dims* dims, const float* x, const float* const* params, const uint32_t* keep,
+                           const float* dout, float* const* grads, const float* workspace, float* scratch, regt_stream_t stream);
+
 /* Arithmetic of the dense contractions.  0 (default): fp32 MFMA (v_mfma_f32_32x32x2_f32).  1: every fp32 operand is
  * split exactly into three bf16 pieces and the six leading partial products run on the bf16 MFMA with fp32
  * accumulation -- fp32-level rounding error (dropped terms <= 3 * 2^-24 of a product), ~2x the matrix-pipe rate.

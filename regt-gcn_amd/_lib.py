@@ -51,6 +51,11 @@ class StnormDims(C.Structure):
                                          "tnorm", "snorm", "training")]
 
 
+class StidDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_nodes", "batch", "input_len", "in_features", "input_dim", "embed_dim", "node_dim",
+                                         "num_layer", "output_len", "if_node")] + [("dropout_p", C.c_float)]
+
+
 class Graph(C.Structure):
     _fields_ = [("rowptr", vp), ("col", vp), ("val", vp), ("node_region", vp), ("chunk_tab", vp),
                 ("chunk_region", vp), ("n_chunks", C.c_int32),
@@ -128,6 +133,9 @@ SIGNATURES = {
     "regt_stnorm_sizes": (C.c_int32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "regt_stnorm_forward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp]),
     "regt_stnorm_backward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "regt_stid_sizes": (C.c_int32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "regt_stid_forward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp]),
+    "regt_stid_backward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "regt_mse_loss_grad": (C.c_int32, [vp, vp, vp, vp, C.c_int64, C.c_int64, vp]),
 }
 

@@ -1683,6 +1683,62 @@ int32_t regt_stnorm_backward(const regt_stnorm_dims* d, const float* x, const fl
     return regt::launch_stnorm_bwd(s, x, params, running, dout, grads, ws, scratch, (hipStream_t)st);
 }
 
+static int stid_check(const char* what, const regt_stid_dims* d, regt::StidDims* s) {
+    REGT_CHECK_ARG(d != nullptr, "%s: dims is NULL", what);
+    REGT_CHECK_ARG(d->num_nodes >= 1, "%s: num_nodes must be >= 1, got %d", what, d->num_nodes);
+    REGT_CHECK_ARG(d->batch >= 1, "%s: batch must be >= 1, got %d", what, d->batch);
+    REGT_CHECK_ARG(d->embed_dim == 32, "%s: embed_dim must be 32, got %d", what, d->embed_dim);
+    REGT_CHECK_ARG(d->node_dim == 32, "%s: node_dim must be 32, got %d", what, d->node_dim);
+    REGT_CHECK_ARG(d->num_layer >= 1 && d->num_layer <= regt::STID_MAX_LAYERS, "%s: num_layer must be in [1, %d], got %d", what,
+                   regt::STID_MAX_LAYERS, d->num_layer);
+    REGT_CHECK_ARG(d->input_len >= 1 && d->input_len <= 255, "%s: input_len must be in [1, 255], got %d", what, d->input_len);
+    REGT_CHECK_ARG(d->in_features >= 1 && d->in_features <= 256, "%s: in_features must be in [1, 256], got %d", what, d->in_features);
+    REGT_CHECK_ARG(d->input_dim >= 1 && d->input_dim <= d->in_features, "%s: input_dim must be in [1, in_features = %d], got %d", what,
+                   d->in_features, d->input_dim);
+    REGT_CHECK_ARG((long)d->input_dim * d->input_len <= regt::STID_MAX_KIN, "%s: input_dim * input_len must be <= %d, got %d * %d", what,
+                   regt::STID_MAX_KIN, d->input_dim, d->input_len);
+    REGT_CHECK_ARG(d->output_len >= 1 && d->output_len <= regt::STID_MAX_OUT, "%s: output_len must be in [1, %d], got %d", what,
+                   regt::STID_MAX_OUT, d->output_len);
+    REGT_CHECK_ARG(d->dropout_p >= 0.f && d->dropout_p < 1.f, "%s: dropout_p must be in [0, 1), got %g", what, (double)d->dropout_p);
+    REGT_CHECK_ARG((long)d->batch * d->num_nodes * 64 * (2 * d->num_layer + 1) < (1L << 40), "%s: batch * num_nodes is too large", what);
+    *s = regt::StidDims{d->num_nodes, d->batch, d->input_len, d->in_features, d->input_dim, d->embed_dim, d->node_dim, d->num_layer,
+                        d->output_len, d->if_node ? 1 : 0, d->dropout_p};
+    return REGT_OK;
+}
+
+static int stid_check_table(const char* what, const regt::StidDims& s, const void* const* p) {
+    REGT_CHECK_ARG(p != nullptr, "%s: table is NULL", what);
+    if (s.if_node) REGT_CHECK_ARG(p[0] != nullptr, "%s: entry 0 (node_emb) is NULL", what);
+    for (int k = 1; k < 3 + 4 * s.num_layer + 2; ++k) REGT_CHECK_ARG(p[k] != nullptr, "%s: entry %d is NULL", what, k);
+    return REGT_OK;
+}
+
+int32_t regt_stid_sizes(const regt_stid_dims* d, size_t* ws, size_t* scratch) {
+    regt::StidDims s;
+    if (int rc = stid_check("regt_stid_sizes", d, &s)) return rc;
+    REGT_CHECK_ARG(regt::stid_sizes(s, ws, scratch), "regt_stid_sizes: unsupported dims");
+    return REGT_OK;
+}
+
+int32_t regt_stid_forward(const regt_stid_dims* d, const float* x, const float* const* params, const uint32_t* keep, float* out, float* ws,
+                          regt_stream_t st) {
+    regt::StidDims s;
+    if (int rc = stid_check("regt_stid_forward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && out, "regt_stid_forward: x or out is NULL");
+    if (int rc = stid_check_table("regt_stid_forward: params", s, reinterpret_cast<const void* const*>(params))) return rc;
+    return regt::launch_stid_fwd(s, x, params, keep, out, ws, (hipStream_t)st);
+}
+
+int32_t regt_stid_backward(const regt_stid_dims* d, const float* x, const float* const* params, const uint32_t* keep, const float* dout,
+                           float* const* grads, const float* ws, float* scratch, regt_stream_t st) {
+    regt::StidDims s;
+    if (int rc = stid_check("regt_stid_backward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && dout && ws && scratch, "regt_stid_backward: x, dout, workspace or scratch is NULL");
+    if (int rc = stid_check_table("regt_stid_backward: params", s, reinterpret_cast<const void* const*>(params))) return rc;
+    if (int rc = stid_check_table("regt_stid_backward: grads", s, reinterpret_cast<const void* const*>(grads))) return rc;
+    return regt::launch_stid_bwd(s, x, params, keep, dout, grads, ws, scratch, (hipStream_t)st);
+}
+
 int64_t regt_debug_trace(int64_t* out_host, int64_t capacity) { return fused_trace_fetch(reinterpret_cast<long*>(out_host), (long)capacity); }
 
 int32_t regt_profile_enable(int32_t on) {

@@ -360,6 +360,16 @@ int launch_stnorm_fwd(const StnDims& s, const float* x, const float* const* P, f
 int launch_stnorm_bwd(const StnDims& s, const float* x, const float* const* P, float* const* run, const float* dout, float* const* G,
                       const float* ws, float* scratch, hipStream_t st);
 
+// STID (stid.hip): the whole per-node network in one forward launch; the backward is one launch plus a fixed-order reduction.
+// Parameter / gradient pointer tables in state_dict order: node_emb (NULL when if_node is 0), time_series_emb_layer w, b, then per
+// layer fc1 w, b, fc2 w, b, then regression_layer w, b: 3 + 4 * num_layer + 2 entries.
+struct StidDims { int num_nodes, batch, input_len, in_features, input_dim, embed_dim, node_dim, num_layer, output_len, if_node; float dropout_p; };
+constexpr int STID_MAX_LAYERS = 8, STID_MAX_KIN = 192, STID_MAX_OUT = 64, STID_MAX_WGS = 256;
+bool stid_sizes(const StidDims& s, size_t* ws_floats, size_t* scratch_floats);
+int launch_stid_fwd(const StidDims& s, const float* x, const float* const* P, const uint32_t* keep, float* out, float* ws, hipStream_t st);
+int launch_stid_bwd(const StidDims& s, const float* x, const float* const* P, const uint32_t* keep, const float* dout, float* const* G,
+                    const float* ws, float* scratch, hipStream_t st);
+
 // hipFuncSetAttribute is a (slow, host-synchronous) driver call: do it once per kernel, not per launch.
 template <class K>
 static int set_lds_once(K kernel, int bytes, bool* done) {

@@ -80,17 +80,17 @@ def load_processed_pickle(path: str) -> Dict[str, torch.Tensor]:
 
 
 @torch.no_grad()
-def predict_metrics_stnorm(model, xs, ys, snap_batch: int = 1):
-    """predict.py:173-180 for STNorm: the errors are ``batch.y - out`` with out (1, O, N, L_out) and y (N, O), broadcast as the
-    reference broadcasts them; MAPE divides by the 95th percentile of the snapshot's y and skips a snapshot whose ratio is infinite.
-    Snapshots run ``snap_batch`` at a time with per-snapshot TNorm (tnorm_group = 1); eval mode reads only the running buffers."""
+def _predict_metrics_windows(model, xs, ys, snap_batch: int, call):
+    """predict.py:173-180 for the models fed (b, T, N, F) windows: the errors are ``batch.y - out`` with out (1, O, N, L_out) and
+    y (N, O), broadcast as the reference broadcasts them; MAPE divides by the 95th percentile of the snapshot's y and skips a
+    snapshot whose ratio is infinite."""
     model.eval()
     ae = se = ape = 0.0
     count = ape_count = 0
     for i in range(0, len(xs), snap_batch):
         x = torch.stack(list(xs[i:i + snap_batch])).permute(0, 3, 1, 2)          # (b, T, N, F)
         y = torch.stack(list(ys[i:i + snap_batch]))
-        out = model(x, tnorm_group=1)
+        out = call(x)
         for k in range(x.shape[0]):
             err = (y[k] - out[k:k + 1]).double()
             ae += float(err.abs().sum())
@@ -103,12 +103,23 @@ def predict_metrics_stnorm(model, xs, ys, snap_batch: int = 1):
     return ae / count, (se / count) ** 0.5, (ape / max(ape_count, 1)) * 100
 
 
+def predict_metrics_stnorm(model, xs, ys, snap_batch: int = 1):
+    """predict.py:173-180 for STNorm: (MAE, RMSE, MAPE).  Snapshots run ``snap_batch`` at a time with per-snapshot TNorm
+    (tnorm_group = 1); eval mode reads only the running buffers."""
+    return _predict_metrics_windows(model, xs, ys, snap_batch, lambda x: model(x, tnorm_group=1))
+
+
+def predict_metrics_stid(model, xs, ys, snap_batch: int = 1):
+    """predict.py:173-180 for STID: (MAE, RMSE, MAPE); out is (1, O, N, 1)."""
+    return _predict_metrics_windows(model, xs, ys, snap_batch, lambda x: model(x))
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="RegT-GCN evaluation (reference predict.py metrics)")
     ap.add_argument("--fixture", help=".npz in the layout of tests/golden/tpims_fixture.npz")
     ap.add_argument("--pickle", help="the reference's processed tpims_data_small.pkl")
     ap.add_argument("--checkpoint", required=True)
-    ap.add_argument("--model", default="RegionalTemporalGCN", choices=["RegionalTemporalGCN", "TemporalGCN", "SpatialGCN", "STNorm"])   # predict.py:110-114
+    ap.add_argument("--model", default="RegionalTemporalGCN", choices=["RegionalTemporalGCN", "TemporalGCN", "SpatialGCN", "STNorm", "STID"])   # predict.py:110-114
     ap.add_argument("--num_timesteps_in", default=6, type=int)
     ap.add_argument("--num_timesteps_out", default=1, type=int)
     ap.add_argument("--tr", "--train_ratio", default=0.2, type=float, dest="tr")
@@ -133,6 +144,13 @@ def main(argv=None):
         model = rnn.STNorm(num_nodes=n, in_dim=f, out_dim=a.num_timesteps_out).to(dev)
         model.load_state_dict(torch.load(a.checkpoint, map_location=dev, weights_only=True))
         mae, rmse, mape = predict_metrics_stnorm(model, vx, vy, max(1, a.snap_batch))
+        print("MAE: {:.4f}, RMSE: {:.4f}, MAPE: {:.4f}".format(mae, rmse, mape))
+        return
+    if a.model == "STID":                                     # predict.py:132-133, 173-180
+        model = rnn.STID(num_nodes=n, input_len=a.num_timesteps_in, output_len=a.num_timesteps_out, if_time_in_day=False,
+                         if_day_in_week=False).to(dev)
+        model.load_state_dict(torch.load(a.checkpoint, map_location=dev, weights_only=True))
+        mae, rmse, mape = predict_metrics_stid(model, vx, vy, max(1, a.snap_batch))
         print("MAE: {:.4f}, RMSE: {:.4f}, MAPE: {:.4f}".format(mae, rmse, mape))
         return
     if a.model == "RegionalTemporalGCN":

@@ -644,6 +644,50 @@ class STNormFunction(torch.autograd.Function):
         return (None, None, None) + tuple(grads)
 
 
+def _deliver_grads(params, grads):
+    """Gradients of ``params`` as autograd's return values, or, under :func:`set_grad_accumulation_in_backward`, added to ``.grad``
+    here (one fused add) with None returned for each."""
+    live = [(p, g) for p, g in zip(params, grads) if p is not None and g is not None]
+    if _ACCUMULATE_IN_BACKWARD and all(p.is_leaf and p.requires_grad for p, _ in live):
+        have, new = [], []
+        for p, g in live:
+            if p.grad is None:
+                p.grad = g
+            else:
+                have.append(p.grad)
+                new.append(g)
+        if have:
+            torch._foreach_add_(have, new)
+        return (None,) * len(params)
+    return tuple(grads)
+
+
+class STIDFunction(torch.autograd.Function):
+    """(x (B, L, N, C), dims, keep, *params) -> out (B, output_len, N, 1): the whole STID forward and backward in HIP
+    (regt_stid_forward / regt_stid_backward; ``params`` in state_dict order, None for node_emb when if_node is off; ``keep`` the
+    int32 keep bits or None).  When a gradient is wanted the forward leaves the block inputs and activations in a workspace that
+    the backward reads.  x is data: no dx.  Honours :func:`set_grad_accumulation_in_backward`."""
+
+    @staticmethod
+    def forward(ctx, x, dims, keep, *params):
+        from . import ops
+        save = any(ctx.needs_input_grad[3:])
+        out, ws = ops.stid_forward(dims, x, params, keep, save=save)
+        ctx.dims, ctx.keep, ctx.ws = dims, keep, ws
+        ctx.leaf_params = params
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import ops
+        (x,) = ctx.saved_tensors
+        params = ctx.leaf_params
+        grads = ops.stid_backward(ctx.dims, x, [None if p is None else p.detach() for p in params], ctx.keep, dout.contiguous(), ctx.ws)
+        ctx.ws = None
+        return (None, None, None) + _deliver_grads(params, grads)
+
+
 class ZeroGradAnchor(torch.autograd.Function):
     """Identity on ``(pred, hidden)`` that gives ``dead`` parameters an all-zero gradient: in the reference's GraphSAGE / GAT models
     the reset gate is computed and multiplied by the zero hidden state, so autograd hands its parameters zeros, not None --

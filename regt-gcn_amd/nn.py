@@ -10,6 +10,7 @@ unchanged:
 * :class:`TGCN`                 <-> models/utils.py:69-203 (parameter container of the GRU cell)
 * :class:`SpatialGCN`           <-> models/SpatialGCN.py:8-49
 * :class:`STNorm`               <-> models/STNorm.py:6-185
+* :class:`STID`                 <-> models/STID.py:5-157
 
 The modules only *hold* parameters; all arithmetic runs in libregtgcn_hip.so through
 :class:`regt-gcn_amd.functional.RegTGCNFunction`.  There is no CPU implementation here: calling
@@ -26,7 +27,7 @@ import torch.nn as nn
 from . import _lib
 from . import ops
 from .functional import (HEAD_HIDDEN, PARAM_NAMES_CELL, AggregateFunction, Cell0Function, CellFunction, GatAggregateFunction,
-                         LinearFunction, RegTGCNFunction, SpatialEmbedFunction, STNormFunction, ZeroGradAnchor, param_names)
+                         LinearFunction, RegTGCNFunction, SpatialEmbedFunction, STIDFunction, STNormFunction, ZeroGradAnchor, param_names)
 from .graph import (AttentionPattern, GcnOperator, MeanOperator, PreparedGraph, fingerprint, prepare_attention_pattern,
                     prepare_cheb_operator, prepare_gcn_operator, prepare_graph, prepare_mean_operator)
 
@@ -755,3 +756,90 @@ class STNorm(nn.Module):
         if input.dtype != torch.float32:
             raise _lib.RegtError(f"STNorm input must be float32, got {input.dtype}")
         return STNormFunction.apply(input.contiguous(), dims, self.running_table(), *params)
+
+
+# ---- STID (models/STID.py) -------------------------------------------------------------------------------------------------------------
+
+def draw_stid_keep(num_layer: int, batch: int, num_nodes: int, hidden: int, device, p: float = ops.STID_DROPOUT) -> torch.Tensor:
+    """nn.Dropout(p) keep bits for STID's blocks: (num_layer, batch, num_nodes, hidden / 32) int32, bit j of word w keeps channel
+    32w + j, every bit an independent Bernoulli(1 - p) draw from torch's generator of ``device``.  The bits are packed bytewise and
+    the bytes viewed as int32, so the top bit of a word is as live as the others (see :func:`draw_keep_mask`)."""
+    weights = (2 ** torch.arange(8, device=device)).to(torch.uint8)
+    out = torch.empty(num_layer, batch, num_nodes, hidden // 32, dtype=torch.int32, device=device)
+    for l in range(num_layer):                                    # layer by layer: bounds the transient to 128 bytes per word
+        bits = torch.rand(batch, num_nodes, hidden // 8, 8, device=device) >= p
+        out[l] = (bits.to(torch.uint8) * weights).sum(-1, dtype=torch.uint8).view(torch.int32)
+    return out
+
+
+class _MLPParams(nn.Module):
+    """Parameters of one residual block (models/STID.py:5-15): fc1, fc2 1x1 convolutions."""
+
+    def __init__(self, hidden: int):
+        super().__init__()
+        self.fc1 = nn.Conv2d(hidden, hidden, kernel_size=(1, 1), bias=True)
+        self.fc2 = nn.Conv2d(hidden, hidden, kernel_size=(1, 1), bias=True)
+
+
+class STID(nn.Module):
+    """STID (models/STID.py:32-157) with the reference's constructor, ``forward(history_data (B, L, N, C)) -> (B, output_len, N, 1)``
+    and state_dict, for the configuration run.py:134 / predict.py:133 build: ``if_time_in_day=False, if_day_in_week=False``.  All
+    arithmetic runs in regt_stid_forward / regt_stid_backward; the ``nn.Conv2d`` modules only hold weights and are created in the
+    reference's order, so a seeded construction draws the same initial values.
+
+    Dropout (p = 0.15 inside every block) follows ``self.training``: a training-mode call draws fresh keep bits on the device
+    (:func:`draw_stid_keep`) unless ``keep=`` supplies them, and leaves the bits it used in ``self.last_keep``.  Eval mode ignores
+    ``keep``.  A strided ``history_data`` (train.py's window view) is made contiguous once here; the kernels gather the first
+    ``input_dim`` features of each time step from that tensor themselves."""
+
+    def __init__(self, num_nodes, input_len=12, output_len=12, input_dim=3, embed_dim=32, node_dim=32, temp_dim_tid=32, temp_dim_diw=32,
+                 time_of_day_size=288, day_of_week_size=7, if_node=True, if_time_in_day=True, if_day_in_week=True, num_layer=3):
+        super().__init__()
+        if if_time_in_day or if_day_in_week:
+            raise ValueError("STID runs with if_time_in_day=False and if_day_in_week=False only (as run.py and predict.py construct it): "
+                             "the time-of-day / day-of-week embeddings index their tables with a dataset-specific feature convention "
+                             "(models/STID.py:116-125) that the TPIMS data does not follow")
+        if num_nodes < 1:
+            raise ValueError(f"STID needs num_nodes >= 1, got num_nodes={num_nodes}")
+        ops.stid_limits(input_len, output_len, input_dim, embed_dim, node_dim, num_layer)
+        self.num_nodes, self.node_dim, self.input_len, self.input_dim = num_nodes, node_dim, input_len, input_dim
+        self.embed_dim, self.output_len, self.num_layer = embed_dim, output_len, num_layer
+        self.temp_dim_tid, self.temp_dim_diw = temp_dim_tid, temp_dim_diw
+        self.time_of_day_size, self.day_of_week_size = time_of_day_size, day_of_week_size
+        self.if_time_in_day, self.if_day_in_week, self.if_spatial = if_time_in_day, if_day_in_week, bool(if_node)
+        if self.if_spatial:
+            self.node_emb = nn.Parameter(torch.empty(num_nodes, node_dim))
+            nn.init.xavier_uniform_(self.node_emb)
+        self.time_series_emb_layer = nn.Conv2d(input_dim * input_len, embed_dim, kernel_size=(1, 1), bias=True)
+        self.hidden_dim = embed_dim + node_dim * int(self.if_spatial)
+        self.encoder = nn.Sequential(*[_MLPParams(self.hidden_dim) for _ in range(num_layer)])
+        self.regression_layer = nn.Conv2d(self.hidden_dim, output_len, kernel_size=(1, 1), bias=True)
+        self.last_keep = None
+
+    def param_table(self):
+        """The parameters in state_dict order, the table order of regt_stid_forward (None for node_emb when if_node is off)."""
+        t = [self.node_emb if self.if_spatial else None, self.time_series_emb_layer.weight, self.time_series_emb_layer.bias]
+        for m in self.encoder:
+            t += [m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias]
+        return t + [self.regression_layer.weight, self.regression_layer.bias]
+
+    def forward(self, history_data: torch.Tensor, *, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        _need_cuda(history_data)
+        if history_data.dim() != 4 or history_data.shape[1] != self.input_len or history_data.shape[2] != self.num_nodes \
+                or history_data.shape[3] < self.input_dim:
+            raise ValueError(f"history_data must be (B, {self.input_len}, {self.num_nodes}, C >= {self.input_dim}), got "
+                             f"{tuple(history_data.shape)}")
+        if history_data.dtype != torch.float32:
+            raise _lib.RegtError(f"STID input must be float32, got {history_data.dtype}")
+        b, c = history_data.shape[0], history_data.shape[3]
+        dims = ops.stid_dims(self.num_nodes, b, self.input_len, c, self.input_dim, self.num_layer, self.output_len, self.if_spatial,
+                             self.embed_dim, self.node_dim)
+        params = self.param_table()
+        ops.stid_check_tables(dims, history_data.device, params)            # raw pointers: device, dtype, shape, layout
+        if self.training:
+            if keep is None:
+                keep = draw_stid_keep(self.num_layer, b, self.num_nodes, self.hidden_dim, history_data.device)
+            self.last_keep = keep
+        else:
+            keep = None
+        return STIDFunction.apply(history_data.contiguous(), dims, keep, *params)

@@ -292,3 +292,126 @@ def stnorm_backward(dims: _lib.StnormDims, x: torch.Tensor, params, running, dou
     _lib.check(_lib.load().regt_stnorm_backward(ctypes.byref(dims), _lib.ptr(x), pt, rt if dims.tnorm else None, _lib.ptr(dout), gt,
                                                 _lib.ptr(ws), _lib.ptr(sc), _stream()), "regt_stnorm_backward")
     return grads
+
+
+# ---- STID (models/STID.py) -----------------------------------------------------------------------------------------------------------
+
+STID_DIM = 32                # embed_dim and node_dim the kernels are built for (models/STID.py defaults)
+STID_MAX_LAYERS = 8
+STID_MAX_KIN = 192           # input_dim * input_len: rows of the embedding weight in LDS (include/regtgcn.h)
+STID_MAX_OUT = 64
+STID_DROPOUT = 0.15          # nn.Dropout(p=0.15) of models/STID.py:15
+
+
+def stid_limits(input_len: int, output_len: int, input_dim: int, embed_dim: int, node_dim: int, num_layer: int):
+    """ValueError naming the field unless the dims are inside what regt_stid_* accept (include/regtgcn.h)."""
+    if embed_dim != STID_DIM or node_dim != STID_DIM:
+        raise ValueError(f"STID runs with embed_dim = node_dim = {STID_DIM} only, got embed_dim={embed_dim}, node_dim={node_dim}")
+    if not 1 <= num_layer <= STID_MAX_LAYERS:
+        raise ValueError(f"STID runs with 1 <= num_layer <= {STID_MAX_LAYERS}, got num_layer={num_layer}")
+    if not 1 <= input_len <= 255:
+        raise ValueError(f"STID runs with 1 <= input_len <= 255, got input_len={input_len}")
+    if not 1 <= input_dim <= 256 or input_dim * input_len > STID_MAX_KIN:
+        raise ValueError(f"STID runs with 1 <= input_dim <= 256 and input_dim * input_len <= {STID_MAX_KIN}, got input_dim={input_dim}, "
+                         f"input_len={input_len}")
+    if not 1 <= output_len <= STID_MAX_OUT:
+        raise ValueError(f"STID runs with 1 <= output_len <= {STID_MAX_OUT}, got output_len={output_len}")
+
+
+def stid_dims(n: int, batch: int, input_len: int, in_features: int, input_dim: int, num_layer: int, output_len: int, if_node: bool = True,
+              embed_dim: int = STID_DIM, node_dim: int = STID_DIM, dropout_p: float = STID_DROPOUT) -> _lib.StidDims:
+    return _lib.StidDims(n, batch, input_len, in_features, input_dim, embed_dim, node_dim, num_layer, output_len, int(bool(if_node)),
+                         float(dropout_p))
+
+
+def stid_hidden(dims: _lib.StidDims) -> int:
+    return dims.embed_dim + (dims.node_dim if dims.if_node else 0)
+
+
+def stid_sizes(dims: _lib.StidDims):
+    """(workspace floats, scratch floats) of regt_stid_forward / _backward."""
+    ws, sc = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(_lib.load().regt_stid_sizes(ctypes.byref(dims), ctypes.byref(ws), ctypes.byref(sc)), "regt_stid_sizes")
+    return ws.value, sc.value
+
+
+def stid_table_shapes(dims: _lib.StidDims):
+    """Expected shapes of the parameter table in state_dict order (None: the entry must be None, if_node off)."""
+    h = stid_hidden(dims)
+    shapes = [(dims.num_nodes, dims.node_dim) if dims.if_node else None, (dims.embed_dim, dims.input_dim * dims.input_len, 1, 1),
+              (dims.embed_dim,)]
+    for _ in range(dims.num_layer):
+        shapes += [(h, h, 1, 1), (h,), (h, h, 1, 1), (h,)]
+    return shapes + [(dims.output_len, h, 1, 1), (dims.output_len,)]
+
+
+def stid_check_tables(dims: _lib.StidDims, device, params, what: str = "STID"):
+    """RegtError unless every parameter is a contiguous float32 tensor of its reference shape on ``device``: the kernels read them
+    through raw device pointers."""
+    shapes = stid_table_shapes(dims)
+    if len(params) != len(shapes):
+        raise _lib.RegtError(f"{what}: expected {len(shapes)} parameter entries, got {len(params)}")
+    for i, (t, shape) in enumerate(zip(params, shapes)):
+        if shape is None:
+            if t is not None:
+                raise _lib.RegtError(f"{what}: parameter entry {i} must be None (if_node off)")
+            continue
+        if t is None or not isinstance(t, torch.Tensor):
+            raise _lib.RegtError(f"{what}: parameter entry {i} is missing")
+        if t.dtype != torch.float32 or t.device != torch.device(device) or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise _lib.RegtError(f"{what}: parameter entry {i} must be a contiguous float32 {shape} tensor on {device}, got "
+                                 f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else " (not contiguous)"))
+
+
+def stid_keep_shape(dims: _lib.StidDims):
+    return (dims.num_layer, dims.batch, dims.num_nodes, stid_hidden(dims) // 32)
+
+
+def _stid_keep_ptr(dims: _lib.StidDims, keep: Optional[torch.Tensor], dev):
+    if keep is None:
+        return None
+    shape = stid_keep_shape(dims)
+    if keep.dtype != torch.int32 or keep.device != dev or tuple(keep.shape) != shape or not keep.is_contiguous():
+        raise ValueError(f"keep must be a contiguous int32 {shape} tensor on {dev}")
+    return _lib.ptr(keep)
+
+
+def _stid_x(dims: _lib.StidDims, x: torch.Tensor) -> torch.Tensor:
+    x = _f32c(x, "x")
+    shape = (dims.batch, dims.input_len, dims.num_nodes, dims.in_features)
+    if tuple(x.shape) != shape:
+        raise ValueError(f"x must be {shape}, got {tuple(x.shape)}")
+    return x
+
+
+def stid_forward(dims: _lib.StidDims, x: torch.Tensor, params, keep: Optional[torch.Tensor] = None, save: bool = True):
+    """out (B, output_len, N, 1) of STID for x (B, L, N, C); ``params`` in state_dict order (None for node_emb when if_node is off);
+    ``keep``: int32 keep bits (num_layer, B, N, hidden / 32) or None (eval).  Returns (out, workspace): with ``save`` the workspace
+    holds what regt_stid_backward reads, else it is None."""
+    x = _stid_x(dims, x)
+    stid_check_tables(dims, x.device, params, "regt_stid_forward")
+    kp = _stid_keep_ptr(dims, keep, x.device)
+    out = torch.empty(dims.batch, dims.output_len, dims.num_nodes, 1, dtype=torch.float32, device=x.device)
+    ws = torch.empty(stid_sizes(dims)[0], dtype=torch.float32, device=x.device) if save else None
+    _lib.check(_lib.load().regt_stid_forward(ctypes.byref(dims), _lib.ptr(x), _ptr_table(params), kp, _lib.ptr(out),
+                                             None if ws is None else _lib.ptr(ws), _stream()), "regt_stid_forward")
+    return out, ws
+
+
+def stid_backward(dims: _lib.StidDims, x: torch.Tensor, params, keep: Optional[torch.Tensor], dout: torch.Tensor, ws: torch.Tensor):
+    """Gradients of every entry of ``params`` (None where the entry is None) from dL/dout; ``ws`` is the forward's workspace and
+    ``keep`` the keep bits it ran with."""
+    x, dout = _stid_x(dims, x), _f32c(dout, "dout")
+    stid_check_tables(dims, x.device, params, "regt_stid_backward")
+    kp = _stid_keep_ptr(dims, keep, x.device)
+    ws_n, sc_n = stid_sizes(dims)
+    out_shape = (dims.batch, dims.output_len, dims.num_nodes, 1)
+    if tuple(dout.shape) != out_shape or dout.device != x.device:
+        raise ValueError(f"dout must be {out_shape} on {x.device}, got {tuple(dout.shape)} on {dout.device}")
+    if ws is None or ws.dtype != torch.float32 or ws.device != x.device or ws.numel() != ws_n or not ws.is_contiguous():
+        raise ValueError("ws must be the workspace stid_forward(save=True) returned for these dims")
+    sc = torch.empty(sc_n, dtype=torch.float32, device=x.device)
+    grads = [None if p is None else torch.empty_like(p) for p in params]
+    _lib.check(_lib.load().regt_stid_backward(ctypes.byref(dims), _lib.ptr(x), _ptr_table(params), kp, _lib.ptr(dout), _ptr_table(grads),
+                                              _lib.ptr(ws), _lib.ptr(sc), _stream()), "regt_stid_backward")
+    return grads

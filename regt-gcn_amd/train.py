@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import argparse
 import os
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -192,25 +192,28 @@ def split(xs, ys, ratio: float):
 
 
 # models of run.py:115-136: those built on the TGCN cell (the hot path and the SURVEY 8(f) baselines), SpatialGCN (two ChebConv
-# layers, run.py:117-118) and STNorm (gated dilated convolutions with temporal / spatial normalisation, no graph, run.py:135-136);
-# TemporalGConvLSTM (which run.py:122 cannot construct), StackedGRU, STAEformer and STID are out of scope
+# layers, run.py:117-118), STNorm (gated dilated convolutions with temporal / spatial normalisation, no graph, run.py:135-136) and
+# STID (a per-node MLP on the node's history and a learned node embedding, no graph, run.py:133-134); TemporalGConvLSTM (which
+# run.py:122 cannot construct), StackedGRU and STAEformer are out of scope
 MODELS = ("RegionalTemporalGCN", "RandomTemporalGCN", "TemporalGCN", "ConvStackedTemporalGCN", "GraphSAGETemporalGCN", "GAT", "GATTemporal",
-          "SpatialGCN", "STNorm")
+          "SpatialGCN", "STNorm", "STID")
 
 
-# ---- STNorm (run.py:181-184, 217-221) -------------------------------------------------------------------------------------------------
-# run.py feeds STNorm batch.x.permute(2, 0, 1).unsqueeze(0) -- (1, T, N, F) -- and takes mean((out - y)**2) with out (1, O, N, L_out)
-# and y (N, O): for O > 1 that broadcasts to (1, O, N, O), kept as it is.  test() compares out[0][0] (N, L_out) with y (N, O).  A
-# batch of B snapshots runs as one (B, T, N, F) call with tnorm_group = 1: TNorm's statistics and running-buffer updates stay per
-# snapshot, in snapshot order, so the losses, the accumulated gradients and the buffers are those of B sequential run.py steps.
+# ---- STNorm and STID (run.py:181-186, 217-222) ------------------------------------------------------------------------------------------
+# run.py feeds both batch.x.permute(2, 0, 1).unsqueeze(0) -- (1, T, N, F) -- and takes mean((out - y)**2) with out (1, O, N, L_out)
+# (L_out = 1 for STID) and y (N, O): for O > 1 that broadcasts to (1, O, N, O), kept as it is.  test() compares out[0][0] (N, L_out)
+# with y (N, O).  A batch of B snapshots runs as one (B, T, N, F) call.  STNorm takes tnorm_group = 1: TNorm's statistics and
+# running-buffer updates stay per snapshot, in snapshot order, so the losses, the accumulated gradients and the buffers are those of
+# B sequential run.py steps.  STID has no batch statistics: the batch is just B independent snapshots.  The window view below is
+# strided; both modules make it contiguous once.
 
 def stnorm_batch(store: "WindowStore", i: int, b: int):
-    """Snapshots i .. i+b-1 as STNorm's input (b, T, N, F) and their targets (b, N, O)."""
+    """Snapshots i .. i+b-1 as STNorm's / STID's input (b, T, N, F) and their targets (b, N, O)."""
     return store.X[i:i + b].permute(0, 3, 1, 2), store.Y[i:i + b]
 
 
-def train_epoch_stnorm(model, store: "WindowStore", optimizer, snap_batch: int) -> Tuple[torch.Tensor, List[torch.Tensor]]:
-    """run.py::train() for STNorm; returns (last snapshot's loss, all per-snapshot losses)."""
+def _train_epoch_windows(model, store: "WindowStore", optimizer, snap_batch: int, call) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """run.py::train() for the models fed (b, T, N, F) windows; ``call(x, i, b)`` runs the model on snapshots i .. i+b-1."""
     model.train()
     losses = []
     prev = F_.set_grad_accumulation_in_backward(True)
@@ -218,8 +221,8 @@ def train_epoch_stnorm(model, store: "WindowStore", optimizer, snap_batch: int) 
         for i in range(0, len(store), snap_batch):
             b = min(snap_batch, len(store) - i)
             x, y = stnorm_batch(store, i, b)
-            out = model(x, tnorm_group=1)
-            per = ((out - y.unsqueeze(1)) ** 2).mean(dim=(1, 2, 3))       # run.py:184 per snapshot
+            out = call(x, i, b)
+            per = ((out - y.unsqueeze(1)) ** 2).mean(dim=(1, 2, 3))       # run.py:184 / :186 per snapshot
             per.sum().backward()
             losses.append(per.detach())
     finally:
@@ -231,19 +234,42 @@ def train_epoch_stnorm(model, store: "WindowStore", optimizer, snap_batch: int) 
 
 
 @torch.no_grad()
-def evaluate_stnorm(model, store: "WindowStore", snap_batch: int) -> Tuple[float, float]:
-    """run.py::test() for STNorm: (rmse, mse) of out[0][0] against y."""
+def _evaluate_windows(model, store: "WindowStore", snap_batch: int, call) -> Tuple[float, float]:
+    """run.py::test() for the same models: (rmse, mse) of out[0][0] against y."""
     model.eval()
     se = torch.zeros((), dtype=torch.float64, device=store.X.device)
     count = 0
     for i in range(0, len(store), snap_batch):
         b = min(snap_batch, len(store) - i)
         x, y = stnorm_batch(store, i, b)
-        e = (model(x, tnorm_group=1)[:, 0] - y) ** 2
+        e = (call(x, i, b)[:, 0] - y) ** 2
         se += e.sum(dtype=torch.float64)
         count += e.numel()
     m = float(se) / float(max(count, 1))
     return m ** 0.5, m
+
+
+def train_epoch_stnorm(model, store: "WindowStore", optimizer, snap_batch: int) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """run.py::train() for STNorm; returns (last snapshot's loss, all per-snapshot losses)."""
+    return _train_epoch_windows(model, store, optimizer, snap_batch, lambda x, i, b: model(x, tnorm_group=1))
+
+
+def evaluate_stnorm(model, store: "WindowStore", snap_batch: int) -> Tuple[float, float]:
+    """run.py::test() for STNorm: (rmse, mse) of out[0][0] against y."""
+    return _evaluate_windows(model, store, snap_batch, lambda x, i, b: model(x, tnorm_group=1))
+
+
+def train_epoch_stid(model, store: "WindowStore", optimizer, snap_batch: int,
+                     keeps: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """run.py::train() for STID; returns (last snapshot's loss, all per-snapshot losses).  ``keeps``: the dropout keep bits of all
+    snapshots, int32 (num_layer, len(store), N, hidden / 32), instead of a fresh draw per call."""
+    return _train_epoch_windows(model, store, optimizer, snap_batch,
+                                lambda x, i, b: model(x, keep=None if keeps is None else keeps[:, i:i + b].contiguous()))
+
+
+def evaluate_stid(model, store: "WindowStore", snap_batch: int) -> Tuple[float, float]:
+    """run.py::test() for STID: (rmse, mse) of out[0][0] (N, 1) against y (N, O)."""
+    return _evaluate_windows(model, store, snap_batch, lambda x, i, b: model(x))
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -348,6 +374,14 @@ def main(argv=None):
             raise SystemExit("--fused_step covers RegionalTemporalGCN (regional decomposition) / TemporalGCN")
         model = rnn.STNorm(num_nodes=n, in_dim=f, out_dim=a.num_timesteps_out).to(dev)
         graph = None
+    elif a.model == "STID":                                                 # run.py:133-134 (input_dim = 3, the module's default)
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("STID runs on one GPU (it has no graph to shard; its kernels take all nodes in one launch)")
+        if a.fused_step:
+            raise SystemExit("--fused_step covers RegionalTemporalGCN (regional decomposition) / TemporalGCN")
+        model = rnn.STID(num_nodes=n, input_len=a.num_timesteps_in, output_len=a.num_timesteps_out, if_time_in_day=False,
+                         if_day_in_week=False).to(dev)
+        graph = None
     elif a.model == "GraphSAGETemporalGCN":                                 # run.py:127-128
         model = rnn.GraphSAGETemporalGCN(f, n, a.num_timesteps_in, a.num_timesteps_out).to(dev)
         graph = model.prepare_graph(ei, n)
@@ -365,11 +399,12 @@ def main(argv=None):
         os.makedirs("logs", exist_ok=True)
         log = open(os.path.join("logs", datetime.datetime.now().strftime("%y-%m-%d_%H-%M") + ".txt"), "a")
     batched = None
-    if a.model == "STNorm":
+    if a.model in ("STNorm", "STID"):
         from_store = (WindowStore(tx, ty), WindowStore(vx, vy))
+        train_fn, eval_fn = (train_epoch_stnorm, evaluate_stnorm) if a.model == "STNorm" else (train_epoch_stid, evaluate_stid)
         for epoch in range(a.epochs + 1):
-            last, _ = train_epoch_stnorm(model, from_store[0], opt, max(1, a.snap_batch))
-            rmse, mse = evaluate_stnorm(model, from_store[1], max(1, a.snap_batch))
+            last, _ = train_fn(model, from_store[0], opt, max(1, a.snap_batch))
+            rmse, mse = eval_fn(model, from_store[1], max(1, a.snap_batch))
             _report(a, log, out_dir, model, epoch, last, rmse, mse)
         return
     if a.snap_batch > 1:
