@@ -380,6 +380,37 @@ int32_t regt_stid_forward(const regt_stid_dims* dims, const float* x, const floa
 int32_t regt_stid_backward(const regt_stid_dims* dims, const float* x, const float* const* params, const uint32_t* keep,
                            const float* dout, float* const* grads, const float* workspace, float* scratch, regt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * One torch.nn.GRU layer (one layer, one direction, gates stacked r, z, n) over a whole sequence: what models/StackedGRU.py
+ * runs twice.  r = sigmoid(W_ir x + b_ir + W_hr h + b_hr), z likewise, n = tanh(W_in x + b_in + r (W_hn h + b_hn)),
+ * h' = (1 - z) n + z h.
+ *   x: element (step s, row b, input k) at x[s * x_stride_seq + b * x_stride_row + k * x_stride_t] (strides in elements, >= 0),
+ *   read in place.  w_ih (768, input_size), w_hh (768, 256), b_ih, b_hh (768).  h0 (rows, 256) or NULL (zeros).
+ *   out (seq_len, rows, 256) or NULL; h_last (rows, 256) or NULL; not both NULL.
+ *   workspace: workspace_floats floats, always required (it holds the repacked weights); with training = 1 the forward also
+ *   leaves every step's state and gate activations there for the backward.  The size depends on training.
+ *   regt_gru_backward (training = 1 only): weights = {w_ih, w_hh, b_ih, b_hh}, grads the same layout (overwritten);
+ *   dout (seq_len, rows, 256) or NULL, dh_last (rows, 256) or NULL, not both NULL; dh0 (rows, 256) or NULL receives the
+ *   gradient of h0.  h0 is accepted for symmetry and not read (the workspace holds it).  scratch: scratch_floats floats.
+ *   Limits: hidden == 256; 1 <= input_size <= 255; seq_len >= 1; rows >= 1; seq_len * rows < 2^31 - rows.  workspace and
+ *   scratch 16-byte aligned.  One workgroup owns 8 rows for the whole sequence and waits for no other workgroup.  Sums run in
+ *   a fixed order without float atomics: bit-reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t seq_len, rows, input_size, hidden, training;
+    int64_t x_stride_seq, x_stride_row, x_stride_t;
+} regt_gru_dims;
+int32_t regt_gru_sizes(const regt_gru_dims* dims, size_t* workspace_floats, size_t* scratch_floats);
+int32_t regt_gru_forward(const regt_gru_dims* dims, const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                         const float* b_hh, const float* h0, float* out, float* h_last, float* workspace, regt_stream_t stream);
+int32_t regt_gru_backward(const regt_gru_dims* dims, const float* x, const float* const* weights, const float* h0, const float* dout,
+                          const float* dh_last, float* const* grads, float* dh0, const float* workspace, float* scratch,
+                          regt_stream_t stream);
+
+/* relu's gradient in place: d[i] = 0 where y[i] <= 0, y the relu's output (the head of StackedGRU between two regt_linear calls).
+ * 1 <= n < 2^31. */
+int32_t regt_relu_backward(const float* y, float* d, int64_t n, regt_stream_t stream);
+
 /* Arithmetic of the dense contractions.  0 (default): fp32 MFMA (v_mfma_f32_32x32x2_f32).  1: every fp32 operand is
  * split exactly into three bf16 pieces and the six leading partial products run on the bf16 MFMA with fp32
  * accumulation -- fp32-level rounding error (dropped terms <= 3 * 2^-24 of a product), ~2x the matrix-pipe rate.

@@ -56,6 +56,11 @@ class StidDims(C.Structure):
                                          "num_layer", "output_len", "if_node")] + [("dropout_p", C.c_float)]
 
 
+class GruDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("seq_len", "rows", "input_size", "hidden", "training")] + \
+               [(n, C.c_int64) for n in ("x_stride_seq", "x_stride_row", "x_stride_t")]
+
+
 class Graph(C.Structure):
     _fields_ = [("rowptr", vp), ("col", vp), ("val", vp), ("node_region", vp), ("chunk_tab", vp),
                 ("chunk_region", vp), ("n_chunks", C.c_int32),
@@ -136,6 +141,10 @@ SIGNATURES = {
     "regt_stid_sizes": (C.c_int32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "regt_stid_forward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp]),
     "regt_stid_backward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "regt_gru_sizes": (C.c_int32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "regt_gru_forward": (C.c_int32, [vp] * 11),
+    "regt_gru_backward": (C.c_int32, [vp] * 11),
+    "regt_relu_backward": (C.c_int32, [vp, vp, C.c_int64, vp]),
     "regt_mse_loss_grad": (C.c_int32, [vp, vp, vp, vp, C.c_int64, C.c_int64, vp]),
 }
 

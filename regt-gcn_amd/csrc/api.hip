@@ -1739,6 +1739,59 @@ int32_t regt_stid_backward(const regt_stid_dims* d, const float* x, const float*
     return regt::launch_stid_bwd(s, x, params, keep, dout, grads, ws, scratch, (hipStream_t)st);
 }
 
+int32_t regt_relu_backward(const float* y, float* d, int64_t n, regt_stream_t st) {
+    REGT_CHECK_ARG(y && d, "regt_relu_backward: y or d is NULL");
+    REGT_CHECK_ARG(n >= 1 && n < (1L << 31), "regt_relu_backward: n must be in [1, 2^31), got %ld", (long)n);   // one thread each
+    return regt::launch_relu_mask(y, d, (long)n, (hipStream_t)st);
+}
+
+static int gru_check(const char* what, const regt_gru_dims* d, regt::GruDims* s) {
+    REGT_CHECK_ARG(d != nullptr, "%s: dims is NULL", what);
+    REGT_CHECK_ARG(d->hidden == regt::GRU_HIDDEN, "%s: hidden must be %d, got %d", what, regt::GRU_HIDDEN, d->hidden);
+    REGT_CHECK_ARG(d->input_size >= 1 && d->input_size <= regt::GRU_MAX_INPUT, "%s: input_size must be in [1, %d], got %d", what,
+                   regt::GRU_MAX_INPUT, d->input_size);
+    REGT_CHECK_ARG(d->seq_len >= 1, "%s: seq_len must be >= 1, got %d", what, d->seq_len);
+    REGT_CHECK_ARG(d->rows >= 1, "%s: rows must be >= 1, got %d", what, d->rows);
+    REGT_CHECK_ARG((long)d->seq_len * d->rows < (1L << 31) - d->rows, "%s: seq_len * rows must be below 2^31, got %d * %d", what, d->seq_len,
+                   d->rows);
+    REGT_CHECK_ARG(d->x_stride_seq >= 0 && d->x_stride_row >= 0 && d->x_stride_t >= 0, "%s: x strides must be >= 0", what);
+    *s = regt::GruDims{d->seq_len, d->rows, d->input_size, d->hidden, d->training ? 1 : 0, (long)d->x_stride_seq, (long)d->x_stride_row,
+                       (long)d->x_stride_t};
+    return REGT_OK;
+}
+
+int32_t regt_gru_sizes(const regt_gru_dims* d, size_t* ws, size_t* scratch) {
+    regt::GruDims s;
+    if (int rc = gru_check("regt_gru_sizes", d, &s)) return rc;
+    regt::gru_sizes(s, ws, scratch);
+    return REGT_OK;
+}
+
+int32_t regt_gru_forward(const regt_gru_dims* d, const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                         const float* h0, float* out, float* h_last, float* ws, regt_stream_t st) {
+    regt::GruDims s;
+    if (int rc = gru_check("regt_gru_forward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh, "regt_gru_forward: x or a weight is NULL");
+    REGT_CHECK_ARG(ws != nullptr, "regt_gru_forward: workspace is NULL");
+    REGT_CHECK_ARG(out || h_last, "regt_gru_forward: out and h_last are both NULL");
+    REGT_CHECK_ARG(((uintptr_t)ws & 15) == 0, "regt_gru_forward: workspace must be 16-byte aligned");
+    return regt::launch_gru_fwd(s, x, w_ih, w_hh, b_ih, b_hh, h0, out, h_last, ws, (hipStream_t)st);
+}
+
+int32_t regt_gru_backward(const regt_gru_dims* d, const float* x, const float* const* weights, const float* h0, const float* dout,
+                          const float* dh_last, float* const* grads, float* dh0, const float* ws, float* scratch, regt_stream_t st) {
+    regt::GruDims s;
+    if (int rc = gru_check("regt_gru_backward", d, &s)) return rc;
+    (void)h0;                                                   // the workspace holds it as step 0's previous state
+    REGT_CHECK_ARG(s.training, "regt_gru_backward: dims.training must be 1 (the forward saves nothing otherwise)");
+    REGT_CHECK_ARG(x && ws && scratch, "regt_gru_backward: x, workspace or scratch is NULL");
+    REGT_CHECK_ARG(weights && grads, "regt_gru_backward: weights or grads table is NULL");
+    for (int k = 0; k < 4; ++k) REGT_CHECK_ARG(weights[k] && grads[k], "regt_gru_backward: weights or grads entry %d is NULL", k);
+    REGT_CHECK_ARG(dout || dh_last, "regt_gru_backward: dout and dh_last are both NULL");
+    REGT_CHECK_ARG((((uintptr_t)ws | (uintptr_t)scratch) & 15) == 0, "regt_gru_backward: workspace and scratch must be 16-byte aligned");
+    return regt::launch_gru_bwd(s, x, weights[1], dout, dh_last, grads, dh0, ws, scratch, (hipStream_t)st);
+}
+
 int64_t regt_debug_trace(int64_t* out_host, int64_t capacity) { return fused_trace_fetch(reinterpret_cast<long*>(out_host), (long)capacity); }
 
 int32_t regt_profile_enable(int32_t on) {

@@ -370,6 +370,18 @@ int launch_stid_fwd(const StidDims& s, const float* x, const float* const* P, co
 int launch_stid_bwd(const StidDims& s, const float* x, const float* const* P, const uint32_t* keep, const float* dout, float* const* G,
                     const float* ws, float* scratch, hipStream_t st);
 
+// One torch.nn.GRU layer over a whole sequence (gru.hip): a persistent forward and a persistent reverse pass, each workgroup owning
+// GRU_RT batch rows for all steps, then fixed-order weight-gradient contractions.  x is read through three element strides.
+struct GruDims { int seq_len, rows, input_size, hidden, training; long x_stride_seq, x_stride_row, x_stride_t; };
+constexpr int GRU_HIDDEN = 256, GRU_RT = 8, GRU_MAX_INPUT = 255;
+void gru_sizes(const GruDims& s, size_t* ws_floats, size_t* scratch_floats);
+int launch_gru_fwd(const GruDims& s, const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                   const float* h0, float* out, float* h_last, float* ws, hipStream_t st);
+int launch_relu_mask(const float* y, float* d, long n, hipStream_t st);      // d[i] = 0 where y[i] <= 0 (relu's gradient, in place)
+// grads: dW_ih, dW_hh, db_ih, db_hh
+int launch_gru_bwd(const GruDims& s, const float* x, const float* w_hh, const float* dout, const float* dh_last, float* const* grads,
+                   float* dh0, const float* ws, float* scratch, hipStream_t st);
+
 // hipFuncSetAttribute is a (slow, host-synchronous) driver call: do it once per kernel, not per launch.
 template <class K>
 static int set_lds_once(K kernel, int bytes, bool* done) {

@@ -80,19 +80,21 @@ def load_processed_pickle(path: str) -> Dict[str, torch.Tensor]:
 
 
 @torch.no_grad()
-def _predict_metrics_windows(model, xs, ys, snap_batch: int, call):
+def _predict_metrics_windows(model, xs, ys, snap_batch: int, call, stack=lambda x: x.permute(0, 3, 1, 2),
+                             pick=lambda out, k, b: out[k:k + 1]):
     """predict.py:173-180 for the models fed (b, T, N, F) windows: the errors are ``batch.y - out`` with out (1, O, N, L_out) and
     y (N, O), broadcast as the reference broadcasts them; MAPE divides by the 95th percentile of the snapshot's y and skips a
-    snapshot whose ratio is infinite."""
+    snapshot whose ratio is infinite.  ``stack`` turns the stacked snapshots (b, N, F, T) into the model's input and ``pick(out, k, b)``
+    gives snapshot k's prediction (StackedGRU batches and slices differently: predict_metrics_gru)."""
     model.eval()
     ae = se = ape = 0.0
     count = ape_count = 0
     for i in range(0, len(xs), snap_batch):
-        x = torch.stack(list(xs[i:i + snap_batch])).permute(0, 3, 1, 2)          # (b, T, N, F)
+        x = stack(torch.stack(list(xs[i:i + snap_batch])))                       # (b, T, N, F)
         y = torch.stack(list(ys[i:i + snap_batch]))
         out = call(x)
-        for k in range(x.shape[0]):
-            err = (y[k] - out[k:k + 1]).double()
+        for k in range(y.shape[0]):
+            err = (y[k] - pick(out, k, y.shape[0])).double()
             ae += float(err.abs().sum())
             se += float((err ** 2).sum())
             count += err.numel()
@@ -114,12 +116,24 @@ def predict_metrics_stid(model, xs, ys, snap_batch: int = 1):
     return _predict_metrics_windows(model, xs, ys, snap_batch, lambda x: model(x))
 
 
+def predict_metrics_gru(model, xs, ys, snap_batch: int = 1):
+    """predict.py:155-162 for StackedGRU: (MAE, RMSE, MAPE) of ``batch.y - out[:, -1, :]``.  ``snap_batch`` snapshots run as
+    stacked batch rows (N, 8 b, T); snapshot k's prediction is its last feature row."""
+    def stack(x):                                                                # (b, N, F, T) -> (N, F b, T)
+        return x[0] if x.shape[0] == 1 else x.permute(1, 0, 2, 3).reshape(x.shape[1], x.shape[0] * x.shape[2], x.shape[3])
+
+    def pick(out, k, b):                                                         # (N, F b, O) -> snapshot k's (N, O)
+        return out.view(out.shape[0], b, -1, out.shape[2])[:, k, -1, :]
+
+    return _predict_metrics_windows(model, xs, ys, snap_batch, lambda x: model(x), stack=stack, pick=pick)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="RegT-GCN evaluation (reference predict.py metrics)")
     ap.add_argument("--fixture", help=".npz in the layout of tests/golden/tpims_fixture.npz")
     ap.add_argument("--pickle", help="the reference's processed tpims_data_small.pkl")
     ap.add_argument("--checkpoint", required=True)
-    ap.add_argument("--model", default="RegionalTemporalGCN", choices=["RegionalTemporalGCN", "TemporalGCN", "SpatialGCN", "STNorm", "STID"])   # predict.py:110-114
+    ap.add_argument("--model", default="RegionalTemporalGCN", choices=["RegionalTemporalGCN", "TemporalGCN", "SpatialGCN", "STNorm", "STID", "StackedGRU"])   # predict.py:110-114
     ap.add_argument("--num_timesteps_in", default=6, type=int)
     ap.add_argument("--num_timesteps_out", default=1, type=int)
     ap.add_argument("--tr", "--train_ratio", default=0.2, type=float, dest="tr")
@@ -151,6 +165,13 @@ def main(argv=None):
                          if_day_in_week=False).to(dev)
         model.load_state_dict(torch.load(a.checkpoint, map_location=dev, weights_only=True))
         mae, rmse, mape = predict_metrics_stid(model, vx, vy, max(1, a.snap_batch))
+        print("MAE: {:.4f}, RMSE: {:.4f}, MAPE: {:.4f}".format(mae, rmse, mape))
+        return
+    if a.model == "StackedGRU":                               # predict.py:122-123, 155-162
+        model = rnn.StackedGRU(in_channels=a.num_timesteps_in, node_features=f, periods=a.num_timesteps_in,
+                               output_dim=a.num_timesteps_out).to(dev)
+        model.load_state_dict(torch.load(a.checkpoint, map_location=dev, weights_only=True))
+        mae, rmse, mape = predict_metrics_gru(model, vx, vy, max(1, a.snap_batch))
         print("MAE: {:.4f}, RMSE: {:.4f}, MAPE: {:.4f}".format(mae, rmse, mape))
         return
     if a.model == "RegionalTemporalGCN":

@@ -688,6 +688,58 @@ class STIDFunction(torch.autograd.Function):
         return (None, None, None) + _deliver_grads(params, grads)
 
 
+class GRUFunction(torch.autograd.Function):
+    """(x (seq_len, rows, T), h0 (1, rows, 256) | None, want_out, want_last, weight_ih, weight_hh, bias_ih, bias_hh) ->
+    (out (seq_len, rows, 256) | None, h_last (1, rows, 256) | None): one torch.nn.GRU layer in HIP (regt_gru_forward /
+    regt_gru_backward).  When a gradient is wanted the forward leaves every step's state and gates in a workspace that the reverse
+    pass reads.  x is data: no dx; h0 receives its gradient.  Honours :func:`set_grad_accumulation_in_backward`."""
+
+    @staticmethod
+    def forward(ctx, x, h0, want_out, want_last, *weights):
+        from . import ops
+        ctx.set_materialize_grads(False)
+        save = any(ctx.needs_input_grad[4:]) or ctx.needs_input_grad[1]
+        out, last, dims, ws = ops.gru_forward(x, [w.detach() for w in weights], h0, want_out, want_last, save=save)
+        ctx.dims, ctx.ws, ctx.x = dims, ws if save else None, x
+        ctx.leaf_params = weights
+        ctx.want_dh0 = h0 is not None and ctx.needs_input_grad[1]
+        return out, last
+
+    @staticmethod
+    def backward(ctx, dout, dlast):
+        from . import ops
+        weights = ctx.leaf_params
+        grads, dh0 = ops.gru_backward(ctx.dims, ctx.x, [w.detach() for w in weights], dout, dlast, ctx.ws, ctx.want_dh0)
+        ctx.ws = None
+        return (None, dh0, None, None) + _deliver_grads(weights, grads)
+
+
+class MLPHeadFunction(torch.autograd.Function):
+    """(a (M, K), w1 (H1, K), b1, w2 (O, H1), b2) -> relu(a w1^T + b1) w2^T + b2 on the dense entry points (regt_linear, regt_wgrad,
+    regt_relu_backward): StackedGRU's linear1 / relu / linear2.  Honours :func:`set_grad_accumulation_in_backward`."""
+
+    @staticmethod
+    def forward(ctx, a, w1, b1, w2, b2):
+        from . import ops
+        y1 = ops.linear(a, w1, b1, 2)
+        ctx.save_for_backward(a, y1)
+        ctx.leaf_params = (w1, b1, w2, b2)
+        ctx.need_da = ctx.needs_input_grad[0]
+        return ops.linear(y1, w2, b2, 0)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import ops
+        a, y1 = ctx.saved_tensors
+        w1, b1, w2, b2 = ctx.leaf_params
+        dy = dy.contiguous()
+        dw2, db2 = ops.wgrad(dy, y1)
+        d1 = ops.relu_backward_(y1, ops.linear(dy, w2.detach().t().contiguous(), None, 0))
+        dw1, db1 = ops.wgrad(d1, a)
+        da = ops.linear(d1, w1.detach().t().contiguous(), None, 0) if ctx.need_da else None
+        return (da,) + _deliver_grads((w1, b1, w2, b2), (dw1, db1, dw2, db2))
+
+
 class ZeroGradAnchor(torch.autograd.Function):
     """Identity on ``(pred, hidden)`` that gives ``dead`` parameters an all-zero gradient: in the reference's GraphSAGE / GAT models
     the reset gate is computed and multiplied by the zero hidden state, so autograd hands its parameters zeros, not None --

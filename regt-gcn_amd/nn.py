@@ -11,6 +11,7 @@ unchanged:
 * :class:`SpatialGCN`           <-> models/SpatialGCN.py:8-49
 * :class:`STNorm`               <-> models/STNorm.py:6-185
 * :class:`STID`                 <-> models/STID.py:5-157
+* :class:`StackedGRU`           <-> models/StackedGRU.py:4-30
 
 The modules only *hold* parameters; all arithmetic runs in libregtgcn_hip.so through
 :class:`regt-gcn_amd.functional.RegTGCNFunction`.  There is no CPU implementation here: calling
@@ -27,7 +28,7 @@ import torch.nn as nn
 from . import _lib
 from . import ops
 from .functional import (HEAD_HIDDEN, PARAM_NAMES_CELL, AggregateFunction, Cell0Function, CellFunction, GatAggregateFunction,
-                         LinearFunction, RegTGCNFunction, SpatialEmbedFunction, STIDFunction, STNormFunction, ZeroGradAnchor, param_names)
+                         GRUFunction, LinearFunction, MLPHeadFunction, RegTGCNFunction, SpatialEmbedFunction, STIDFunction, STNormFunction, ZeroGradAnchor, param_names)
 from .graph import (AttentionPattern, GcnOperator, MeanOperator, PreparedGraph, fingerprint, prepare_attention_pattern,
                     prepare_cheb_operator, prepare_gcn_operator, prepare_graph, prepare_mean_operator)
 
@@ -843,3 +844,46 @@ class STID(nn.Module):
         else:
             keep = None
         return STIDFunction.apply(history_data.contiguous(), dims, keep, *params)
+
+
+# ---- StackedGRU (models/StackedGRU.py) ----------------------------------------------------------------------------------------------
+
+class StackedGRU(nn.Module):
+    """StackedGRU (models/StackedGRU.py:4-30) with the reference's constructor, ``forward(x (N, rows, T), edge_index) ->
+    (N, rows, output_dim)`` and 12-entry state_dict.  ``nn.GRU`` is sequence-first, so -- exactly as in the reference -- the
+    sequence runs over the N nodes, the 8 node features (or 8 B of them for B stacked snapshots) are independent batch rows and
+    the T periods are the input vector.  ``gru``'s sequence output is dead in the reference (its relu is overwritten): only its
+    final state is computed, as ``gru2``'s initial state.  All arithmetic runs in regt_gru_forward / regt_gru_backward and the
+    dense entry points; the ``nn.GRU`` / ``nn.Linear`` modules only hold weights and are created in the reference's order, so a
+    seeded construction draws the same initial values.  ``x`` is read in place through its strides."""
+
+    def __init__(self, in_channels, node_features, periods, output_dim):
+        super().__init__()
+        hidden_dim = ops.GRU_HIDDEN
+        ops.gru_limits(in_channels, hidden_dim)
+        if output_dim < 1:
+            raise ValueError(f"StackedGRU needs output_dim >= 1, got output_dim={output_dim}")
+        self.in_channels, self.output_dim, self.periods, self.node_features = in_channels, output_dim, periods, node_features
+        self.gru = nn.GRU(input_size=in_channels, hidden_size=hidden_dim)
+        self.gru2 = nn.GRU(input_size=in_channels, hidden_size=hidden_dim)
+        self.linear1 = nn.Linear(hidden_dim, hidden_dim)
+        self.linear2 = nn.Linear(hidden_dim, output_dim)
+
+    @staticmethod
+    def _weights(g: nn.GRU):
+        return [g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0]
+
+    def forward(self, x: torch.Tensor, edge_index=None) -> torch.Tensor:
+        _need_cuda(x)
+        if x.dim() != 3 or x.shape[2] != self.in_channels or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"x must be (N, rows, {self.in_channels}), got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise _lib.RegtError(f"StackedGRU input must be float32, got {x.dtype}")
+        w1, w2 = self._weights(self.gru), self._weights(self.gru2)
+        ops.gru_check_weights(self.in_channels, x.device, w1, "StackedGRU.gru")
+        ops.gru_check_weights(self.in_channels, x.device, w2, "StackedGRU.gru2")
+        _, h = GRUFunction.apply(x, None, False, True, *w1)
+        out, _ = GRUFunction.apply(x, h, True, False, *w2)
+        y = MLPHeadFunction.apply(out.view(-1, ops.GRU_HIDDEN), self.linear1.weight, self.linear1.bias, self.linear2.weight,
+                                  self.linear2.bias)
+        return y.view(x.shape[0], x.shape[1], self.output_dim)

@@ -415,3 +415,121 @@ def stid_backward(dims: _lib.StidDims, x: torch.Tensor, params, keep: Optional[t
     _lib.check(_lib.load().regt_stid_backward(ctypes.byref(dims), _lib.ptr(x), _ptr_table(params), kp, _lib.ptr(dout), _ptr_table(grads),
                                               _lib.ptr(ws), _lib.ptr(sc), _stream()), "regt_stid_backward")
     return grads
+
+
+# ---- GRU layer and StackedGRU (models/StackedGRU.py) ---------------------------------------------------------------------------------
+
+GRU_HIDDEN = 256             # hidden size the kernels are built for (models/StackedGRU.py:7)
+GRU_MAX_INPUT = 255
+
+
+def gru_limits(input_size: int, hidden: int = GRU_HIDDEN):
+    """ValueError naming the field unless the sizes are inside what regt_gru_* accept (include/regtgcn.h)."""
+    if hidden != GRU_HIDDEN:
+        raise ValueError(f"the GRU kernels run with hidden = {GRU_HIDDEN} only, got hidden={hidden}")
+    if not 1 <= input_size <= GRU_MAX_INPUT:
+        raise ValueError(f"the GRU kernels run with 1 <= input_size <= {GRU_MAX_INPUT}, got input_size={input_size}")
+
+
+def gru_dims(seq_len: int, rows: int, input_size: int, x_strides=None, training: bool = True, hidden: int = GRU_HIDDEN) -> _lib.GruDims:
+    """``x_strides``: element strides of x over (step, row, input); default: a contiguous (seq_len, rows, input_size) tensor."""
+    ss, sr, st = (rows * input_size, input_size, 1) if x_strides is None else x_strides
+    return _lib.GruDims(seq_len, rows, input_size, hidden, int(bool(training)), ss, sr, st)
+
+
+def gru_sizes(dims: _lib.GruDims):
+    """(workspace floats, scratch floats) of regt_gru_forward / _backward."""
+    ws, sc = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(_lib.load().regt_gru_sizes(ctypes.byref(dims), ctypes.byref(ws), ctypes.byref(sc)), "regt_gru_sizes")
+    return ws.value, sc.value
+
+
+def _gru_x(x: torch.Tensor) -> torch.Tensor:
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        raise _lib.RegtError("x must be a float32 CUDA tensor (no CPU path)")
+    if x.dim() != 3:
+        raise ValueError(f"x must be (seq_len, rows, input_size), got {tuple(x.shape)}")
+    if any(s < 0 for s in x.stride()) or x.data_ptr() % 4:
+        x = x.contiguous()
+    return x
+
+
+def gru_check_weights(input_size: int, device, weights, what: str = "GRU"):
+    """RegtError unless the four tensors are contiguous float32 (768, input_size), (768, 256), (768,), (768,) on ``device``: the
+    kernels read them through raw device pointers."""
+    g = 3 * GRU_HIDDEN
+    shapes = [(g, input_size), (g, GRU_HIDDEN), (g,), (g,)]
+    if len(weights) != 4:
+        raise _lib.RegtError(f"{what}: expected weight_ih, weight_hh, bias_ih, bias_hh, got {len(weights)} entries")
+    for i, (t, shape) in enumerate(zip(weights, shapes)):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.RegtError(f"{what}: weight entry {i} is missing")
+        if t.dtype != torch.float32 or t.device != torch.device(device) or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise _lib.RegtError(f"{what}: weight entry {i} must be a contiguous float32 {shape} tensor on {device}, got "
+                                 f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else " (not contiguous)"))
+
+
+def _gru_state(t: Optional[torch.Tensor], rows: int, dev, name: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    t = _f32c(t, name)
+    if t.numel() != rows * GRU_HIDDEN or t.shape[-1] != GRU_HIDDEN or t.device != dev:
+        raise ValueError(f"{name} must hold ({rows}, {GRU_HIDDEN}) values on {dev}, got {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def gru_forward(x: torch.Tensor, weights, h0: Optional[torch.Tensor] = None, want_out: bool = True, want_last: bool = True,
+                save: bool = True):
+    """One GRU layer over x (seq_len, rows, input_size), read in place through its strides.  ``weights``: weight_ih, weight_hh,
+    bias_ih, bias_hh of torch.nn.GRU.  Returns (out (seq_len, rows, 256) | None, h_last (1, rows, 256) | None, dims, workspace);
+    with ``save`` the workspace holds what regt_gru_backward reads."""
+    x = _gru_x(x)
+    n, rows, t = x.shape
+    gru_limits(t)
+    gru_check_weights(t, x.device, weights, "regt_gru_forward")
+    if not (want_out or want_last):
+        raise ValueError("gru_forward: nothing to compute (want_out and want_last are both off)")
+    h0 = _gru_state(h0, rows, x.device, "h0")
+    dims = gru_dims(n, rows, t, x.stride(), save)
+    ws = torch.empty(gru_sizes(dims)[0], dtype=torch.float32, device=x.device)
+    out = torch.empty(n, rows, GRU_HIDDEN, dtype=torch.float32, device=x.device) if want_out else None
+    last = torch.empty(1, rows, GRU_HIDDEN, dtype=torch.float32, device=x.device) if want_last else None
+    _lib.check(_lib.load().regt_gru_forward(ctypes.byref(dims), _lib.ptr(x), *[_lib.ptr(w) for w in weights], _lib.ptr(h0), _lib.ptr(out),
+                                            _lib.ptr(last), _lib.ptr(ws), _stream()), "regt_gru_forward")
+    return out, last, dims, ws
+
+
+def gru_backward(dims: _lib.GruDims, x: torch.Tensor, weights, dout: Optional[torch.Tensor], dh_last: Optional[torch.Tensor],
+                 ws: torch.Tensor, want_dh0: bool = False):
+    """(gradients of weight_ih, weight_hh, bias_ih, bias_hh; dh0 (1, rows, 256) | None) from dL/dout and / or dL/dh_last; ``dims``
+    and ``ws`` are what gru_forward(save=True) returned for the same x."""
+    x = _gru_x(x)
+    if tuple(x.shape) != (dims.seq_len, dims.rows, dims.input_size) or tuple(x.stride()) != (dims.x_stride_seq, dims.x_stride_row,
+                                                                                             dims.x_stride_t):
+        raise ValueError("gru_backward: x must be the tensor gru_forward ran on")
+    gru_check_weights(dims.input_size, x.device, weights, "regt_gru_backward")
+    if dout is not None:
+        dout = _f32c(dout, "dout")
+        if tuple(dout.shape) != (dims.seq_len, dims.rows, GRU_HIDDEN) or dout.device != x.device:
+            raise ValueError(f"dout must be {(dims.seq_len, dims.rows, GRU_HIDDEN)} on {x.device}, got {tuple(dout.shape)} on {dout.device}")
+    dh_last = _gru_state(dh_last, dims.rows, x.device, "dh_last")
+    if dout is None and dh_last is None:
+        raise ValueError("gru_backward: dout and dh_last are both None")
+    ws_n, sc_n = gru_sizes(dims)
+    if ws is None or ws.dtype != torch.float32 or ws.device != x.device or ws.numel() != ws_n or not ws.is_contiguous() or not dims.training:
+        raise ValueError("ws must be the workspace gru_forward(save=True) returned for these dims")
+    sc = torch.empty(sc_n, dtype=torch.float32, device=x.device)
+    grads = [torch.empty_like(w) for w in weights]
+    dh0 = torch.empty(1, dims.rows, GRU_HIDDEN, dtype=torch.float32, device=x.device) if want_dh0 else None
+    _lib.check(_lib.load().regt_gru_backward(ctypes.byref(dims), _lib.ptr(x), _ptr_table(weights), None, _lib.ptr(dout), _lib.ptr(dh_last),
+                                             _ptr_table(grads), _lib.ptr(dh0), _lib.ptr(ws), _lib.ptr(sc), _stream()), "regt_gru_backward")
+    return grads, dh0
+
+
+def relu_backward_(y: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
+    """relu's gradient in place: d = 0 where y <= 0."""
+    y, dd = _f32c(y, "y"), _f32c(d, "d")
+    if dd.data_ptr() != d.data_ptr() or y.numel() != d.numel():
+        raise ValueError("relu_backward_: d must be contiguous and of y's size")
+    _lib.check(_lib.load().regt_relu_backward(_lib.ptr(y), _lib.ptr(d), d.numel(), _stream()), "regt_relu_backward")
+    return d

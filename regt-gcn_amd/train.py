@@ -193,10 +193,11 @@ def split(xs, ys, ratio: float):
 
 # models of run.py:115-136: those built on the TGCN cell (the hot path and the SURVEY 8(f) baselines), SpatialGCN (two ChebConv
 # layers, run.py:117-118), STNorm (gated dilated convolutions with temporal / spatial normalisation, no graph, run.py:135-136) and
-# STID (a per-node MLP on the node's history and a learned node embedding, no graph, run.py:133-134); TemporalGConvLSTM (which
-# run.py:122 cannot construct), StackedGRU and STAEformer are out of scope
+# STID (a per-node MLP on the node's history and a learned node embedding, no graph, run.py:133-134) and StackedGRU (two GRU layers
+# whose sequence runs over the nodes, no graph, run.py:123-124); TemporalGConvLSTM (which run.py:122 cannot construct) and
+# STAEformer are out of scope
 MODELS = ("RegionalTemporalGCN", "RandomTemporalGCN", "TemporalGCN", "ConvStackedTemporalGCN", "GraphSAGETemporalGCN", "GAT", "GATTemporal",
-          "SpatialGCN", "STNorm", "STID")
+          "SpatialGCN", "STNorm", "STID", "StackedGRU")
 
 
 # ---- STNorm and STID (run.py:181-186, 217-222) ------------------------------------------------------------------------------------------
@@ -272,6 +273,62 @@ def evaluate_stid(model, store: "WindowStore", snap_batch: int) -> Tuple[float, 
     return _evaluate_windows(model, store, snap_batch, lambda x, i, b: model(x))
 
 
+# ---- StackedGRU (run.py:174-176, 210-212) --------------------------------------------------------------------------------------------
+# run.py feeds batch.x (N, F = 8, T) as it is: nn.GRU is sequence-first, so the sequence runs over the nodes and the F features are
+# independent batch rows; the loss reads the last row only, mean((out[:, -1, :] - y)**2) with y (N, O).  B snapshots run as one call
+# on (N, F B, T): rows F j .. F j + F - 1 are snapshot j's, its loss reads row F j + F - 1.  One snapshot is a view of the store;
+# B > 1 gathers the rows once.
+
+def gru_batch(store: "WindowStore", i: int, b: int):
+    """Snapshots i .. i+b-1 as StackedGRU's input (N, F b, T) and their targets (b, N, O)."""
+    x = store.X[i:i + b]
+    x = x[0] if b == 1 else x.permute(1, 0, 2, 3).reshape(x.shape[1], b * x.shape[2], x.shape[3])
+    return x, store.Y[i:i + b]
+
+
+def _gru_last_rows(out: torch.Tensor, b: int) -> torch.Tensor:
+    """out (N, F b, O) -> the last feature row of every snapshot, (b, N, O)."""
+    n, fb, o = out.shape
+    return out.view(n, b, fb // b, o)[:, :, -1, :].permute(1, 0, 2)
+
+
+def train_epoch_gru(model, store: "WindowStore", optimizer, snap_batch: int) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """run.py::train() for StackedGRU: gradients accumulate over the epoch, one optimizer step at its end; returns (last snapshot's
+    loss, all per-snapshot losses)."""
+    model.train()
+    losses = []
+    prev = F_.set_grad_accumulation_in_backward(True)
+    try:
+        for i in range(0, len(store), snap_batch):
+            b = min(snap_batch, len(store) - i)
+            x, y = gru_batch(store, i, b)
+            per = ((_gru_last_rows(model(x), b) - y) ** 2).mean(dim=(1, 2))      # run.py:176 per snapshot
+            per.sum().backward()
+            losses.append(per.detach())
+    finally:
+        F_.set_grad_accumulation_in_backward(prev)
+    optimizer.step()
+    optimizer.zero_grad()
+    all_l = torch.cat(losses)
+    return all_l[-1], list(all_l.unbind(0))
+
+
+@torch.no_grad()
+def evaluate_gru(model, store: "WindowStore", snap_batch: int) -> Tuple[float, float]:
+    """run.py::test() for StackedGRU: (rmse, mse) of out[:, -1, :] against y."""
+    model.eval()
+    se = torch.zeros((), dtype=torch.float64, device=store.X.device)
+    count = 0
+    for i in range(0, len(store), snap_batch):
+        b = min(snap_batch, len(store) - i)
+        x, y = gru_batch(store, i, b)
+        e = (_gru_last_rows(model(x), b) - y) ** 2
+        se += e.sum(dtype=torch.float64)
+        count += e.numel()
+    m = float(se) / float(max(count, 1))
+    return m ** 0.5, m
+
+
 def build_parser() -> argparse.ArgumentParser:
     """run.py's flag set (run.py:22-45) -- the reference's own launch lines parse unchanged, e.g. scripts/RegionalTemporalGCN.sh:1 --
     plus this package's data-source flags.  Flags run.py parses and never reads (--momentum, --bs, --checkpoint_path: RMSprop is
@@ -304,6 +361,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dataset_root", help="the reference's dataset/ directory (read through regtgcn_amd.etl)")
     ap.add_argument("--max_steps", type=int, default=None, help="with --dataset_root: use the first MAX_STEPS timesteps")
     ap.add_argument("--out_dir", default="pretrained")
+    ap.add_argument("--loss_digits", default=4, type=int, help="decimals of the printed epoch line (run.py prints 4)")
     ap.add_argument("--fused_step", action="store_true", help="train through functional.FusedTrainStep (no autograd; faster on small graphs)")
     ap.add_argument("--snap_batch", type=int, default=1,
                     help="snapshots per forward / backward (block-diagonal graph of B copies; same accumulated gradients and metrics, "
@@ -382,6 +440,14 @@ def main(argv=None):
         model = rnn.STID(num_nodes=n, input_len=a.num_timesteps_in, output_len=a.num_timesteps_out, if_time_in_day=False,
                          if_day_in_week=False).to(dev)
         graph = None
+    elif a.model == "StackedGRU":                                           # run.py:123-124
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("StackedGRU runs on one GPU (its sequence runs over all nodes: there is nothing to shard)")
+        if a.fused_step:
+            raise SystemExit("--fused_step covers RegionalTemporalGCN (regional decomposition) / TemporalGCN")
+        model = rnn.StackedGRU(in_channels=a.num_timesteps_in, node_features=f, periods=a.num_timesteps_in,
+                               output_dim=a.num_timesteps_out).to(dev)
+        graph = None
     elif a.model == "GraphSAGETemporalGCN":                                 # run.py:127-128
         model = rnn.GraphSAGETemporalGCN(f, n, a.num_timesteps_in, a.num_timesteps_out).to(dev)
         graph = model.prepare_graph(ei, n)
@@ -399,9 +465,10 @@ def main(argv=None):
         os.makedirs("logs", exist_ok=True)
         log = open(os.path.join("logs", datetime.datetime.now().strftime("%y-%m-%d_%H-%M") + ".txt"), "a")
     batched = None
-    if a.model in ("STNorm", "STID"):
+    if a.model in ("STNorm", "STID", "StackedGRU"):
         from_store = (WindowStore(tx, ty), WindowStore(vx, vy))
-        train_fn, eval_fn = (train_epoch_stnorm, evaluate_stnorm) if a.model == "STNorm" else (train_epoch_stid, evaluate_stid)
+        train_fn, eval_fn = {"STNorm": (train_epoch_stnorm, evaluate_stnorm), "STID": (train_epoch_stid, evaluate_stid),
+                             "StackedGRU": (train_epoch_gru, evaluate_gru)}[a.model]
         for epoch in range(a.epochs + 1):
             last, _ = train_fn(model, from_store[0], opt, max(1, a.snap_batch))
             rmse, mse = eval_fn(model, from_store[1], max(1, a.snap_batch))
@@ -436,7 +503,7 @@ def main(argv=None):
 
 
 def _report(a, log, out_dir, model, epoch, last, rmse, mse):
-    line = "Train Loss: {:.4f}, Test RMSE: {:.4f}, MAE: {:.4f}".format(float(last), rmse, mse)   # run.py:236 format
+    line = "Train Loss: {:.{d}f}, Test RMSE: {:.{d}f}, MAE: {:.{d}f}".format(float(last), rmse, mse, d=a.loss_digits)   # run.py:236 format
     print(line)
     if log:
         log.write(line + "\n")
