@@ -109,6 +109,9 @@ int32_t regt_pack_x_bf16(const float* x, void* x_packed, int32_t num_nodes, int3
  *                                              (3 sigmoid, 4 tanh: gate epilogues of the zero-hidden cell)
  * and the matching weight gradient  dW[N,K] = dOut[M,N]^T A[M,K]  (+ optional dbias = column sums).
  * regt_wgrad needs `slab` of regt_wgrad_slab_floats(...) floats.
+ * Operands (pinned by tests/test_gpu_windows.py): any leading dimension >= the logical width and any 4-byte aligned pointer
+ * (16-byte aligned rows only select the vector kernels); bias / dbias may be NULL.  Nothing outside the M x K, N x K and M x N
+ * windows (and the N bias words, the slab) is read into a result or written; what dW, dbias and `slab` hold on entry is irrelevant.
  * ---------------------------------------------------------------------------------------------- */
 int32_t regt_linear(const float* A, int64_t lda, int64_t M, int32_t K, const float* W, int64_t ldw, int32_t N,
                     const float* bias, int32_t act, float slope, float* out, int64_t ldo, regt_stream_t stream);
@@ -302,7 +305,8 @@ int32_t regt_cell0_backward(const regt_dims* dims, const regt_cell0_args* args, 
  * sites).  rowptr/col: the pattern of regt_gcn_csr (in-edges without self loops + one self loop per node).  x, out:
  * (N, T, F) packed rows; stats (N*T, 4) floats are kept for the backward.  regt_gat_backward turns dL/dout (N, T, F) into
  * the score gradients dsd (N*T, 2) = (dL/ds_j, dL/dd_i) per row; du_src = dsd[:, 0]^T x and du_dst = dsd[:, 1]^T x are then
- * ordinary regt_wgrad contractions.  t_rowptr/t_col: the transposed pattern (out-edges of every node). */
+ * ordinary regt_wgrad contractions.  t_rowptr/t_col: the transposed pattern (out-edges of every node).  F % 4 == 0, F <= 256;
+ * x, out, dout, u_src, u_dst and stats 16-byte aligned (rows are read and written in 16-byte pieces). */
 int32_t regt_gat_forward(const int32_t* rowptr, const int32_t* col, const float* x, const float* u_src, const float* u_dst,
                          float slope, int32_t num_nodes, int32_t periods, int32_t num_features, float* out, float* stats,
                          regt_stream_t stream);
