@@ -157,6 +157,7 @@ typedef struct regt_dims {
 #define REGT_DIMS_NO_BF16_ROWS 1u   /* bf16 arithmetic without the bf16-row layout / fused forward (= regt_set_option("xbf", 0)) */
 #define REGT_DIMS_NO_FUSED_BWD 2u   /* bf16 arithmetic with the three data-gradient launches (= regt_set_option("fused_bwd", 0)) */
 #define REGT_DIMS_NO_SIDE_STREAM 4u /* every kernel of this call on `stream` itself (no library side stream) */
+#define REGT_DIMS_FORWARD_ONLY 8u   /* regt_forward / _packed / _packed_bf16 / regt_cell_forward: no backward will follow (see below) */
 
 typedef struct regt_graph {
     const int32_t* rowptr;        /* (2N+1) */
@@ -225,6 +226,29 @@ typedef struct regt_grads {
 /* Bytes of device workspace regt_forward / regt_backward need (same buffer for both: the forward
  * leaves the activations the backward reads). */
 size_t regt_workspace_bytes(const regt_dims* dims, int32_t n_chunks, int32_t overlap);
+
+/* Forward-only calls (evaluation, serving): with REGT_DIMS_FORWARD_ONLY in dims->flags the four forward entry points compute pred
+ * and hidden exactly as without it -- bit for bit, same kernels' arithmetic and summation orders -- but write no array that only the
+ * backward reads, and need only the bytes this function returns (a workspace of regt_workspace_bytes is accepted too).
+ *   bf16 arithmetic on the fused forward (C = 256, F = 32 / 64, node-disjoint regions, merged operator): no (N*T x C) array at all --
+ *     bf16 rows of x, A_hat x, L~ x, the head's (N x H1) activation, the composed weights.
+ *   every other form (fp32, bf16x3, bf16 without bf16 rows, overlapping regions, TemporalGCN, regt_cell_forward): h, [Z | R] (the R
+ *     half is left unwritten) and q = h R: four (N*T x C) element arrays instead of the training layout's nine.
+ * The function reads host-side fields of `graph` only and dereferences no device pointer: overlap, n_chunks, region_sorted,
+ * region_lo / region_hi and whether the m_* and chunk_* pointers are NULL; it picks the form the forward will take from them, from
+ * dims->arith / dims->flags and the process options.  0 = invalid dims or NULL graph (message in regt_last_error).
+ * The form is the one the training forward takes for the same call, so the flag never changes which arithmetic runs.
+ * regt_forward_only_workspace_bytes sizes regt_forward and regt_cell_forward.  The packed entry points are sized by
+ * regt_forward_only_packed_workspace_bytes with the call's own x_rows and row type (x_is_bf16: 0 = regt_forward_packed, 1 =
+ * regt_forward_packed_bf16), because both enter the choice of the form exactly as in the forward (fp32 rows take the fused form up to
+ * x_rows = 2 N, and x_rows * T * F * 2 must stay below 2^32 bytes) and the fused form keeps a bf16 copy of all x_rows fp32 rows in
+ * the workspace.  With x_rows = N it returns what regt_forward_only_workspace_bytes returns.  0 also for x_rows < N, and for bf16
+ * rows where the fused form does not apply (regt_forward_packed_bf16 refuses those).
+ * Refused with an error, before anything is launched: a forward-only call with workspace_bytes below its sizing function's value
+ * (a workspace of exactly that value is accepted); and regt_backward / regt_cell_backward on a workspace whose last forward was
+ * forward-only (it holds nothing they could read). */
+size_t regt_forward_only_workspace_bytes(const regt_dims* dims, const regt_graph* graph);
+size_t regt_forward_only_packed_workspace_bytes(const regt_dims* dims, const regt_graph* graph, int32_t x_rows, int32_t x_is_bf16);
 
 /* x (N,F,T) -> pred (N,O), hidden (N,C).  RegionalTemporalGCN.forward / TemporalGCN.forward. */
 int32_t regt_forward(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const float* x,

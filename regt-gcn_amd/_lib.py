@@ -34,6 +34,7 @@ class Dims(C.Structure):
 ARITH_DEFAULT, ARITH_FP32, ARITH_BF16X3, ARITH_BF16 = 0, 1, 2, 3
 ARITH_NAMES = {None: ARITH_DEFAULT, "default": ARITH_DEFAULT, "fp32": ARITH_FP32, "bf16x3": ARITH_BF16X3, "bf16": ARITH_BF16}
 DIMS_NO_BF16_ROWS, DIMS_NO_FUSED_BWD, DIMS_NO_SIDE_STREAM = 1, 2, 4
+DIMS_FORWARD_ONLY = 8      # forward entry points: no backward follows; workspace of regt_forward_only_workspace_bytes
 
 
 def arith_code(arith) -> int:
@@ -117,6 +118,8 @@ SIGNATURES = {
     "regt_wgrad_slab_floats": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "regt_wgrad": (C.c_int32, [vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, vp, vp, vp]),
     "regt_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.c_int32, C.c_int32]),
+    "regt_forward_only_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.POINTER(Graph)]),
+    "regt_forward_only_packed_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.POINTER(Graph), C.c_int32, C.c_int32]),
     "regt_forward": (C.c_int32, [C.POINTER(Dims), C.POINTER(Graph), C.POINTER(Params), vp, vp, vp, vp, C.c_size_t, vp]),
     "regt_forward_packed": (C.c_int32, [C.POINTER(Dims), C.POINTER(Graph), C.POINTER(Params), vp, C.c_int32, vp, vp, vp,
                                         C.c_size_t, vp]),

@@ -176,7 +176,8 @@ struct CallScope {
 };
 // workspace formats remembered between forward and backward (note_q_format): bit 0 = bf16 intermediates, bit 1 = bf16 rows of
 // x / A_hat x / L~ x, bit 2 = the packed input was the CALLER's bf16 buffer (else the rounded copy lives in the workspace)
-enum : int { FMT_QBF = 1, FMT_XBF = 2, FMT_XCALLER = 4, FMT_TCOLLAPSE = 8 };
+// bit 4 = the forward ran with REGT_DIMS_FORWARD_ONLY: the workspace has the forward-only layout and holds nothing a backward could read
+enum : int { FMT_QBF = 1, FMT_XBF = 2, FMT_XCALLER = 4, FMT_TCOLLAPSE = 8, FMT_FWDONLY = 16 };
 // TemporalGCN / A3T-GCN (regional = 0): the hidden input h = x W0^T + (L~ x) W1^T + b has NO activation (models/TemporalGCN.py:88 --
 // RegT-GCN applies leaky_relu, RegionalTemporalGCN.py:143), so wherever the gates use h LINEARLY it folds into the input:
 //     h [Uz2; Ur2]^T = x ([Uz2; Ur2] W0)^T + (L~ x) ([Uz2; Ur2] W1)^T + ([Uz2; Ur2] b)^T
@@ -363,6 +364,59 @@ Layout make_layout(const regt_dims& d, int n_chunks_tab, int overlap, char* base
     return L;
 }
 
+// Workspace of a forward-only call (REGT_DIMS_FORWARD_ONLY, regt_forward_only_workspace_bytes): what the forward itself reads back,
+// nothing that only the backward reads, none of the backward's temporaries.
+//   fused (the FMT_XBF form: fused_fwd_kernel / fused_fwd_rows_kernel): NO M x C array -- h and q cross LDS / registers, Z stays in
+//     registers.  bf16 rows of A_hat x and L~ x, y1, the composed weights and their fragment-order copies, the tile counter, and
+//     LAST the bf16 copy of the packed input (x_rows rows: a region shard's halo rows lengthen the workspace at its end; not used
+//     when the caller's bf16 buffer is read in place).
+//   every other form: h, [Z | R] with its (M, 2C) leading dimension -- the R half is never written --, q: four M x C element arrays
+//     (the gate kernel reads h, the candidate kernel q, Z and h); no H~.  A width-C array for Z would save one more, at the price of
+//     a second leading dimension in the gate and candidate epilogues' address arithmetic, which the training kernels share.
+Layout make_layout_fwd(const regt_dims& d, int overlap, bool fused, long x_rows, char* base) {
+    Layout L{};
+    const long N = d.N, T = d.T, F = d.F, C = d.C, R = d.R, H1 = d.H1;
+    const long M = N * T;
+    size_t off = 0;
+    auto take_b = [&](size_t nbytes) {
+        size_t o = off;
+        off += (nbytes + 255) & ~size_t(255);
+        return base ? reinterpret_cast<float*>(base + o) : nullptr;
+    };
+    auto take = [&](long nfloats) { return take_b((size_t)nfloats * 4); };
+    if (fused) {
+        L.AX = take_b((size_t)M * F * 2);
+        L.LX = take_b((size_t)M * F * 2);
+    } else {
+        L.Xp = take(M * F);
+        L.AX = take((overlap ? 1 + R : 2) * M * F);
+        L.LX = L.AX ? L.AX + M * F : nullptr;
+        L.h = take(M * C);
+        L.ZR = take(M * 2 * C);
+        L.q = take(M * C);
+    }
+    L.y1 = take(N * H1);
+    L.probs = take(T);
+    L.S = take(C * C);
+    L.A0 = take(C * F);
+    L.Aall = take(R * C * F);
+    L.bprime = take(C);
+    L.Gzr = take(2 * C * F);
+    L.Gh = take(C * F);
+    L.czr = take(2 * C);
+    L.ch = take(C);
+    if (!fused) {
+        L.P0zr = take(2 * C * F);
+        L.P1zr = take(2 * C * F);
+        L.czr2 = take(2 * C);
+    }
+    L.Wb = take((6 * frag_bytes(C, C) + frag_bytes(2 * C, F) + (2 + R) * frag_bytes(C, F)) / 4 + 64);   // (the block layout of wb_ptrs)
+    L.tile_ctr = reinterpret_cast<unsigned*>(take(16));
+    if (fused) L.Xp = take_b((size_t)(x_rows > N ? x_rows : N) * T * F * 2);
+    L.bytes = off;
+    return L;
+}
+
 int check_dims(const regt_dims* d) {
     REGT_CHECK_ARG(d != nullptr, "dims is NULL");
     REGT_CHECK_ARG(d->N > 0 && d->T > 0 && d->F > 0 && d->C > 0 && d->R > 0 && d->O > 0 && d->H1 > 0,
@@ -487,6 +541,7 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
     const float* H = h_ext ? h_ext : L.h;
     const int qbf = bf16_intermediates(d) ? 1 : 0;      // q (and dhp, dzp|drp in the backward) stored as bf16
     const int abf = qbf && !h_ext ? 1 : 0;              // ... and h, [Z|R], H~ (dh in the backward) too: everything M x C
+    const bool save = !(fmt & FMT_FWDONLY);             // forward-only: the kernels that store nothing the backward alone reads
     // The weight compositions do not depend on the snapshot: they run on the side stream next to pack_x + aggregation and are
     // joined in front of their first consumer (0.03-0.10 ms per step off the critical path at every size).
     {
@@ -527,12 +582,12 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
             a.Uzf = wbf.U[0]; a.Urf = wbf.U[1]; a.Uhf = wbf.U[2]; a.Gzrf = wbf.Gzr; a.Ghf = wbf.Gh;
             a.bprime = L.bprime; a.czr = L.czr; a.ch = L.ch; a.probs = L.probs;
             a.node_region = R > 1 ? g.node_region : nullptr;
-            a.h = L.h; a.ZR = L.ZR; a.q = L.q; a.Ht = L.Ht; a.OH = hidden;
+            a.h = L.h; a.ZR = L.ZR; a.q = L.q; a.Ht = L.Ht; a.OH = hidden;      // (forward-only layout: all four NULL, never touched)
             a.M = M; a.T = T; a.slope = d.lrelu_slope; a.act_lrelu = 1; a.tile_ctr = L.tile_ctr;
             PROF("fused_forward", st);
             TRY(launch_zero_f32(hidden, (long)N * C, st));
-            if (fused_rows_form(d, g)) TRY(launch_fused_forward_rows(a, C, F, option(OPT_FUSED_ROWS) == 2 ? 4 : 8, st));
-            else TRY(launch_fused_forward(a, C, F, st));
+            if (fused_rows_form(d, g)) TRY(launch_fused_forward_rows(a, C, F, option(OPT_FUSED_ROWS) == 2 ? 4 : 8, st, save));
+            else TRY(launch_fused_forward(a, C, F, st, save));
         }
         return head_forward(d, p, hidden, L.y1, pred, st);
     }
@@ -620,7 +675,7 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
         EpiGates e{L.ZR, H, L.q, (fmt & FMT_TCOLLAPSE) ? L.czr2 : L.czr, C};
         e.q_bf16 = qbf; e.h_bf16 = abf; e.zr_bf16 = abf;
         PROF("gemm_gates", st);
-        TRY(launch_gemm_gates(S, M, 2 * C, e, st));
+        TRY(launch_gemm_gates(S, M, 2 * C, e, st, save));
     }
     // 4. candidate state, GRU blend and attention-weighted sum over periods -> hidden (N,C)
     {
@@ -639,7 +694,7 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
         a.act_bf16 = abf;
         a.node_sum_rows = abf && fused_rows_form(d, g) ? 16 : 64;
         PROF("gemm_candidate", st);
-        TRY(launch_gemm_candidate(a, st));
+        TRY(launch_gemm_candidate(a, st, save));
     }
     // 5. head: relu -> linear1 -> relu -> linear2
     return head_forward(d, p, hidden, L.y1, pred, st);
@@ -1296,6 +1351,46 @@ size_t regt_workspace_bytes(const regt_dims* dims, int32_t n_chunks, int32_t ove
     return make_layout(*dims, n_chunks, overlap, nullptr).bytes;
 }
 
+// the form a forward takes, decided from host-side fields only (shared by forward_common and the forward-only sizing function)
+static int forward_format(const regt_dims& d, const regt_graph& g, int x_rows, bool packed_fp32, bool xp_is_bf16) {
+    int fmt = bf16_intermediates(d) ? FMT_QBF : 0;
+    if (fmt && xbf_ok(d, g, false, x_rows, packed_fp32)) fmt |= FMT_XBF | (xp_is_bf16 ? FMT_XCALLER : 0);
+    if (!d.regional && !g.overlap && !(fmt & FMT_QBF) && tcollapse_wanted()) fmt |= FMT_TCOLLAPSE;
+    return fmt;
+}
+
+// Form and layout of a forward-only call: the ONE rule of the sizing functions and of forward_common.  `packed`: the caller hands in
+// x_rows packed rows (regt_forward_packed / _packed_bf16).  The form is the training forward's for the same call (xbf_ok with the
+// same x_rows and row type), so the flag never changes which kernels' arithmetic runs.  The fused form converts packed fp32 rows into
+// the workspace, all x_rows of them (make_layout_fwd puts them last); every other case sizes Xp for the N own rows.
+static Layout forward_only_layout(const regt_dims& d, const regt_graph& g, bool packed, int x_rows, bool xp_is_bf16, char* base, int* fmt) {
+    *fmt = forward_format(d, g, packed ? x_rows : d.N, packed && !xp_is_bf16, xp_is_bf16);
+    const bool conv = (*fmt & FMT_XBF) && !(*fmt & FMT_XCALLER) && packed;
+    return make_layout_fwd(d, g.overlap, (*fmt & FMT_XBF) != 0, conv ? x_rows : d.N, base);
+}
+
+size_t regt_forward_only_workspace_bytes(const regt_dims* dims, const regt_graph* graph) {
+    if (check_dims(dims)) return 0;
+    if (!graph) { set_error("regt_forward_only_workspace_bytes: graph is NULL"); return 0; }
+    CallScope call(dims);
+    int fmt;
+    return forward_only_layout(*dims, *graph, false, dims->N, false, nullptr, &fmt).bytes;
+}
+
+size_t regt_forward_only_packed_workspace_bytes(const regt_dims* dims, const regt_graph* graph, int32_t x_rows, int32_t x_is_bf16) {
+    if (check_dims(dims)) return 0;
+    if (!graph) { set_error("regt_forward_only_packed_workspace_bytes: graph is NULL"); return 0; }
+    if (x_rows < dims->N) { set_error("regt_forward_only_packed_workspace_bytes: x_rows=%d < N=%d", x_rows, dims->N); return 0; }
+    CallScope call(dims);
+    int fmt;
+    const size_t bytes = forward_only_layout(*dims, *graph, true, x_rows, x_is_bf16 != 0, nullptr, &fmt).bytes;
+    if (x_is_bf16 && !(fmt & FMT_XBF)) {
+        set_error("regt_forward_only_packed_workspace_bytes: bf16 input rows need bf16 arithmetic and a shape the fused forward covers");
+        return 0;
+    }
+    return bytes;
+}
+
 static int32_t forward_common(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const float* x,
                               const float* xp_ext, int32_t x_rows, float* pred, float* hidden, void* ws, size_t ws_bytes,
                               regt_stream_t st, bool xp_is_bf16 = false) {
@@ -1307,14 +1402,20 @@ static int32_t forward_common(const regt_dims* dims, const regt_graph* graph, co
     REGT_CHECK_ARG(al16(x) && al16(xp_ext) && al16(hidden) && al16(ws),
                    "regt_forward: x, hidden and workspace must be 16-byte aligned");
     REGT_CHECK_ARG(!xp_ext || x_rows >= dims->N, "regt_forward_packed: x_rows=%d < N=%d", x_rows, dims->N);
-    Layout L = make_layout(*dims, graph->n_chunks, graph->overlap, (char*)ws);
-    REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_forward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
     hipStream_t hs = (hipStream_t)st;
-    int fmt = bf16_intermediates(*dims) ? FMT_QBF : 0;
-    if (fmt && xbf_ok(*dims, *graph, false, xp_ext ? x_rows : dims->N, xp_ext && !xp_is_bf16)) fmt |= FMT_XBF | (xp_is_bf16 ? FMT_XCALLER : 0);
-    if (!dims->regional && !graph->overlap && !(fmt & FMT_QBF) && tcollapse_wanted()) fmt |= FMT_TCOLLAPSE;
+    int fmt = forward_format(*dims, *graph, xp_ext ? x_rows : dims->N, xp_ext && !xp_is_bf16, xp_is_bf16);
     REGT_CHECK_ARG(!xp_is_bf16 || (fmt & FMT_XBF), "regt_forward_packed_bf16: bf16 input rows need REGT_GEMM_MODE=bf16 and a shape the fused "
                    "forward covers (C = 256, F = 64, node-disjoint regions, merged operator)");
+    Layout L;
+    if (dims->flags & REGT_DIMS_FORWARD_ONLY) {
+        L = forward_only_layout(*dims, *graph, xp_ext != nullptr, x_rows, xp_is_bf16, (char*)ws, &fmt);
+        REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_forward (REGT_DIMS_FORWARD_ONLY): workspace %zu < required %zu bytes (%s)", ws_bytes, L.bytes,
+                       xp_ext ? "regt_forward_only_packed_workspace_bytes" : "regt_forward_only_workspace_bytes");
+        fmt |= FMT_FWDONLY;
+    } else {
+        L = make_layout(*dims, graph->n_chunks, graph->overlap, (char*)ws);
+        REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_forward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
+    }
     note_q_format(ws, fmt);
     if (!graphs_wanted((long)dims->N * dims->T))
         return forward_impl(*dims, *graph, *params, x, xp_ext, x_rows, pred, hidden, L, hs, false, nullptr, fmt);
@@ -1380,10 +1481,12 @@ int32_t regt_backward(const regt_dims* dims, const regt_graph* graph, const regt
         if (dims->regional) ok = ok && g.region_w && g.region_b;
         REGT_CHECK_ARG(ok, "regt_backward: a required gradient pointer is NULL (only `attention` may be NULL)");
     }
+    const int qbf = q_format(ws);
+    REGT_CHECK_ARG(!(qbf & FMT_FWDONLY), "regt_backward: the last forward on this workspace ran with REGT_DIMS_FORWARD_ONLY and kept no activations; "
+                   "run the forward without that flag on a workspace of regt_workspace_bytes");
     Layout L = make_layout(*dims, graph->n_chunks, graph->overlap, (char*)ws);
     REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_backward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
     hipStream_t hs = (hipStream_t)st;
-    const int qbf = q_format(ws);
     REGT_CHECK_ARG((qbf & FMT_QBF) == (bf16_intermediates(*dims) ? 1 : 0),
                    "regt_backward: the GEMM arithmetic changed since the forward on this workspace (another regt_dims.arith, or regt_set_gemm_mode between forward and backward)");
     REGT_CHECK_ARG(!(qbf & FMT_XCALLER) || x_packed, "regt_backward: the forward ran on the caller's bf16 packed input; pass the same buffer as x_packed");
@@ -1419,10 +1522,19 @@ int32_t regt_cell_forward(const regt_dims* dims, const regt_graph* graph, const 
     TRY(check_ptrs(params, *dims, true));
     REGT_CHECK_ARG(x && h_in && pred && hidden && ws, "regt_cell_forward: NULL pointer");
     REGT_CHECK_ARG(al16(x) && al16(h_in) && al16(hidden) && al16(ws), "regt_cell_forward: x, h_in, hidden and workspace must be 16-byte aligned");
-    Layout L = make_layout(*dims, 0, 0, (char*)ws);
-    REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_cell_forward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
-    note_q_format(ws, bf16_intermediates(*dims) ? 1 : 0);
-    return forward_impl(*dims, *graph, *params, x, nullptr, 0, pred, hidden, L, (hipStream_t)st, false, h_in);
+    int fmt = bf16_intermediates(*dims) ? FMT_QBF : 0;
+    Layout L;
+    if (dims->flags & REGT_DIMS_FORWARD_ONLY) {
+        L = make_layout_fwd(*dims, 0, false, dims->N, (char*)ws);
+        REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_cell_forward (REGT_DIMS_FORWARD_ONLY): workspace %zu < required %zu bytes (regt_forward_only_workspace_bytes)",
+                       ws_bytes, L.bytes);
+        fmt |= FMT_FWDONLY;
+    } else {
+        L = make_layout(*dims, 0, 0, (char*)ws);
+        REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_cell_forward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
+    }
+    note_q_format(ws, fmt);
+    return forward_impl(*dims, *graph, *params, x, nullptr, 0, pred, hidden, L, (hipStream_t)st, false, h_in, fmt);
 }
 
 int32_t regt_cell_backward(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const regt_grads* grads,
@@ -1441,9 +1553,11 @@ int32_t regt_cell_backward(const regt_dims* dims, const regt_graph* graph, const
         for (int k = 0; k < 3; ++k) ok = ok && g.conv_lin_w[k] && g.conv_bias[k] && g.gate_w[k] && g.gate_b[k];
         REGT_CHECK_ARG(ok, "regt_cell_backward: a required gradient pointer is NULL (only `attention` may be NULL)");
     }
+    const int qbf = q_format(ws);
+    REGT_CHECK_ARG(!(qbf & FMT_FWDONLY), "regt_cell_backward: the last forward on this workspace ran with REGT_DIMS_FORWARD_ONLY and kept no activations; "
+                   "run the forward without that flag on a workspace of regt_workspace_bytes");
     Layout L = make_layout(*dims, 0, 0, (char*)ws);
     REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_cell_backward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
-    const int qbf = q_format(ws);
     REGT_CHECK_ARG((qbf & FMT_QBF) == (bf16_intermediates(*dims) ? 1 : 0),
                    "regt_cell_backward: the GEMM arithmetic changed since the forward on this workspace");
     return backward_impl(*dims, *graph, *params, *grads, dpred, dhidden, hidden, nullptr, L, (hipStream_t)st, qbf, h_in, dh_in);

@@ -64,7 +64,10 @@ struct FusedFwdLds {
 #else
 #define FT_STORE16(...) __builtin_amdgcn_raw_buffer_store_b128(__VA_ARGS__)
 #endif
-template <int C, int F>
+// SAVE = false (forward-only calls, REGT_DIMS_FORWARD_ONLY): none of the h / [Z|R] / q / H~ stores is issued and none of their
+// descriptors is built -- nothing of them is read back here (h and q cross LDS, Z stays in registers), only the backward pass reads
+// them.  Every rounding (the bf16 packing of h, q, Z feeds the next stage) and every sum stays where it is.
+template <int C, int F, bool SAVE>
 __global__ __launch_bounds__(256, 2) void fused_fwd_kernel(FusedFwdArgs a) {
     static_assert(C % 128 == 0 && F % 16 == 0, "tile shapes");
     using L = FusedFwdLds<C, F>;
@@ -85,9 +88,9 @@ __global__ __launch_bounds__(256, 2) void fused_fwd_kernel(FusedFwdArgs a) {
 #else
 #define FT_FINE(i) do {} while (0)
 #endif
-    // (timing-only switches, REGT_FUSED_DBG: bit 0 = zero-record store descriptors: every activation store is dropped by the range
-    // check; bit 1 = zero-record weight descriptors: fragment loads return 0 without traffic -- cdna_hip_programming.md section 7)
-    const int st_on = (a.dbg & 1) ? 0 : 1, w_on = (a.dbg & 2) ? 0 : 1;
+    // (timing-only switch, REGT_FUSED_DBG: bit 1 = zero-record weight descriptors: fragment loads return 0 without traffic --
+    // cdna_hip_programming.md section 7)
+    const int w_on = (a.dbg & 2) ? 0 : 1;
     // A-fragment offsets of the K = F operands: lane (lr, lh) holds k = 8 lh .. 8 lh + 7 of row 32 mi + lr of a 16-k block
     const int afo = lr * F * 2 + lh * 16;
 
@@ -193,10 +196,13 @@ __global__ __launch_bounds__(256, 2) void fused_fwd_kernel(FusedFwdArgs a) {
     // ---- descriptors: the tile's rows of every activation array (rows past the end are out of range: loads return 0, stores are dropped)
     const __amdgpu_buffer_rsrc_t sLX = f_rsrc(reinterpret_cast<const char*>(a.LX) + m0 * F * 2, (long)nvalid * F * 2);
     const __amdgpu_buffer_rsrc_t sAX = f_rsrc(reinterpret_cast<const char*>(a.AX) + m0 * F * 2, (long)nvalid * F * 2);
-    const __amdgpu_buffer_rsrc_t sh = f_rsrc(reinterpret_cast<char*>(a.h) + m0 * C * 2, (long)nvalid * C * 2 * st_on);
-    const __amdgpu_buffer_rsrc_t sq = f_rsrc(reinterpret_cast<char*>(a.q) + m0 * C * 2, (long)nvalid * C * 2 * st_on);
-    const __amdgpu_buffer_rsrc_t sHt = f_rsrc(reinterpret_cast<char*>(a.Ht) + m0 * C * 2, (long)nvalid * C * 2 * st_on);
-    const __amdgpu_buffer_rsrc_t sZR = f_rsrc(reinterpret_cast<char*>(a.ZR) + m0 * C * 4, (long)nvalid * C * 4 * st_on);
+    __amdgpu_buffer_rsrc_t sh, sq, sHt, sZR;
+    if constexpr (SAVE) {
+        sh = f_rsrc(reinterpret_cast<char*>(a.h) + m0 * C * 2, (long)nvalid * C * 2);
+        sq = f_rsrc(reinterpret_cast<char*>(a.q) + m0 * C * 2, (long)nvalid * C * 2);
+        sHt = f_rsrc(reinterpret_cast<char*>(a.Ht) + m0 * C * 2, (long)nvalid * C * 2);
+        sZR = f_rsrc(reinterpret_cast<char*>(a.ZR) + m0 * C * 4, (long)nvalid * C * 4);
+    }
     bf16x8 axf[2][KBF], b0[2][KBF], b1[2][KBF];                  // A_hat x fragments; A0 ([0]) / A_region ([1]) fragments of column tile 0 / 1
     const int rgt = rg0, rga = rg_a, rgb = rg_b;                 // (this tile's; the loop-carried set is refilled further down)
     {
@@ -355,7 +361,7 @@ __global__ __launch_bounds__(256, 2) void fused_fwd_kernel(FusedFwdArgs a) {
             for (int i = 0; i < 8; ++i) { const float s = v.v[i] + b.v[i]; o.v[i] = s > 0.f ? s : s * ns; }
             const u32x4_t pk = f_pack8(o);
             const int row = 16 * rnd + er, c = 128 * j + ec;
-            FT_STORE16(pk, sh, (row * C + c) * 2, 0, 0);
+            if constexpr (SAVE) FT_STORE16(pk, sh, (row * C + c) * 2, 0, 0);
             *reinterpret_cast<u32x4_t*>(Hp + plane_off(row, c)) = pk;
         }
         FT_FINE(9 + 2 * j);
@@ -388,9 +394,9 @@ __global__ __launch_bounds__(256, 2) void fused_fwd_kernel(FusedFwdArgs a) {
             V8 qv;
 #pragma unroll
             for (int i = 0; i < 8; ++i) qv.v[i] = hv.v[i] * g.v[i];
-            FT_STORE16(f_pack8(g), sZR, (row * 2 * C + C + c) * 2, 0, 0);
+            if constexpr (SAVE) FT_STORE16(f_pack8(g), sZR, (row * 2 * C + C + c) * 2, 0, 0);
             const u32x4_t pq = f_pack8(qv);
-            FT_STORE16(pq, sq, (row * C + c) * 2, 0, 0);
+            if constexpr (SAVE) FT_STORE16(pq, sq, (row * C + c) * 2, 0, 0);
             *reinterpret_cast<u32x4_t*>(Qp + plane_off(row, c)) = pq;
         }
         FT_FINE(17 + 5 * j);
@@ -415,7 +421,7 @@ __global__ __launch_bounds__(256, 2) void fused_fwd_kernel(FusedFwdArgs a) {
                 const V8 v = img8();
                 const V8 g = f_sigmoid8(v, b);
                 zk[rnd] = f_pack8(g);
-                FT_STORE16(zk[rnd], sZR, ((16 * rnd + er) * 2 * C + 128 * j + ec) * 2, 0, 0);
+                if constexpr (SAVE) FT_STORE16(zk[rnd], sZR, ((16 * rnd + er) * 2 * C + 128 * j + ec) * 2, 0, 0);
             }
         }
         FT_MARK(4 + 2 * j);
@@ -448,7 +454,7 @@ __global__ __launch_bounds__(256, 2) void fused_fwd_kernel(FusedFwdArgs a) {
             V8 bl;
 #pragma unroll
             for (int i = 0; i < 8; ++i) bl.v[i] = __fmul_rn(pt, gru_blend(Zv.v[i], hv.v[i], ht.v[i]));
-            FT_STORE16(f_pack8(ht), sHt, (row * C + c) * 2, 0, 0);
+            if constexpr (SAVE) FT_STORE16(f_pack8(ht), sHt, (row * C + c) * 2, 0, 0);
             *reinterpret_cast<float4*>(imgw + e_lo) = make_float4(bl.v[0], bl.v[1], bl.v[2], bl.v[3]);
             *reinterpret_cast<float4*>(imgw + e_hi) = make_float4(bl.v[4], bl.v[5], bl.v[6], bl.v[7]);
 #if defined(REGT_FUSED_ABL) && (REGT_FUSED_ABL & 8)      // timing-only developer build: no per-node sums
@@ -877,10 +883,11 @@ long fused_trace_fetch(long* out, long capacity) {
     if (hipMemcpy(out, g_fused_trace, n * sizeof(long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return n;
 }
-int launch_fused_forward(const FusedFwdArgs& a_, int C, int F, hipStream_t st) {
+int launch_fused_forward(const FusedFwdArgs& a_, int C, int F, hipStream_t st, bool save) {
     REGT_CHECK_ARG(a_.M > 0 && a_.T > 0, "fused forward: empty problem");
+    REGT_CHECK_ARG(!save || (a_.h && a_.ZR && a_.q && a_.Ht), "fused forward: the training form stores h, [Z|R], q and H~ (NULL array)");
     FusedFwdArgs a = a_;
-    a.dbg = 0;                  // (timing-only descriptor switches of the kernel: developer builds set them, see tools/fused_ablation.sh)
+    a.dbg = 0;                  // (timing-only descriptor switch of the kernel: developer builds set it, see tools/fused_ablation.sh)
     REGT_CHECK_ARG(a.M % a.T == 0, "fused forward: M = %ld rows are no whole number of T = %d periods", a.M, a.T);
     a.nodes = a.M / a.T;
     a.pmask = 0;
@@ -892,16 +899,23 @@ int launch_fused_forward(const FusedFwdArgs& a_, int C, int F, hipStream_t st) {
     using L = FusedFwdLds<256, 64>;              // (the LDS footprint does not depend on F)
     static bool attr_done = false;
     if (!attr_done) {
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<256, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<256, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
+        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<256, 64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
+        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<256, 32, true>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
+        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<256, 64, false>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
+        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<256, 32, false>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
         attr_done = true;
     }
     // persistent: two workgroups per CU (what LDS and registers admit), each walks its tiles with a stride of the grid
     const long slots = 2L * fused_cus();
     const unsigned grid = (unsigned)(tiles < slots ? tiles : slots);
     if (a.tile_ctr) REGT_CHECK_HIP(hipMemsetAsync(a.tile_ctr, 0, sizeof(unsigned), st));
-    if (F == 64) hipLaunchKernelGGL((fused_fwd_kernel<256, 64>), dim3(grid), dim3(256), L::BYTES, st, a);
-    else hipLaunchKernelGGL((fused_fwd_kernel<256, 32>), dim3(grid), dim3(256), L::BYTES, st, a);
+    if (save) {
+        if (F == 64) hipLaunchKernelGGL((fused_fwd_kernel<256, 64, true>), dim3(grid), dim3(256), L::BYTES, st, a);
+        else hipLaunchKernelGGL((fused_fwd_kernel<256, 32, true>), dim3(grid), dim3(256), L::BYTES, st, a);
+    } else {
+        if (F == 64) hipLaunchKernelGGL((fused_fwd_kernel<256, 64, false>), dim3(grid), dim3(256), L::BYTES, st, a);
+        else hipLaunchKernelGGL((fused_fwd_kernel<256, 32, false>), dim3(grid), dim3(256), L::BYTES, st, a);
+    }
     REGT_CHECK_LAUNCH();
     return REGT_OK;
 }

@@ -70,7 +70,13 @@ __device__ __forceinline__ constexpr int fr_par(int r) { return ((r >> 1) & 3) |
 // (region ids sorted by node: a tile's regions are a range)
 struct FrTileInfo { int rg_first, nreg; };
 
-template <int F, int NW>
+// SAVE = false (forward-only calls, REGT_DIMS_FORWARD_ONLY): none of the h / [Z|R] / q / H~ stores is issued, none of their descriptors
+// built; the hand-counted waits of the ring count those stores, so vm_epi() below drops them with the stores.  In place of a store
+// its packed operand is pinned where the store stood (an empty asm statement: no instruction): with the operands simply dead hipcc
+// rescheduled the epilogue rounds into 58-76 spilled vector registers (scratch, whose reloads drain the ring); pinned, the
+// allocation is the training kernel's (203-215 registers, no scratch) at the price of eight conversions per round nobody reads.
+#define FR_STORE16(v, ...) do { if constexpr (SAVE) __builtin_amdgcn_raw_buffer_store_b128(v, __VA_ARGS__); else asm volatile("" :: "v"(v)); } while (0)
+template <int F, int NW, bool SAVE>
 __global__ __launch_bounds__(64 * NW, 2) void fused_fwd_rows_kernel(FusedFwdArgs a) {
     constexpr int C = FR_C, KF = F / 32;                         // k blocks (32 k) of a K = F operand
     static_assert(F == 32 || F == 64, "row widths");
@@ -166,6 +172,7 @@ __global__ __launch_bounds__(64 * NW, 2) void fused_fwd_rows_kernel(FusedFwdArgs
     // after the last slice also the next tile's row loads
     auto vm_epi = [&](int t) {
         const int u0 = 2 * KF, g0 = 4 * KF, gl = 8 + KF;
+        if (!SAVE) return t == g0 + 6 * gl - 1 ? 3 * KF + 1 : 0;                               // no activation stores: only the next tile's rows
         if (t == u0 - 1 || t == 2 * u0 - 1) return 4;                                         // embedding: h
         if (t == g0 + gl - 1 || t == g0 + 2 * gl - 1) return 8;                               // R: R and q
         if (t == g0 + 3 * gl - 1 || t == g0 + 5 * gl - 1) return 4;                           // Z
@@ -363,10 +370,13 @@ __global__ __launch_bounds__(64 * NW, 2) void fused_fwd_rows_kernel(FusedFwdArgs
         const unsigned emask = nv > 0 ? ((smask >> 1) | (1u << (nv - 1))) & vmask : 0u;
         const unsigned amask = (t0 != 0 ? emask & (0u - emask) : 0u) | ((nv > 0 && ((unsigned)(t0 + nv) % uT) != 0) ? 1u << (nv - 1) : 0u);
         FT_MARK(0);
-        const __amdgpu_buffer_rsrc_t sh = f_rsrc(reinterpret_cast<char*>(a.h) + m0 * C * 2, (long)nv * C * 2);
-        const __amdgpu_buffer_rsrc_t sq = f_rsrc(reinterpret_cast<char*>(a.q) + m0 * C * 2, (long)nv * C * 2);
-        const __amdgpu_buffer_rsrc_t sHt = f_rsrc(reinterpret_cast<char*>(a.Ht) + m0 * C * 2, (long)nv * C * 2);
-        const __amdgpu_buffer_rsrc_t sZR = f_rsrc(reinterpret_cast<char*>(a.ZR) + m0 * C * 4, (long)nv * C * 4);
+        __amdgpu_buffer_rsrc_t sh, sq, sHt, sZR;
+        if constexpr (SAVE) {
+            sh = f_rsrc(reinterpret_cast<char*>(a.h) + m0 * C * 2, (long)nv * C * 2);
+            sq = f_rsrc(reinterpret_cast<char*>(a.q) + m0 * C * 2, (long)nv * C * 2);
+            sHt = f_rsrc(reinterpret_cast<char*>(a.Ht) + m0 * C * 2, (long)nv * C * 2);
+            sZR = f_rsrc(reinterpret_cast<char*>(a.ZR) + m0 * C * 4, (long)nv * C * 4);
+        }
         const int rgl = rg_row; const float pt = pt_row;
         bf16x8 hA[8], qA[8], axA[KF];
 #pragma unroll
@@ -414,7 +424,7 @@ __global__ __launch_bounds__(64 * NW, 2) void fused_fwd_rows_kernel(FusedFwdArgs
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { const float s = vv.v[i] + b.v[i]; o.v[i] = s > 0.f ? s : s * ns; }
                 const u32x4_t pk = f_pack8(o);
-                __builtin_amdgcn_raw_buffer_store_b128(pk, sh, eg.ro + (128 * j + 32 * q) * 2, 0, 0);
+                FR_STORE16(pk, sh, eg.ro + (128 * j + 32 * q) * 2, 0, 0);
                 hA[4 * j + q] = __builtin_bit_cast(bf16x8, pk);
             }
             FT_MARK(2 + 2 * j);
@@ -447,9 +457,9 @@ __global__ __launch_bounds__(64 * NW, 2) void fused_fwd_rows_kernel(FusedFwdArgs
                 V8 qv;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) qv.v[i] = hv.v[i] * gt.v[i];
-                __builtin_amdgcn_raw_buffer_store_b128(f_pack8(gt), sZR, eg.rzo + (C + 128 * j + 32 * q) * 2, 0, 0);
+                FR_STORE16(f_pack8(gt), sZR, eg.rzo + (C + 128 * j + 32 * q) * 2, 0, 0);
                 const u32x4_t pq = f_pack8(qv);
-                __builtin_amdgcn_raw_buffer_store_b128(pq, sq, eg.ro + (128 * j + 32 * q) * 2, 0, 0);
+                FR_STORE16(pq, sq, eg.ro + (128 * j + 32 * q) * 2, 0, 0);
                 qA[4 * j + q] = __builtin_bit_cast(bf16x8, pq);
             }
             FT_MARK(6 + 2 * j);
@@ -477,7 +487,7 @@ __global__ __launch_bounds__(64 * NW, 2) void fused_fwd_rows_kernel(FusedFwdArgs
                     const V8 vv = img8(eg);
                     const V8 b = bias8(C + 128 * j + 32 * q + 8 * g);
                     zk[q] = f_pack8(f_sigmoid8(vv, b));
-                    __builtin_amdgcn_raw_buffer_store_b128(zk[q], sZR, eg.rzo + (128 * j + 32 * q) * 2, 0, 0);
+                    FR_STORE16(zk[q], sZR, eg.rzo + (128 * j + 32 * q) * 2, 0, 0);
                 }
             }
             FT_MARK(10 + 4 * j);
@@ -507,7 +517,7 @@ __global__ __launch_bounds__(64 * NW, 2) void fused_fwd_rows_kernel(FusedFwdArgs
                 V8 bl;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) bl.v[i] = __fmul_rn(pt, gru_blend(Zv.v[i], hv.v[i], ht.v[i]));
-                __builtin_amdgcn_raw_buffer_store_b128(f_pack8(ht), sHt, eg.ro + (128 * j + 32 * q) * 2, 0, 0);
+                FR_STORE16(f_pack8(ht), sHt, eg.ro + (128 * j + 32 * q) * 2, 0, 0);
                 *reinterpret_cast<float4*>(imgw + eg.e_lo) = make_float4(bl.v[0], bl.v[1], bl.v[2], bl.v[3]);
                 *reinterpret_cast<float4*>(imgw + eg.e_hi) = make_float4(bl.v[4], bl.v[5], bl.v[6], bl.v[7]);
                 // Per-node sums over the wave's 16 rows, in row order (see fused.hip: one running sum per lane = column lr of the
@@ -553,8 +563,9 @@ int fused_cus();
 
 bool fused_forward_rows_ok(int C, int F, int T) { return C == FR_C && (F == 64 || F == 32) && T <= 16; }
 
-int launch_fused_forward_rows(const FusedFwdArgs& a_, int C, int F, int waves, hipStream_t st) {
+int launch_fused_forward_rows(const FusedFwdArgs& a_, int C, int F, int waves, hipStream_t st, bool save) {
     REGT_CHECK_ARG(a_.M > 0 && a_.T > 0, "fused forward: empty problem");
+    REGT_CHECK_ARG(!save || (a_.h && a_.ZR && a_.q && a_.Ht), "fused forward (row form): the training form stores h, [Z|R], q and H~ (NULL array)");
     REGT_CHECK_ARG(fused_forward_rows_ok(C, F, a_.T), "fused forward (row form): built for C = 256, F = 32 or 64, T <= 16 (got C = %d, F = %d, T = %d)", C, F, a_.T);
     FusedFwdArgs a = a_;
     REGT_CHECK_ARG(a.M % a.T == 0, "fused forward: M = %ld rows are no whole number of T = %d periods", a.M, a.T);
@@ -579,23 +590,25 @@ int launch_fused_forward_rows(const FusedFwdArgs& a_, int C, int F, int waves, h
     }
     static bool attr_done = false;
     if (!attr_done) {
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_rows_kernel<64, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, FusedRowsLds<8>::BYTES));
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_rows_kernel<32, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, FusedRowsLds<8>::BYTES));
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_rows_kernel<64, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, FusedRowsLds<4>::BYTES));
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_rows_kernel<32, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, FusedRowsLds<4>::BYTES));
+#define ATTR_(F_, NW_, S_) REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_rows_kernel<F_, NW_, S_>), hipFuncAttributeMaxDynamicSharedMemorySize, FusedRowsLds<NW_>::BYTES))
+        ATTR_(64, 8, true); ATTR_(32, 8, true); ATTR_(64, 4, true); ATTR_(32, 4, true);
+        ATTR_(64, 8, false); ATTR_(32, 8, false); ATTR_(64, 4, false); ATTR_(32, 4, false);
+#undef ATTR_
         attr_done = true;
     }
     // persistent: 8 waves per CU (one workgroup of eight or two of four)
     const long slots = (long)fused_cus() * (8 / nw);
     const unsigned grid = (unsigned)(tiles < slots ? tiles : slots);
     if (a.tile_ctr) REGT_CHECK_HIP(hipMemsetAsync(a.tile_ctr, 0, sizeof(unsigned), st));
-    if (nw == 8) {
-        if (F == 64) hipLaunchKernelGGL((fused_fwd_rows_kernel<64, 8>), dim3(grid), dim3(512), FusedRowsLds<8>::BYTES, st, a);
-        else hipLaunchKernelGGL((fused_fwd_rows_kernel<32, 8>), dim3(grid), dim3(512), FusedRowsLds<8>::BYTES, st, a);
+#define LAUNCH_(F_, NW_, S_) hipLaunchKernelGGL((fused_fwd_rows_kernel<F_, NW_, S_>), dim3(grid), dim3(64 * NW_), FusedRowsLds<NW_>::BYTES, st, a)
+    if (save) {
+        if (nw == 8) { if (F == 64) LAUNCH_(64, 8, true); else LAUNCH_(32, 8, true); }
+        else { if (F == 64) LAUNCH_(64, 4, true); else LAUNCH_(32, 4, true); }
     } else {
-        if (F == 64) hipLaunchKernelGGL((fused_fwd_rows_kernel<64, 4>), dim3(grid), dim3(256), FusedRowsLds<4>::BYTES, st, a);
-        else hipLaunchKernelGGL((fused_fwd_rows_kernel<32, 4>), dim3(grid), dim3(256), FusedRowsLds<4>::BYTES, st, a);
+        if (nw == 8) { if (F == 64) LAUNCH_(64, 8, false); else LAUNCH_(32, 8, false); }
+        else { if (F == 64) LAUNCH_(64, 4, false); else LAUNCH_(32, 4, false); }
     }
+#undef LAUNCH_
     REGT_CHECK_LAUNCH();
     return REGT_OK;
 }

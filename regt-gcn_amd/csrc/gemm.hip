@@ -115,11 +115,14 @@ struct EpiBiasActF {
 #undef F_
     }
 };
-struct EpiGatesF {
+// SAVE_R = false (forward-only calls, REGT_DIMS_FORWARD_ONLY): R is formed and multiplied into q exactly as before but not stored --
+// only the backward pass reads it; Z and q are (the candidate kernel reads both).  Same arithmetic, one store per r element less.
+template <bool SAVE_R>
+struct EpiGatesT {
     EpiGates e;
     __device__ __forceinline__ void operator()(long m, int c, float v) const {
         float g = fast_sigmoid(v + e.bias[c]);
-        e.ZR[m * (2L * e.C) + c] = g;
+        if (SAVE_R || c < e.C) e.ZR[m * (2L * e.C) + c] = g;
         if (c >= e.C) e.q[m * e.C + c - e.C] = e.h[m * e.C + c - e.C] * g;      // fp32 storage only (vector path handles bf16)
     }
     static constexpr int ROUND_ROWS = 16;
@@ -134,7 +137,7 @@ struct EpiGatesF {
 #define F_(k) fast_sigmoid(v.k + a.b.k)
         const float4 g = REGT_V4(F_);
 #undef F_
-        st4(e.ZR + m * (2L * e.C) + c, g);
+        if (SAVE_R || c < e.C) st4(e.ZR + m * (2L * e.C) + c, g);
         if (c >= e.C) {
             const float4 qv = make_float4(a.h.x * g.x, a.h.y * g.y, a.h.z * g.z, a.h.w * g.w);
             if (e.q_bf16) st4_bf16(e.q, m * e.C + c - e.C, qv);
@@ -155,9 +158,11 @@ struct EpiGatesF {
     template <int V> __device__ __forceinline__ Col vcol(int c) const { return Col{ld4(e.bias + c)}; }
     template <int V> __device__ __forceinline__ Tile vtile(const EpiGeom& g) const {
         Tile t;
-        t.zr = buf_srd(e.ZR + g.m0 * (2L * e.C) + g.n0);
-        t.vzr = (g.rr * 2 * e.C + g.c) * 4;
-        t.szr = g.step * 2 * e.C * 4;
+        if (SAVE_R || !(V & 1)) {
+            t.zr = buf_srd(e.ZR + g.m0 * (2L * e.C) + g.n0);
+            t.vzr = (g.rr * 2 * e.C + g.c) * 4;
+            t.szr = g.step * 2 * e.C * 4;
+        }
         if (V & 1) {
             const long o = g.m0 * e.C + g.n0 - e.C;
             t.h = buf_srd(e.h + o);
@@ -178,7 +183,7 @@ struct EpiGatesF {
 #define F_(k) fast_sigmoid(v.k + col.b.k)
         const float4 g = REGT_V4(F_);
 #undef F_
-        buf_st4(t.zr, t.vzr + i * t.szr, 0, g);
+        if (SAVE_R || !(V & 1)) buf_st4(t.zr, t.vzr + i * t.szr, 0, g);
         if (V & 1) {
             const float4 qv = make_float4(a.h.x * g.x, a.h.y * g.y, a.h.z * g.z, a.h.w * g.w);
             if (V & 2) buf_st4_bf16(t.q, t.vq + i * t.sq, 0, qv);
@@ -186,6 +191,8 @@ struct EpiGatesF {
         }
     }
 };
+struct EpiGatesF : EpiGatesT<true> {};
+struct EpiGatesFwdF : EpiGatesT<false> {};
 // (drp / dh through the fixed instruction sequences cb_drp / cb_dh of kernels.h since round 4: left to -ffp-contract, the two-launch
 // kernel and the generated-operand kernel of the bf16x3 arithmetic contracted `v R + p d Z` differently -- last-bit differences between
 // two paths that tests/test_gpu_ops.py compares bit for bit)
@@ -572,7 +579,8 @@ struct EpiBiasAct8F {
 #undef F_
     }
 };
-struct EpiGates8F {
+template <bool SAVE_R>     // (as EpiGatesT)
+struct EpiGates8T {
     typedef F8 Vec;
     EpiGates e;
     static constexpr int ROUND_ROWS = 4;
@@ -588,7 +596,7 @@ struct EpiGates8F {
 #define F_(k) fast_sigmoid(v.k + ca.b.k)
         const F8 g = REGT_F8(F_);
 #undef F_
-        st8(e.ZR, m * (2L * e.C) + c, g, e.zr_bf16);
+        if (SAVE_R || c < e.C) st8(e.ZR, m * (2L * e.C) + c, g, e.zr_bf16);
         if (c >= e.C) {
 #define F_(k) (a.h.k * g.k)
             st8(e.q, m * e.C + c - e.C, REGT_F8(F_), e.q_bf16);
@@ -605,9 +613,11 @@ struct EpiGates8F {
     template <int V> __device__ __forceinline__ Col vcol(int c) const { return col(c); }
     template <int V> __device__ __forceinline__ Tile vtile(const EpiGeom& g) const {
         Tile t;
-        t.zr = buf_srd(reinterpret_cast<const char*>(e.ZR) + 2 * (g.m0 * (2L * e.C) + g.n0));
-        t.vzr = (g.rr * 2 * e.C + g.c) * 2;
-        t.szr = g.step * 2 * e.C * 2;
+        if (SAVE_R || !(V & 1)) {
+            t.zr = buf_srd(reinterpret_cast<const char*>(e.ZR) + 2 * (g.m0 * (2L * e.C) + g.n0));
+            t.vzr = (g.rr * 2 * e.C + g.c) * 2;
+            t.szr = g.step * 2 * e.C * 2;
+        }
         if (V & 1) {
             const long o = g.m0 * e.C + g.n0 - e.C;
             t.h = buf_srd(reinterpret_cast<const char*>(e.h) + 2 * o);
@@ -626,7 +636,7 @@ struct EpiGates8F {
 #define F_(k) fast_sigmoid(v.k + ca.b.k)
         const F8 g = REGT_F8(F_);
 #undef F_
-        buf_st8_bf16(t.zr, t.vzr + i * t.szr, g);
+        if (SAVE_R || !(V & 1)) buf_st8_bf16(t.zr, t.vzr + i * t.szr, g);
         if (V & 1) {
             const F8 h = widen8(a.h);
 #define F_(k) (h.k * g.k)
@@ -635,6 +645,8 @@ struct EpiGates8F {
         }
     }
 };
+struct EpiGates8F : EpiGates8T<true> {};
+struct EpiGates8FwdF : EpiGates8T<false> {};
 struct EpiDgrad18F {
     typedef F8 Vec;
     EpiDgrad1 e;
@@ -1067,16 +1079,21 @@ int launch_gemm_bias_act(const GemmSegs& S, long M, int N, const EpiBiasAct& e, 
     }
     return launch_flat(S, M, N, EpiBiasActF{e}, vec, st);
 }
-int launch_gemm_gates(const GemmSegs& S, long M, int N, const EpiGates& e, hipStream_t st) {
+int launch_gemm_gates(const GemmSegs& S, long M, int N, const EpiGates& e, hipStream_t st, bool save_r) {
     REGT_CHECK_ARG(N == 2 * e.C, "gates gemm expects N == 2C");
     const bool vec = e.C % 4 == 0 && a16(e.ZR) && a16(e.h) && a16(e.q) && a16(e.bias);
     if (e.h_bf16 || e.zr_bf16) {
         REGT_CHECK_ARG(fast_class(S, N, vec) == 1 && e.C % 8 == 0, "gates gemm: bf16-stored activations need the bf16-operand vector path");
-        return launch_split8<EpiGates8F, false>(S, M, N, EpiGates8F{e}, st);
+        if (!save_r) return launch_split8<EpiGates8FwdF, false>(S, M, N, EpiGates8FwdF{{e}}, st);
+        return launch_split8<EpiGates8F, false>(S, M, N, EpiGates8F{{e}}, st);
     }
-    if (fast_class(S, N, vec) == 1) return launch_fast<EpiGatesF, true, false>(S, M, N, EpiGatesF{e}, 0, st);
+    if (fast_class(S, N, vec) == 1) {
+        if (!save_r) return launch_fast<EpiGatesFwdF, true, false>(S, M, N, EpiGatesFwdF{{e}}, 0, st);
+        return launch_fast<EpiGatesF, true, false>(S, M, N, EpiGatesF{{e}}, 0, st);
+    }
     REGT_CHECK_ARG(!e.q_bf16, "gates gemm: bf16 storage of q needs the vector path");
-    return launch_flat(S, M, N, EpiGatesF{e}, vec, st);
+    if (!save_r) return launch_flat(S, M, N, EpiGatesFwdF{{e}}, vec, st);
+    return launch_flat(S, M, N, EpiGatesF{{e}}, vec, st);
 }
 int launch_gemm_dgrad1(const GemmSegs& S, long M, int N, const EpiDgrad1& e, hipStream_t st) {
     REGT_CHECK_ARG(N == e.C, "dgrad1 gemm expects N == C");
@@ -1136,6 +1153,9 @@ int launch_gemm_mask_add(const GemmSegs& S, long M, int N, const EpiMaskAdd& e, 
 // with the gate (Z*h + (1-Z)*Ht) and accumulated with the attention probability p_t in registers;
 // the hidden state (N, C) is written once after the last period.
 // Generic (scalar-epilogue) fallback of the candidate stage: one workgroup walks the T periods of a node tile.
+// SAVE = false in all candidate kernels below (forward-only calls, REGT_DIMS_FORWARD_ONLY): H~ is blended and summed but not stored
+// -- only the backward pass reads it; a.Ht is then NULL.
+template <bool SAVE>
 __global__ __launch_bounds__(256, 1) void gemm_cand_kernel(CandArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tiles_n = (a.C + GBN - 1) / GBN;
@@ -1166,7 +1186,7 @@ __global__ __launch_bounds__(256, 1) void gemm_cand_kernel(CandArgs a) {
         core.for_each2(acc, oh, [&](int r, int c, float v, float o) {
             long m = rm.grow(r);
             float ht = fast_tanh(v + a.bias[c]);
-            a.Ht[m * C + c] = ht;
+            if (SAVE) a.Ht[m * C + c] = ht;
             float Z = a.ZR[m * 2 * C + c];
             float hv = a.h[m * C + c];
             return o + pt * (Z * hv + (1.0f - Z) * ht);
@@ -1183,7 +1203,7 @@ __global__ __launch_bounds__(256, 1) void gemm_cand_kernel(CandArgs a) {
 // that straddles two tiles (T <= 64 < 128, so never more than two) gets one partial sum from each,
 // added atomically into the zero-initialised hidden state -- two addends commute, so the result is
 // bit-reproducible.
-template <class Core>
+template <class Core, bool SAVE>
 __global__ __launch_bounds__(256, 2) void gemm_cand_flat_kernel(CandArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int BM = Core::BM, BN = Core::BN, KROW = Core::EKROW, TPR = Core::ETPR;
@@ -1239,7 +1259,7 @@ __global__ __launch_bounds__(256, 2) void gemm_cand_flat_kernel(CandArgs a) {
 #define F_(k) fast_tanh(v.k + b.k)
                     const float4 ht = REGT_V4(F_);
 #undef F_
-                    st4(a.Ht + m * C + c, ht);
+                    if (SAVE) st4(a.Ht + m * C + c, ht);
                     float4 o;
                     o.x = pt * (Z[j].x * hv[j].x + (1.0f - Z[j].x) * ht.x);
                     o.y = pt * (Z[j].y * hv[j].y + (1.0f - Z[j].y) * ht.y);
@@ -1277,6 +1297,7 @@ __global__ __launch_bounds__(256, 2) void gemm_cand_flat_kernel(CandArgs a) {
 
 // The same with ZR, h and Ht stored as bf16 (bf16-operand core, REGT_GEMM_MODE=bf16): 8 columns per thread, so that the
 // epilogue's reads of Z and h and its store of H~ are 16-byte accesses.
+template <bool SAVE>
 __global__ __launch_bounds__(256, 2) void gemm_cand_flat8_kernel(CandArgs a) {
     using Core = SplitCore<false, 1>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1333,7 +1354,7 @@ __global__ __launch_bounds__(256, 2) void gemm_cand_flat8_kernel(CandArgs a) {
 #define F_(k) fast_tanh(v.k + b.k)
                     const F8 ht = REGT_F8(F_);
 #undef F_
-                    st8(a.Ht, m * C + c, ht, 1);
+                    if (SAVE) st8(a.Ht, m * C + c, ht, 1);
 #define F_(k) (pt * (Z[j].k * hv[j].k + (1.0f - Z[j].k) * ht.k))
                     const F8 o = REGT_F8(F_);
 #undef F_
@@ -1376,13 +1397,15 @@ __global__ __launch_bounds__(256, 2) void gemm_cand_flat8_kernel(CandArgs a) {
 // not one 64-bit modulo per row slot of every thread; arrays are addressed through buffer descriptors (one per array
 // and tile); a full tile runs without a single branch (see the functor notes at the top of this file).
 struct CandRowEnt { int nt; float p; };        // nt = (node - first node of the tile) << 8 | period
-template <int NP, bool FULL>
+template <int NP, bool FULL, bool SAVE>
 __device__ __forceinline__ void cand_epilogue(const CandArgs& a, const SplitCore<false, NP>& core, f32x16 (&acc)[2][2], float* lds,
                                               const CandRowEnt* rowtab, long m0, int n0, int nvalid, int node0, int t0) {
     const int tid = threadIdx.x, rr = tid >> 5, c4 = 4 * (tid & 31);
     const int C = a.C;
     const bool col_ok = FULL || n0 + c4 < C;
-    const __amdgpu_buffer_rsrc_t szr = buf_srd(a.ZR + m0 * (2L * C) + n0), sh = buf_srd(a.h + m0 * C + n0), sht = buf_srd(a.Ht + m0 * C + n0);
+    const __amdgpu_buffer_rsrc_t szr = buf_srd(a.ZR + m0 * (2L * C) + n0), sh = buf_srd(a.h + m0 * C + n0);
+    __amdgpu_buffer_rsrc_t sht;
+    if (SAVE) sht = buf_srd(a.Ht + m0 * C + n0);
     const int vc = (rr * C + c4) * 4, vzr = (rr * 2 * C + c4) * 4, sc = 8 * C * 4, szs = 2 * sc;
     const float4 b = col_ok ? ld4(a.bias + n0 + c4) : make_float4(0, 0, 0, 0);
     constexpr int RR = 4, NR = 16 / RR;
@@ -1413,7 +1436,10 @@ __device__ __forceinline__ void cand_epilogue(const CandArgs& a, const SplitCore
 #define F_(q) fast_tanh(v.q + b.q)
                 const float4 ht = REGT_V4(F_);
 #undef F_
-                buf_st4(sht, vc + i * sc, 0, ht);
+                // (forward-only: the value is pinned where the store stood -- an empty asm statement, no instruction; with H~ simply
+                // not stored hipcc rescheduled the rounds of the fp32 kernel into 12 spilled registers under its 168-register cap)
+                if (SAVE) buf_st4(sht, vc + i * sc, 0, ht);
+                else { const u32x4_t w_ = {__float_as_uint(ht.x), __float_as_uint(ht.y), __float_as_uint(ht.z), __float_as_uint(ht.w)}; asm volatile("" :: "v"(w_), "v"(vc + i * sc)); }
                 const float4 Zv = Z[k & 1][j], hh = hv[k & 1][j];
 #define F_(q) __fmul_rn(pt, gru_blend(Zv.q, hh.q, ht.q))
                 *reinterpret_cast<float4*>(img) = REGT_V4(F_);
@@ -1446,7 +1472,7 @@ __device__ __forceinline__ void cand_epilogue(const CandArgs& a, const SplitCore
         }
     }
 }
-template <int NP>
+template <int NP, bool SAVE>
 __global__ __launch_bounds__(256, 3) void gemm_cand_split_kernel(CandArgs a, int uniform) {
     using Core = SplitCore<false, NP>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1475,21 +1501,22 @@ __global__ __launch_bounds__(256, 3) void gemm_cand_split_kernel(CandArgs a, int
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     if (uniform) core.run_uniform(acc, false);
     else core.run(acc, false);
-    if (rm.nvalid == GBM && n0 + GBN <= a.C) cand_epilogue<NP, true>(a, core, acc, lds, rowtab, m0, n0, GBM, node0, t0);
-    else cand_epilogue<NP, false>(a, core, acc, lds, rowtab, m0, n0, rm.nvalid, node0, t0);
+    if (rm.nvalid == GBM && n0 + GBN <= a.C) cand_epilogue<NP, true, SAVE>(a, core, acc, lds, rowtab, m0, n0, GBM, node0, t0);
+    else cand_epilogue<NP, false, SAVE>(a, core, acc, lds, rowtab, m0, n0, rm.nvalid, node0, t0);
 }
 
 // The same with Z, h and H~ stored as bf16 (REGT_GEMM_MODE=bf16, bf16-operand core NP = 1): 8 columns per thread (16-byte
 // accesses of the bf16 arrays), row slots i = 0 .. 7: row (tid >> 4) + 16 i.
-template <bool FULL>
+template <bool FULL, bool SAVE>
 __device__ __forceinline__ void cand8_epilogue(const CandArgs& a, const SplitCore<false, 1>& core, f32x16 (&acc)[2][2], float* lds,
                                                const CandRowEnt* rowtab, long m0, int n0, int nvalid, int node0, int t0) {
     const int tid = threadIdx.x, rr = tid >> 4, c8 = 8 * (tid & 15);
     const int C = a.C;
     const bool col_ok = FULL || n0 + c8 < C;
     const __amdgpu_buffer_rsrc_t szr = buf_srd(reinterpret_cast<const char*>(a.ZR) + 2 * (m0 * (2L * C) + n0)),
-                                 sh = buf_srd(reinterpret_cast<const char*>(a.h) + 2 * (m0 * C + n0)),
-                                 sht = buf_srd(reinterpret_cast<const char*>(a.Ht) + 2 * (m0 * C + n0));
+                                 sh = buf_srd(reinterpret_cast<const char*>(a.h) + 2 * (m0 * C + n0));
+    __amdgpu_buffer_rsrc_t sht;
+    if (SAVE) sht = buf_srd(reinterpret_cast<const char*>(a.Ht) + 2 * (m0 * C + n0));
     const int vc = (rr * C + c8) * 2, vzr = (rr * 2 * C + c8) * 2, sc = 16 * C * 2, szs = 2 * sc;
     F8 b{make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
     if (col_ok) b = ld8(a.bias, n0 + c8, 0);
@@ -1521,7 +1548,7 @@ __device__ __forceinline__ void cand8_epilogue(const CandArgs& a, const SplitCor
 #define F_(q) fast_tanh(v.q + b.q)
                 const F8 ht = REGT_F8(F_);
 #undef F_
-                buf_st8_bf16(sht, vc + i * sc, ht);
+                if (SAVE) buf_st8_bf16(sht, vc + i * sc, ht);
                 const F8 Zv = widen8(Z[k & 1][j]), hh = widen8(hv[k & 1][j]);
 #define F_(q) __fmul_rn(pt, gru_blend(Zv.q, hh.q, ht.q))
                 const F8 o = REGT_F8(F_);
@@ -1567,6 +1594,7 @@ __device__ __forceinline__ void cand8_epilogue(const CandArgs& a, const SplitCor
         }
     }
 }
+template <bool SAVE>
 __global__ __launch_bounds__(256, 3) void gemm_cand_split8_kernel(CandArgs a, int uniform) {
     using Core = SplitCore<false, 1>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1594,57 +1622,81 @@ __global__ __launch_bounds__(256, 3) void gemm_cand_split8_kernel(CandArgs a, in
     if (uniform == 2) core.run_uniform_frag(acc, false);
     else if (uniform) core.run_uniform(acc, false);
     else core.run(acc, false);
-    if (rm.nvalid == GBM && n0 + GBN <= a.C) cand8_epilogue<true>(a, core, acc, lds, rowtab, m0, n0, GBM, node0, t0);
-    else cand8_epilogue<false>(a, core, acc, lds, rowtab, m0, n0, rm.nvalid, node0, t0);
+    if (rm.nvalid == GBM && n0 + GBN <= a.C) cand8_epilogue<true, SAVE>(a, core, acc, lds, rowtab, m0, n0, GBM, node0, t0);
+    else cand8_epilogue<false, SAVE>(a, core, acc, lds, rowtab, m0, n0, rm.nvalid, node0, t0);
 }
 
-int launch_gemm_candidate(const CandArgs& a, hipStream_t st) {
+// `save` = false: the forward-only kernels (H~ not stored, a.Ht ignored); the choice of core is the same either way
+template <class Core>
+static int launch_cand_flat(const CandArgs& a, bool save, unsigned grid, int lds_bytes, hipStream_t st) {
+    static bool attr_done[2] = {false, false};
+    if (save) {
+        if (int rc = set_lds_once(&gemm_cand_flat_kernel<Core, true>, lds_bytes, &attr_done[1])) return rc;
+        hipLaunchKernelGGL((gemm_cand_flat_kernel<Core, true>), dim3(grid), dim3(256), lds_bytes, st, a);
+    } else {
+        if (int rc = set_lds_once(&gemm_cand_flat_kernel<Core, false>, lds_bytes, &attr_done[0])) return rc;
+        hipLaunchKernelGGL((gemm_cand_flat_kernel<Core, false>), dim3(grid), dim3(256), lds_bytes, st, a);
+    }
+    return REGT_OK;
+}
+int launch_gemm_candidate(const CandArgs& a, hipStream_t st, bool save) {
     REGT_CHECK_ARG(a.num_nodes > 0 && a.T > 0 && a.C > 0, "candidate gemm: empty problem");
+    REGT_CHECK_ARG(!save || a.Ht, "candidate gemm: the training form stores H~ (Ht is NULL)");
     long tiles = (long)cdiv(a.num_nodes, GBM) * cdiv(a.C, GBN);
     const bool vec = a.C % 4 == 0 && a16(a.ZR) && a16(a.h) && a16(a.Ht) && a16(a.OH) && a16(a.bias) &&
                      fast_class(a.S, a.C, true) == 1;
     REGT_CHECK_ARG(!a.act_bf16 || (vec && gemm_mode() == 2), "candidate gemm: bf16-stored activations need the bf16-operand vector path");
     if (vec) {
-        static bool attr_done = false, attr_done_split = false, attr_done_bf16 = false;
-        if (int rc = set_lds_once(&gemm_cand_flat_kernel<FastCore<true, false>>, G_FAST_LDS_BYTES, &attr_done)) return rc;
-        if (int rc = set_lds_once(&gemm_cand_flat_kernel<SplitCore<false, 3>>, G_FAST_LDS_BYTES, &attr_done_split)) return rc;
-        if (int rc = set_lds_once(&gemm_cand_flat_kernel<SplitCore<false, 1>>, G_FAST_LDS_BYTES, &attr_done_bf16)) return rc;
         const long M = (long)a.num_nodes * a.T;
         const long ftiles = (long)cdiv(M, GBM) * cdiv(a.C, GBN);
         REGT_CHECK_ARG(ftiles < (1L << 31) && a.T <= 255, "candidate gemm: too many tiles / T > 255");
         if (int rc = launch_zero_f32(a.OH, (long)a.num_nodes * a.C, st)) return rc;
         // three-workgroup kernels (fp32 storage): 64-row halves need T <= 64 (a node meets at most two halves)
         const bool three = !a.act_bf16 && !fp32_core_wide() && gemm_mode() != 2 && (gemm_mode() == 1 || ftiles >= SMALL_TILE_LIMIT) && M < (1L << 31);
-        if (three && gemm_mode() == 0)
-            hipLaunchKernelGGL((gemm_cand_split_kernel<0>), dim3((unsigned)ftiles), dim3(256), SplitGeom<0>::LDS_BYTES, st, a, uniform_ok(a.S, M));
-        else if (three)
-            hipLaunchKernelGGL((gemm_cand_split_kernel<3>), dim3((unsigned)ftiles), dim3(256), SplitGeom<3>::LDS_BYTES, st, a, uniform_ok(a.S, M));
-        else if (gemm_mode() == 1)
-            hipLaunchKernelGGL((gemm_cand_flat_kernel<SplitCore<false, 3>>), dim3((unsigned)ftiles), dim3(256), G_FAST_LDS_BYTES, st, a);
-        else if (gemm_mode() == 2 && a.act_bf16 && a.C % 8 == 0 && M < (1L << 31) && !fp32_core_wide()) {
+        if (three && gemm_mode() == 0) {
+            if (save) hipLaunchKernelGGL((gemm_cand_split_kernel<0, true>), dim3((unsigned)ftiles), dim3(256), SplitGeom<0>::LDS_BYTES, st, a, uniform_ok(a.S, M));
+            else hipLaunchKernelGGL((gemm_cand_split_kernel<0, false>), dim3((unsigned)ftiles), dim3(256), SplitGeom<0>::LDS_BYTES, st, a, uniform_ok(a.S, M));
+        } else if (three) {
+            if (save) hipLaunchKernelGGL((gemm_cand_split_kernel<3, true>), dim3((unsigned)ftiles), dim3(256), SplitGeom<3>::LDS_BYTES, st, a, uniform_ok(a.S, M));
+            else hipLaunchKernelGGL((gemm_cand_split_kernel<3, false>), dim3((unsigned)ftiles), dim3(256), SplitGeom<3>::LDS_BYTES, st, a, uniform_ok(a.S, M));
+        } else if (gemm_mode() == 1) {
+            if (int rc = launch_cand_flat<SplitCore<false, 3>>(a, save, (unsigned)ftiles, G_FAST_LDS_BYTES, st)) return rc;
+        } else if (gemm_mode() == 2 && a.act_bf16 && a.C % 8 == 0 && M < (1L << 31) && !fp32_core_wide()) {
             for (int q = 0; q < a.S.nseg; ++q)
                 REGT_CHECK_ARG(!(a.S.seg[q].flags & SEG_B_FRAG) || uniform_ok(a.S, M) == 2, "candidate gemm: fragment-order weights need K %% 32 == 0");
-            hipLaunchKernelGGL(gemm_cand_split8_kernel, dim3((unsigned)ftiles), dim3(256), SplitGeom<1>::LDS_BYTES, st, a, uniform_ok(a.S, M));
+            if (save) hipLaunchKernelGGL(gemm_cand_split8_kernel<true>, dim3((unsigned)ftiles), dim3(256), SplitGeom<1>::LDS_BYTES, st, a, uniform_ok(a.S, M));
+            else hipLaunchKernelGGL(gemm_cand_split8_kernel<false>, dim3((unsigned)ftiles), dim3(256), SplitGeom<1>::LDS_BYTES, st, a, uniform_ok(a.S, M));
         } else if (gemm_mode() == 2 && a.act_bf16) {
             for (int q = 0; q < a.S.nseg; ++q)
                 REGT_CHECK_ARG(!(a.S.seg[q].flags & SEG_B_FRAG), "candidate gemm: fragment-order weights need the three-workgroup kernel");
-            static bool attr_done8 = false;
+            static bool attr_done8 = false, attr_done8f = false;
             REGT_CHECK_ARG(a.C % 8 == 0, "candidate gemm: bf16 storage needs C %% 8 == 0");
-            if (int rc = set_lds_once(&gemm_cand_flat8_kernel, G_FAST_LDS_BYTES, &attr_done8)) return rc;
-            hipLaunchKernelGGL(gemm_cand_flat8_kernel, dim3((unsigned)ftiles), dim3(256), G_FAST_LDS_BYTES, st, a);
-        } else if (gemm_mode() == 2)
-            hipLaunchKernelGGL((gemm_cand_flat_kernel<SplitCore<false, 1>>), dim3((unsigned)ftiles), dim3(256), G_FAST_LDS_BYTES, st, a);
-        else if (ftiles < SMALL_TILE_LIMIT)      // small graph: 64 x 64 tiles (a node's T <= 64 rows still span at most two)
-            hipLaunchKernelGGL((gemm_cand_flat_kernel<SmallCore<true, false>>), dim3((unsigned)(cdiv(M, SM_B) * cdiv(a.C, SM_B))),
-                               dim3(256), SM_LDS_BYTES, st, a);
-        else
-            hipLaunchKernelGGL((gemm_cand_flat_kernel<FastCore<true, false>>), dim3((unsigned)ftiles), dim3(256), G_FAST_LDS_BYTES, st, a);
+            if (save) {
+                if (int rc = set_lds_once(&gemm_cand_flat8_kernel<true>, G_FAST_LDS_BYTES, &attr_done8)) return rc;
+                hipLaunchKernelGGL(gemm_cand_flat8_kernel<true>, dim3((unsigned)ftiles), dim3(256), G_FAST_LDS_BYTES, st, a);
+            } else {
+                if (int rc = set_lds_once(&gemm_cand_flat8_kernel<false>, G_FAST_LDS_BYTES, &attr_done8f)) return rc;
+                hipLaunchKernelGGL(gemm_cand_flat8_kernel<false>, dim3((unsigned)ftiles), dim3(256), G_FAST_LDS_BYTES, st, a);
+            }
+        } else if (gemm_mode() == 2) {
+            if (int rc = launch_cand_flat<SplitCore<false, 1>>(a, save, (unsigned)ftiles, G_FAST_LDS_BYTES, st)) return rc;
+        } else if (ftiles < SMALL_TILE_LIMIT) {    // small graph: 64 x 64 tiles (a node's T <= 64 rows still span at most two)
+            if (save) hipLaunchKernelGGL((gemm_cand_flat_kernel<SmallCore<true, false>, true>), dim3((unsigned)(cdiv(M, SM_B) * cdiv(a.C, SM_B))), dim3(256), SM_LDS_BYTES, st, a);
+            else hipLaunchKernelGGL((gemm_cand_flat_kernel<SmallCore<true, false>, false>), dim3((unsigned)(cdiv(M, SM_B) * cdiv(a.C, SM_B))), dim3(256), SM_LDS_BYTES, st, a);
+        } else {
+            if (int rc = launch_cand_flat<FastCore<true, false>>(a, save, (unsigned)ftiles, G_FAST_LDS_BYTES, st)) return rc;
+        }
     } else {
         for (int q = 0; q < a.S.nseg; ++q)
             REGT_CHECK_ARG(!(a.S.seg[q].flags & SEG_A_BF16), "candidate gemm: a bf16-stored operand needs the bf16-operand vector path");
-        static bool attr_done2 = false;
-        if (int rc = set_lds_once(&gemm_cand_kernel, G_LDS_BYTES, &attr_done2)) return rc;
-        hipLaunchKernelGGL(gemm_cand_kernel, dim3((unsigned)tiles), dim3(256), G_LDS_BYTES, st, a);
+        static bool attr_done2 = false, attr_done2f = false;
+        if (save) {
+            if (int rc = set_lds_once(&gemm_cand_kernel<true>, G_LDS_BYTES, &attr_done2)) return rc;
+            hipLaunchKernelGGL(gemm_cand_kernel<true>, dim3((unsigned)tiles), dim3(256), G_LDS_BYTES, st, a);
+        } else {
+            if (int rc = set_lds_once(&gemm_cand_kernel<false>, G_LDS_BYTES, &attr_done2f)) return rc;
+            hipLaunchKernelGGL(gemm_cand_kernel<false>, dim3((unsigned)tiles), dim3(256), G_LDS_BYTES, st, a);
+        }
     }
     REGT_CHECK_LAUNCH();
     return REGT_OK;

@@ -102,7 +102,8 @@ struct EpiMaskAdd {     // out[m, c] = v * (mask[m, c] > 0) + (add ? add[m, c] :
 };
 
 int launch_gemm_bias_act(const GemmSegs& S, long M, int N, const EpiBiasAct& e, hipStream_t st);
-int launch_gemm_gates(const GemmSegs& S, long M, int N, const EpiGates& e, hipStream_t st);
+// save_r = false (forward-only calls): the R half of ZR is not written (Z and q are)
+int launch_gemm_gates(const GemmSegs& S, long M, int N, const EpiGates& e, hipStream_t st, bool save_r = true);
 int launch_gemm_dgrad1(const GemmSegs& S, long M, int N, const EpiDgrad1& e, hipStream_t st);
 // cell_bwd + dgrad_candidate in one launch (fp32 arithmetic, C % 128 == 0, big-tile regime): see EpiDgrad1's last fields
 bool gemm_dgrad1_gen_ok(long M, int C, int num_nodes);
@@ -130,7 +131,8 @@ struct CandArgs {
     int node_sum_rows = 64; // bf16 storage: the rows of a node are summed in row order inside blocks of 64 (the staged half) or 16
                             //   rows (what a wave of fused_rows.hip owns: the two paths then agree bit for bit); T <= 16 for the latter
 };
-int launch_gemm_candidate(const CandArgs& a, hipStream_t st);
+// save = false (forward-only calls): H~ is not stored, a.Ht may be NULL
+int launch_gemm_candidate(const CandArgs& a, hipStream_t st, bool save = true);
 
 // ---- weight-gradient GEMM: out[Nout x Nin] = P^T Q, split over row chunks ----------------------
 struct WgradArgs {
@@ -255,7 +257,7 @@ struct FusedFwdArgs {
     const void *Gzrf, *Ghf;                   // composed [Gz; Gr] (2C x F) and Gh (C x F), fragment order
     const float *bprime, *czr, *ch, *probs;   // composed biases (C, 2C, C), softmax(attention) (T)
     const int* node_region;                   // (nodes) or nullptr (one region)
-    void *h, *ZR, *q, *Ht;                    // bf16 outputs: (M x C), (M x 2C) = [Z | R], (M x C), (M x C)
+    void *h, *ZR, *q, *Ht;                    // bf16 outputs: (M x C), (M x 2C) = [Z | R], (M x C), (M x C); not touched (may be NULL) with save = false
     float* OH;                                // (nodes x C) fp32, zero-initialised: the attention-weighted hidden state
     long M; int T; float slope; int act_lrelu;
     long nodes;                               // M / T                                            } filled in by launch_fused_forward
@@ -263,16 +265,17 @@ struct FusedFwdArgs {
     unsigned* tile_ctr;                       // workspace word (zeroed by the launcher): the persistent workgroups draw their tiles from it
     const char* wbase;                        // fused_rows.hip: the weight blocks as 32-bit offsets from one base (filled in by its launcher)
     unsigned o_uz, o_ur, o_uh, o_gzr, o_gh, o_a0, o_aall;
-    int dbg;                                  // timing-only switches (REGT_FUSED_DBG, fused.hip); 0 in normal operation
+    int dbg;                                  // timing-only switch (REGT_FUSED_DBG, fused.hip: bit 1 = no weight traffic); 0 in normal operation
     long* trace;                              // developer trace buffer (REGT_FUSED_TRACE) or nullptr
 };
 long fused_trace_fetch(long* out, long capacity);
-int launch_fused_forward(const FusedFwdArgs& a, int C, int F, hipStream_t st);
+// save = false: the forward-only instantiation (no activation stores; REGT_DIMS_FORWARD_ONLY)
+int launch_fused_forward(const FusedFwdArgs& a, int C, int F, hipStream_t st, bool save = true);
 bool fused_forward_ok(int C, int F);
 // the row-owning form (fused_rows.hip): a wave owns 16 whole rows, weights stream through LDS; needs region ids sorted by node.
 // waves = 8: one workgroup of eight waves per CU (the product form); 4: two workgroups of four with half the ring each (slower --
 // twice the weight traffic -- kept because its short ring is the harder test of the hand-counted waits)
-int launch_fused_forward_rows(const FusedFwdArgs& a, int C, int F, int waves, hipStream_t st);
+int launch_fused_forward_rows(const FusedFwdArgs& a, int C, int F, int waves, hipStream_t st, bool save = true);
 bool fused_forward_rows_ok(int C, int F, int T);
 
 // ---- fused data gradients of the cell for the bf16 arithmetic (fused.hip): cell_bwd + dgrad_candidate + dgrad_gates in one kernel

@@ -93,7 +93,8 @@ class _WsHandle:
 
     def __del__(self):
         try:
-            _POOL.release(self.ws)
+            if self.ws is not None:              # (a forward-only call has released its block already)
+                _POOL.release(self.ws)
         except Exception:  # interpreter shutdown
             pass
 
@@ -133,6 +134,147 @@ def set_grad_accumulation_in_backward(flag: bool) -> bool:
     return prev
 
 
+# Evaluation (train.evaluate*, evaluate.predict_metrics*, a plain model(x) under torch.no_grad()) needs no backward: the modules then
+# call the library with REGT_DIMS_FORWARD_ONLY -- same pred / hidden bit for bit, no activation stores, a workspace of
+# regt_forward_only_workspace_bytes (no M x C array at all on the fused bf16 forward, four instead of nine elsewhere) that goes back
+# to the pool when the call returns.  The decision is made by the callers of the Functions below (inside Function.forward grad mode
+# is always off).  The switch exists for A/B tests and as an escape hatch.
+_FORWARD_ONLY_IN_NO_GRAD = True
+
+
+def set_forward_only_in_no_grad(flag: bool) -> bool:
+    """Returns the previous setting."""
+    global _FORWARD_ONLY_IN_NO_GRAD
+    prev, _FORWARD_ONLY_IN_NO_GRAD = _FORWARD_ONLY_IN_NO_GRAD, bool(flag)
+    return prev
+
+
+def wants_forward_only(*tensors) -> bool:
+    """True when no gradient can be asked of a forward on ``tensors`` (grad mode off, or none of them requires one)."""
+    if not _FORWARD_ONLY_IN_NO_GRAD:
+        return False
+    return not torch.is_grad_enabled() or not any(t_ is not None and t_.requires_grad for t_ in tensors)
+
+
+class _FwdState:
+    """What one regt_forward call leaves for its backward."""
+    __slots__ = ("graph", "regional", "dims", "handle", "wsb", "ps", "gs", "xp", "names", "f_real", "f_pad", "params")
+
+
+def _regt_forward_call(x: torch.Tensor, graph: PreparedGraph, regional: bool, slope: float, packed, params, forward_only: bool):
+    """The library call behind :class:`RegTGCNFunction` and :func:`regt_run`: returns ``(pred, hidden, state)``; ``state`` is
+    None for a forward-only call (its workspace block is back in the pool)."""
+    arith = flags = 0
+    if isinstance(packed, tuple):
+        packed, arith, flags = packed
+    if forward_only:
+        flags = int(flags) | _lib.DIMS_FORWARD_ONLY
+    lib = _lib.load()
+    if not x.is_cuda:
+        raise _lib.RegtError("RegT-GCN forward needs CUDA/HIP tensors: there is no CPU path in this package")
+    xbf = packed and x.dtype == torch.bfloat16        # region shard that packs and exchanges its rows as bf16 (REGT_GEMM_MODE=bf16)
+    if (x.dtype != torch.float32 and not xbf) or x.dim() != 3:
+        raise ValueError(f"x must be float32 (N,F,T) (or packed bfloat16 (x_rows,T,F)), got {x.dtype} {tuple(x.shape)}")
+    names = param_names(regional)
+    if len(params) != len(names):
+        raise ValueError(f"expected {len(names)} parameter tensors, got {len(params)}")
+    for n_, p_ in zip(names, params):
+        if p_.dtype != torch.float32 or not p_.is_cuda or not p_.is_contiguous():
+            raise ValueError(f"parameter {n_} must be a contiguous float32 CUDA tensor")
+    x = x.contiguous()
+    # The kernels read 16-byte feature rows (F a multiple of 4; the reference uses F = 8).  Any other width is staged
+    # padded: zero feature columns in x and zero weight columns for them change nothing in the forward, and their
+    # gradient columns (ds^T x_pad = 0) are sliced off in the backward.
+    f_real = x.shape[2] if packed else x.shape[1]
+    f_pad = (-f_real) % 4
+    if f_pad and xbf:
+        raise ValueError("bf16 packed input needs a feature width that is a multiple of 4")
+    if f_pad:
+        x = torch.nn.functional.pad(x, (0, f_pad) if packed else (0, 0, 0, f_pad)).contiguous()
+        params = tuple(torch.nn.functional.pad(p_, (0, f_pad)).contiguous() if n_ in F_WIDE_PARAMS else p_
+                       for n_, p_ in zip(names, params))
+    if packed:
+        x_rows, T, F = x.shape
+        N = graph.num_nodes
+        if x_rows < N:
+            raise ValueError(f"packed input has {x_rows} rows but the shard owns {N} nodes")
+    else:
+        N, F, T = x.shape
+        x_rows = N
+        if N != graph.num_nodes:
+            raise ValueError(f"x has {N} nodes but the prepared graph has {graph.num_nodes}")
+    # shape validation, the dims / parameter-pointer structs and the workspace size only depend on (shapes, parameter
+    # addresses): remembered per graph, so a steady-state step skips ~60 us of Python (TPIMS-scale steps are host-bound)
+    plan_key = (N, T, F, x_rows, regional, float(slope), arith, flags, tuple((p_.data_ptr(), tuple(p_.shape)) for p_ in params))
+    plans = graph.__dict__.setdefault("_plan_cache", {})
+    plan = plans.get(plan_key)
+    if plan is None:
+        tens = dict(zip(names, params))
+        Cdim = tens["tgnn.conv.bias"].numel()
+        O = tens["linear2.weight"].shape[0]
+        H1 = tens["linear1.weight"].shape[0]
+        R = graph.num_regions
+        expect = {"tgnn._attention": (T,), "tgnn.conv.lins.0.weight": (Cdim, F), "tgnn.conv.lins.1.weight": (Cdim, F),
+                  "linear1.weight": (H1, Cdim), "linear2.weight": (O, H1)}
+        for k in GATES:
+            expect[f"tgnn._base_tgcn.conv_{k}.lin.weight"] = (Cdim, F)
+            expect[f"tgnn._base_tgcn.linear_{k}.weight"] = (Cdim, 2 * Cdim)
+        if regional:
+            expect["tgnn.linear.weight"] = (Cdim, R * Cdim)
+        for k, shp in expect.items():
+            if tuple(tens[k].shape) != shp:
+                raise ValueError(f"parameter {k} has shape {tuple(tens[k].shape)}, expected {shp}")
+        dims = _lib.Dims(N, T, F, Cdim, R, O, H1, 1 if regional else 0, float(slope), int(arith), int(flags))
+        gs = _graph_struct(graph, T)
+        if forward_only and packed:
+            sizer = "regt_forward_only_packed_workspace_bytes"        # (x_rows and the row type enter the form and the layout)
+            wsb = lib.regt_forward_only_packed_workspace_bytes(C.byref(dims), C.byref(gs), x_rows, 1 if xbf else 0)
+        elif forward_only:
+            sizer = "regt_forward_only_workspace_bytes"
+            wsb = lib.regt_forward_only_workspace_bytes(C.byref(dims), C.byref(gs))
+        else:
+            sizer = "regt_workspace_bytes"
+            wsb = lib.regt_workspace_bytes(C.byref(dims), gs.n_chunks, gs.overlap)
+        if wsb == 0:
+            _lib.check(1, sizer)
+        if len(plans) > 16:
+            plans.clear()
+        plan = plans[plan_key] = (dims, gs, wsb, _fill(_lib.Params(), tens, regional), Cdim, O)
+    dims, gs, wsb, ps, Cdim, O = plan
+    handle = _WsHandle(_POOL.acquire(wsb, x.device))
+    ws = handle.ws
+    pred = torch.empty(N, O, dtype=torch.float32, device=x.device)
+    hidden = torch.empty(N, Cdim, dtype=torch.float32, device=x.device)
+    if xbf:
+        _lib.check(lib.regt_forward_packed_bf16(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), x_rows, _lib.ptr(pred),
+                                                _lib.ptr(hidden), _lib.ptr(ws), wsb, _stream()), "regt_forward_packed_bf16")
+    elif packed:
+        _lib.check(lib.regt_forward_packed(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), x_rows, _lib.ptr(pred),
+                                           _lib.ptr(hidden), _lib.ptr(ws), wsb, _stream()), "regt_forward_packed")
+    else:
+        _lib.check(lib.regt_forward(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), _lib.ptr(pred),
+                                    _lib.ptr(hidden), _lib.ptr(ws), wsb, _stream()), "regt_forward")
+    if forward_only:
+        _POOL.release(handle.ws)             # stream-ordered: the pool hands the block out again on this stream only
+        handle.ws = None
+        return pred, hidden, None
+    st = _FwdState()
+    st.graph, st.regional, st.dims, st.handle, st.wsb = graph, regional, dims, handle, wsb
+    st.ps, st.gs = ps, gs                    # parameter / graph pointer structs: unchanged until backward
+    st.xp = x if packed else None
+    st.names, st.f_real, st.f_pad, st.params = names, f_real, f_pad, params
+    return pred, hidden, st
+
+
+def regt_run(x: torch.Tensor, graph: PreparedGraph, regional: bool, slope: float, packed, *params: torch.Tensor):
+    """:class:`RegTGCNFunction` where a gradient may be asked for, the forward-only library call where none can
+    (:func:`wants_forward_only`); same arguments and results as ``RegTGCNFunction.apply``."""
+    if wants_forward_only(x, *params):
+        pred, hidden, _ = _regt_forward_call(x, graph, regional, slope, packed, params, True)
+        return pred, hidden
+    return RegTGCNFunction.apply(x, graph, regional, slope, packed, *params)
+
+
 class RegTGCNFunction(torch.autograd.Function):
     """(x, *params) -> (pred (N,O), hidden (N,C)); whole-model forward and backward in HIP."""
 
@@ -143,96 +285,17 @@ class RegTGCNFunction(torch.autograd.Function):
         (x_rows >= N, T, F) of the region-sharded path (own rows first, halo rows after; see dist.py).
         ``packed`` may also be a tuple ``(packed, arith, flags)``: the per-call GEMM arithmetic (``_lib.ARITH_*``) and
         ``_lib.DIMS_*`` switches of regt_dims (0, 0 = the process defaults)."""
-        arith = flags = 0
-        if isinstance(packed, tuple):
-            packed, arith, flags = packed
-        lib = _lib.load()
-        if not x.is_cuda:
-            raise _lib.RegtError("RegT-GCN forward needs CUDA/HIP tensors: there is no CPU path in this package")
-        xbf = packed and x.dtype == torch.bfloat16        # region shard that packs and exchanges its rows as bf16 (REGT_GEMM_MODE=bf16)
-        if (x.dtype != torch.float32 and not xbf) or x.dim() != 3:
-            raise ValueError(f"x must be float32 (N,F,T) (or packed bfloat16 (x_rows,T,F)), got {x.dtype} {tuple(x.shape)}")
-        names = param_names(regional)
-        if len(params) != len(names):
-            raise ValueError(f"expected {len(names)} parameter tensors, got {len(params)}")
         ctx.leaf_params = params                 # the caller's tensors (before any padding): whose .grad an accumulating backward updates
         ctx.set_materialize_grads(False)         # an output the loss does not use arrives as None in backward, not as a tensor of zeros
                                                  # (N x C floats filled and read back for nothing: `hidden` in every training loop)
-        for n_, p_ in zip(names, params):
-            if p_.dtype != torch.float32 or not p_.is_cuda or not p_.is_contiguous():
-                raise ValueError(f"parameter {n_} must be a contiguous float32 CUDA tensor")
-        x = x.contiguous()
-        # The kernels read 16-byte feature rows (F a multiple of 4; the reference uses F = 8).  Any other width is staged
-        # padded: zero feature columns in x and zero weight columns for them change nothing in the forward, and their
-        # gradient columns (ds^T x_pad = 0) are sliced off in the backward.
-        f_real = x.shape[2] if packed else x.shape[1]
-        f_pad = (-f_real) % 4
-        if f_pad and xbf:
-            raise ValueError("bf16 packed input needs a feature width that is a multiple of 4")
-        if f_pad:
-            x = torch.nn.functional.pad(x, (0, f_pad) if packed else (0, 0, 0, f_pad)).contiguous()
-            params = tuple(torch.nn.functional.pad(p_, (0, f_pad)).contiguous() if n_ in F_WIDE_PARAMS else p_
-                           for n_, p_ in zip(names, params))
-        if packed:
-            x_rows, T, F = x.shape
-            N = graph.num_nodes
-            if x_rows < N:
-                raise ValueError(f"packed input has {x_rows} rows but the shard owns {N} nodes")
-        else:
-            N, F, T = x.shape
-            x_rows = N
-            if N != graph.num_nodes:
-                raise ValueError(f"x has {N} nodes but the prepared graph has {graph.num_nodes}")
-        # shape validation, the dims / parameter-pointer structs and the workspace size only depend on (shapes, parameter
-        # addresses): remembered per graph, so a steady-state step skips ~60 us of Python (TPIMS-scale steps are host-bound)
-        plan_key = (N, T, F, x_rows, regional, float(slope), arith, flags, tuple((p_.data_ptr(), tuple(p_.shape)) for p_ in params))
-        plans = graph.__dict__.setdefault("_plan_cache", {})
-        plan = plans.get(plan_key)
-        if plan is None:
-            tens = dict(zip(names, params))
-            Cdim = tens["tgnn.conv.bias"].numel()
-            O = tens["linear2.weight"].shape[0]
-            H1 = tens["linear1.weight"].shape[0]
-            R = graph.num_regions
-            expect = {"tgnn._attention": (T,), "tgnn.conv.lins.0.weight": (Cdim, F), "tgnn.conv.lins.1.weight": (Cdim, F),
-                      "linear1.weight": (H1, Cdim), "linear2.weight": (O, H1)}
-            for k in GATES:
-                expect[f"tgnn._base_tgcn.conv_{k}.lin.weight"] = (Cdim, F)
-                expect[f"tgnn._base_tgcn.linear_{k}.weight"] = (Cdim, 2 * Cdim)
-            if regional:
-                expect["tgnn.linear.weight"] = (Cdim, R * Cdim)
-            for k, shp in expect.items():
-                if tuple(tens[k].shape) != shp:
-                    raise ValueError(f"parameter {k} has shape {tuple(tens[k].shape)}, expected {shp}")
-            dims = _lib.Dims(N, T, F, Cdim, R, O, H1, 1 if regional else 0, float(slope), int(arith), int(flags))
-            gs = _graph_struct(graph, T)
-            wsb = lib.regt_workspace_bytes(C.byref(dims), gs.n_chunks, gs.overlap)
-            if wsb == 0:
-                _lib.check(1, "regt_workspace_bytes")
-            if len(plans) > 16:
-                plans.clear()
-            plan = plans[plan_key] = (dims, gs, wsb, _fill(_lib.Params(), tens, regional), Cdim, O)
-        dims, gs, wsb, ps, Cdim, O = plan
-        handle = _WsHandle(_POOL.acquire(wsb, x.device))
-        ws = handle.ws
-        pred = torch.empty(N, O, dtype=torch.float32, device=x.device)
-        hidden = torch.empty(N, Cdim, dtype=torch.float32, device=x.device)
-        if xbf:
-            _lib.check(lib.regt_forward_packed_bf16(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), x_rows, _lib.ptr(pred),
-                                                    _lib.ptr(hidden), _lib.ptr(ws), wsb, _stream()), "regt_forward_packed_bf16")
-        elif packed:
-            _lib.check(lib.regt_forward_packed(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), x_rows, _lib.ptr(pred),
-                                               _lib.ptr(hidden), _lib.ptr(ws), wsb, _stream()), "regt_forward_packed")
-        else:
-            _lib.check(lib.regt_forward(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), _lib.ptr(pred),
-                                        _lib.ptr(hidden), _lib.ptr(ws), wsb, _stream()), "regt_forward")
-        ctx.graph, ctx.regional, ctx.dims, ctx.ws, ctx.wsb = graph, regional, dims, ws, wsb
-        ctx.ws_handle = handle
-        ctx.ps, ctx.gs = ps, gs                  # parameter / graph pointer structs: unchanged until backward
-        ctx.xp = x if packed else None
-        ctx.names = names
-        ctx.f_real, ctx.f_pad = f_real, f_pad
-        ctx.save_for_backward(hidden, *params)
+        pred, hidden, st = _regt_forward_call(x, graph, regional, slope, packed, params, False)
+        ctx.graph, ctx.regional, ctx.dims, ctx.ws, ctx.wsb = st.graph, st.regional, st.dims, st.handle.ws, st.wsb
+        ctx.ws_handle = st.handle
+        ctx.ps, ctx.gs = st.ps, st.gs
+        ctx.xp = st.xp
+        ctx.names = st.names
+        ctx.f_real, ctx.f_pad = st.f_real, st.f_pad
+        ctx.save_for_backward(hidden, *st.params)
         return pred, hidden
 
     @staticmethod
@@ -410,37 +473,59 @@ def _gcn_graph_struct(op) -> _lib.Graph:
     return g
 
 
+def _cell_forward_call(x, h_in, op, params, forward_only: bool):
+    """regt_cell_forward behind :class:`CellFunction` and :func:`cell_run`: ``(pred, hidden, h_in, dims, handle, wsb)``; the
+    workspace block of a forward-only call is back in the pool (handle None)."""
+    lib = _lib.load()
+    if not x.is_cuda:
+        raise _lib.RegtError("RegT-GCN forward needs CUDA/HIP tensors: there is no CPU path in this package")
+    names = PARAM_NAMES_CELL
+    if len(params) != len(names):
+        raise ValueError(f"expected {len(names)} parameter tensors, got {len(params)}")
+    x, h_in = x.contiguous(), h_in.contiguous()
+    N, F, T = x.shape
+    tens = dict(zip(names, params))
+    Cdim = tens["tgnn._base_tgcn.conv_z.bias"].numel()
+    O, H1 = tens["linear2.weight"].shape[0], tens["linear1.weight"].shape[0]
+    if tuple(h_in.shape) != (N * T, Cdim) or h_in.dtype != torch.float32:
+        raise ValueError(f"h_in must be float32 ({N * T}, {Cdim}), got {h_in.dtype} {tuple(h_in.shape)}")
+    if N != op.num_nodes:
+        raise ValueError(f"x has {N} nodes but the prepared operator has {op.num_nodes}")
+    dims = _lib.Dims(N, T, F, Cdim, 1, O, H1, 0, 0.0, 0, _lib.DIMS_FORWARD_ONLY if forward_only else 0)
+    gs = _gcn_graph_struct(op)
+    if forward_only:
+        wsb = lib.regt_forward_only_workspace_bytes(C.byref(dims), C.byref(gs))
+    else:
+        wsb = lib.regt_workspace_bytes(C.byref(dims), 0, 0)
+    if wsb == 0:
+        _lib.check(1, "regt_forward_only_workspace_bytes" if forward_only else "regt_workspace_bytes")
+    handle = _WsHandle(_POOL.acquire(wsb, x.device))
+    pred = torch.empty(N, O, dtype=torch.float32, device=x.device)
+    hidden = torch.empty(N, Cdim, dtype=torch.float32, device=x.device)
+    ps = _fill(_lib.Params(), tens, False)
+    _lib.check(lib.regt_cell_forward(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), _lib.ptr(h_in), _lib.ptr(pred),
+                                     _lib.ptr(hidden), _lib.ptr(handle.ws), wsb, _stream()), "regt_cell_forward")
+    if forward_only:
+        _POOL.release(handle.ws)             # stream-ordered, as in _regt_forward_call
+        handle.ws = None
+        handle = None
+    return pred, hidden, h_in, dims, handle, wsb
+
+
+def cell_run(x, h_in, op, *params):
+    """:class:`CellFunction` where a gradient may be asked for, the forward-only library call where none can
+    (:func:`wants_forward_only`); same arguments and results as ``CellFunction.apply``."""
+    if wants_forward_only(x, h_in, *params):
+        return _cell_forward_call(x, h_in, op, params, True)[:2]
+    return CellFunction.apply(x, h_in, op, *params)
+
+
 class CellFunction(torch.autograd.Function):
     """(x (N,F,T), h_in (N*T, C), *cell params) -> (pred (N,O), hidden (N,C)): regt_cell_forward / regt_cell_backward."""
 
     @staticmethod
     def forward(ctx, x, h_in, op, *params):
-        lib = _lib.load()
-        if not x.is_cuda:
-            raise _lib.RegtError("RegT-GCN forward needs CUDA/HIP tensors: there is no CPU path in this package")
-        names = PARAM_NAMES_CELL
-        if len(params) != len(names):
-            raise ValueError(f"expected {len(names)} parameter tensors, got {len(params)}")
-        x, h_in = x.contiguous(), h_in.contiguous()
-        N, F, T = x.shape
-        tens = dict(zip(names, params))
-        Cdim = tens["tgnn._base_tgcn.conv_z.bias"].numel()
-        O, H1 = tens["linear2.weight"].shape[0], tens["linear1.weight"].shape[0]
-        if tuple(h_in.shape) != (N * T, Cdim) or h_in.dtype != torch.float32:
-            raise ValueError(f"h_in must be float32 ({N * T}, {Cdim}), got {h_in.dtype} {tuple(h_in.shape)}")
-        if N != op.num_nodes:
-            raise ValueError(f"x has {N} nodes but the prepared operator has {op.num_nodes}")
-        dims = _lib.Dims(N, T, F, Cdim, 1, O, H1, 0, 0.0)
-        gs = _gcn_graph_struct(op)
-        wsb = lib.regt_workspace_bytes(C.byref(dims), 0, 0)
-        if wsb == 0:
-            _lib.check(1, "regt_workspace_bytes")
-        handle = _WsHandle(_POOL.acquire(wsb, x.device))
-        pred = torch.empty(N, O, dtype=torch.float32, device=x.device)
-        hidden = torch.empty(N, Cdim, dtype=torch.float32, device=x.device)
-        ps = _fill(_lib.Params(), tens, False)
-        _lib.check(lib.regt_cell_forward(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), _lib.ptr(h_in), _lib.ptr(pred),
-                                         _lib.ptr(hidden), _lib.ptr(handle.ws), wsb, _stream()), "regt_cell_forward")
+        pred, hidden, h_in, dims, handle, wsb = _cell_forward_call(x, h_in, op, params, False)
         ctx.op, ctx.dims, ctx.ws_handle, ctx.wsb = op, dims, handle, wsb
         ctx.save_for_backward(hidden, h_in, *params)
         ctx.set_materialize_grads(False)         # an unused output (hidden) arrives as None in backward, not as zeros
@@ -757,6 +842,7 @@ class ZeroGradAnchor(torch.autograd.Function):
 
 
 def regt_gcn_forward(x, graph: PreparedGraph, params: Dict[str, torch.Tensor], regional: bool = True, slope: float = 0.01):
-    """Functional entry: ``params`` keyed by the reference's state_dict names."""
+    """Functional entry: ``params`` keyed by the reference's state_dict names.  Like the modules it takes the forward-only call
+    where no gradient can be asked for (:func:`regt_run`)."""
     names = param_names(regional)
-    return RegTGCNFunction.apply(x, graph, regional, slope, False, *[params[n] for n in names])
+    return regt_run(x, graph, regional, slope, False, *[params[n] for n in names])

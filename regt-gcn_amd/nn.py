@@ -28,7 +28,7 @@ import torch.nn as nn
 from . import _lib
 from . import ops
 from .functional import (HEAD_HIDDEN, PARAM_NAMES_CELL, AggregateFunction, Cell0Function, CellFunction, GatAggregateFunction,
-                         GRUFunction, LinearFunction, MLPHeadFunction, RegTGCNFunction, SpatialEmbedFunction, STIDFunction, STNormFunction, ZeroGradAnchor, param_names)
+                         GRUFunction, LinearFunction, MLPHeadFunction, RegTGCNFunction, SpatialEmbedFunction, STIDFunction, STNormFunction, ZeroGradAnchor, cell_run, param_names, regt_run)
 from .graph import (AttentionPattern, GcnOperator, MeanOperator, PreparedGraph, fingerprint, prepare_attention_pattern,
                     prepare_cheb_operator, prepare_gcn_operator, prepare_graph, prepare_mean_operator)
 
@@ -215,8 +215,10 @@ class _FusedModel(nn.Module):
 
     def _run(self, x: torch.Tensor, graph: PreparedGraph, packed: bool = False):
         arith, flags = _lib.arith_code(self.arithmetic), int(self.call_flags)
-        return RegTGCNFunction.apply(x, graph, self.regional, LEAKY_SLOPE, (packed, arith, flags) if (arith or flags) else packed,
-                                     *self._params_in_order())
+        # (regt_run: RegTGCNFunction.apply, or the forward-only library call when no gradient can be asked for -- decided here,
+        # before apply: inside Function.forward grad mode is always off)
+        return regt_run(x, graph, self.regional, LEAKY_SLOPE, (packed, arith, flags) if (arith or flags) else packed,
+                        *self._params_in_order())
 
     def forward_packed(self, x_packed_ext: torch.Tensor, graph: PreparedGraph):
         """Region-sharded entry: ``x_packed_ext`` (x_rows, T, F) = own packed rows + gathered halo rows (dist.py)."""
@@ -410,7 +412,7 @@ class ConvStackedTemporalGCN(nn.Module):
         zero = torch.zeros(3, self.HIDDEN, device=x.device)
         wcat = torch.cat([P.t()] + cs + [zero], dim=0).t().contiguous()         # (512, F + 8): [W_all | c_5 c_4 c_3 c_2 c_1 | 0 0 0]
         h = LinearFunction.apply(feat, wcat, None)                              # (M, 512)
-        return CellFunction.apply(x, h, op, *[sd[k] for k in PARAM_NAMES_CELL])
+        return cell_run(x, h, op, *[sd[k] for k in PARAM_NAMES_CELL])      # (CellFunction, or forward-only without a gradient)
 
     def forward_layerwise(self, x: torch.Tensor, op: GcnOperator):
         """The reference's evaluation order: every layer aggregates its (learned) input at width T*512."""
@@ -424,7 +426,7 @@ class ConvStackedTemporalGCN(nn.Module):
         for layer in range(2, 6):
             s = AggregateFunction.apply(h.view(n, t * c), op)
             h = LinearFunction.apply(s.view(n * t, c), sd[f"tgnn.conv{layer}.lin.weight"], sd[f"tgnn.conv{layer}.bias"])
-        return CellFunction.apply(x, h, op, *[sd[k] for k in PARAM_NAMES_CELL])
+        return cell_run(x, h, op, *[sd[k] for k in PARAM_NAMES_CELL])      # (CellFunction, or forward-only without a gradient)
 
     def forward(self, x, edge_index, edge_attr):
         _need_cuda(x)
