@@ -224,7 +224,8 @@ typedef struct regt_grads {
 } regt_grads;
 
 /* Bytes of device workspace regt_forward / regt_backward need (same buffer for both: the forward
- * leaves the activations the backward reads). */
+ * leaves the activations the backward reads).  The size depends on the CU count of the current device (the weight-gradient slabs
+ * are sized for the chunk counts the launches pick from it): call it with the execution device current. */
 size_t regt_workspace_bytes(const regt_dims* dims, int32_t n_chunks, int32_t overlap);
 
 /* Forward-only calls (evaluation, serving): with REGT_DIMS_FORWARD_ONLY in dims->flags the four forward entry points compute pred
@@ -246,7 +247,9 @@ size_t regt_workspace_bytes(const regt_dims* dims, int32_t n_chunks, int32_t ove
  * rows where the fused form does not apply (regt_forward_packed_bf16 refuses those).
  * Refused with an error, before anything is launched: a forward-only call with workspace_bytes below its sizing function's value
  * (a workspace of exactly that value is accepted); and regt_backward / regt_cell_backward on a workspace whose last forward was
- * forward-only (it holds nothing they could read). */
+ * forward-only (it holds nothing they could read).
+ * As with regt_workspace_bytes, a size may depend on the CU count of the current device (today only the training layout's slab region
+ * does): call both with the execution device current. */
 size_t regt_forward_only_workspace_bytes(const regt_dims* dims, const regt_graph* graph);
 size_t regt_forward_only_packed_workspace_bytes(const regt_dims* dims, const regt_graph* graph, int32_t x_rows, int32_t x_is_bf16);
 

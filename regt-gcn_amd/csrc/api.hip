@@ -33,6 +33,33 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+// ---- per-device launch state (kernels.h) ----------------------------------------------------------------------------
+struct GraphStream { hipStream_t s = nullptr; hipEvent_t in = nullptr, out = nullptr; };
+struct DeviceState {
+    std::atomic<int> cus{0};
+    GraphStream graph;        // capture / replay stream of run_maybe_graphed and its event pair (guarded by g_graph_stream_mu)
+};
+static DeviceState g_devices[MAX_DEVICES];
+
+int current_device() {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return dev;
+}
+int device_cus(int dev) {
+    const bool cached = (unsigned)dev < (unsigned)MAX_DEVICES;
+    int cus = cached ? g_devices[dev].cus.load(std::memory_order_relaxed) : 0;
+    if (cus > 0) return cus;
+    if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 256;
+    if (cached) g_devices[dev].cus.store(cus, std::memory_order_relaxed);
+    return cus;
+}
+// (a slow, host-synchronous driver call: want_dynamic_lds makes it once per kernel and device)
+int set_dynamic_lds(const void* kernel, int bytes) {
+    REGT_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return REGT_OK;
+}
+
 // ---- optional per-kernel timing with HIP events (bench.py roofline) ---------------------------------
 // When enabled, every pipeline stage is bracketed by two events recorded on the launch stream.
 struct ProfRec { const char* name; hipEvent_t e0, e1; };
@@ -63,7 +90,7 @@ struct ProfScope {
 // into a hipGraph the SECOND time the same set of buffers is seen (pointers are the cache key: a graph is only
 // ever replayed onto exactly the buffers it was captured with) and replayed from then on.
 // Capture cannot run on the legacy default stream PyTorch uses, so graphs are captured and replayed on a
-// library-owned stream that is ordered against the caller's stream with two events.
+// library-owned stream of the current device that is ordered against the caller's stream with two events.
 struct GraphEntry { hipGraphExec_t exec = nullptr; int seen = 0; };
 struct GraphCache {
     std::unordered_map<unsigned long long, GraphEntry> map;
@@ -71,8 +98,6 @@ struct GraphCache {
     long eager = 0, captured = 0, replayed = 0;
 };
 static GraphCache g_fwd_graphs, g_bwd_graphs;
-static hipStream_t g_graph_stream = nullptr;
-static hipEvent_t g_ev_in = nullptr, g_ev_out = nullptr;
 static const long GRAPH_MAX_ROWS = 1L << 15;   // N*T rows below which a step is launch-bound
 
 static unsigned long long hash_bytes(const void* p, size_t n, unsigned long long h) {
@@ -90,28 +115,31 @@ static bool graphs_wanted(long rows) {
 }
 
 // Runs `enqueue(stream)` either eagerly on `st` or as a cached graph replay ordered after / before `st`.
-static std::mutex g_graph_stream_mu;   // g_graph_stream / g_ev_in / g_ev_out are shared by the forward and backward caches
+static std::mutex g_graph_stream_mu;   // a device's GraphStream is shared by the forward and backward caches
 static int run_maybe_graphed(GraphCache& cache, unsigned long long key, hipStream_t st,
                              const std::function<int(hipStream_t)>& enqueue) {
     std::lock_guard<std::mutex> lk_stream(g_graph_stream_mu);
     std::lock_guard<std::mutex> lk(cache.mu);
-    const int gm = gemm_mode();            // a captured launch sequence is only valid for the arithmetic it was captured with
-    key = hash_bytes(&gm, sizeof(gm), key);
+    // a captured launch sequence is only valid for the arithmetic and on the device it was captured with
+    const int gm_dev[2] = {gemm_mode(), current_device()};
+    key = hash_bytes(gm_dev, sizeof(gm_dev), key);
+    if ((unsigned)gm_dev[1] >= (unsigned)MAX_DEVICES) { ++cache.eager; return enqueue(st); }
+    GraphStream& gs = g_devices[gm_dev[1]].graph;
     GraphEntry& e = cache.map[key];
     if (!e.exec) {
-        if (e.seen++ == 0 || cache.map.size() > 256) {   // first sighting (also sets kernel attributes), or buffers
-            ++cache.eager;                               // keep changing: plain launches
+        if (e.seen++ == 0 || cache.map.size() > 256) {   // first sighting (the plain launches also raise the kernels' LDS limits
+            ++cache.eager;                               // on this device), or buffers keep changing: plain launches
             return enqueue(st);
         }
-        if (!g_graph_stream) {
-            REGT_CHECK_HIP(hipStreamCreateWithFlags(&g_graph_stream, hipStreamNonBlocking));
-            REGT_CHECK_HIP(hipEventCreateWithFlags(&g_ev_in, hipEventDisableTiming));
-            REGT_CHECK_HIP(hipEventCreateWithFlags(&g_ev_out, hipEventDisableTiming));
+        if (!gs.s) {
+            REGT_CHECK_HIP(hipStreamCreateWithFlags(&gs.s, hipStreamNonBlocking));
+            REGT_CHECK_HIP(hipEventCreateWithFlags(&gs.in, hipEventDisableTiming));
+            REGT_CHECK_HIP(hipEventCreateWithFlags(&gs.out, hipEventDisableTiming));
         }
         hipGraph_t graph = nullptr;
-        REGT_CHECK_HIP(hipStreamBeginCapture(g_graph_stream, hipStreamCaptureModeRelaxed));
-        const int rc = enqueue(g_graph_stream);
-        const hipError_t ce = hipStreamEndCapture(g_graph_stream, &graph);
+        REGT_CHECK_HIP(hipStreamBeginCapture(gs.s, hipStreamCaptureModeRelaxed));
+        const int rc = enqueue(gs.s);
+        const hipError_t ce = hipStreamEndCapture(gs.s, &graph);
         if (rc != REGT_OK || ce != hipSuccess || !graph) {
             if (graph) (void)hipGraphDestroy(graph);
             (void)hipGetLastError();
@@ -124,11 +152,11 @@ static int run_maybe_graphed(GraphCache& cache, unsigned long long key, hipStrea
         ++cache.captured;
     }
     ++cache.replayed;
-    REGT_CHECK_HIP(hipEventRecord(g_ev_in, st));
-    REGT_CHECK_HIP(hipStreamWaitEvent(g_graph_stream, g_ev_in, 0));
-    REGT_CHECK_HIP(hipGraphLaunch(e.exec, g_graph_stream));
-    REGT_CHECK_HIP(hipEventRecord(g_ev_out, g_graph_stream));
-    REGT_CHECK_HIP(hipStreamWaitEvent(st, g_ev_out, 0));
+    REGT_CHECK_HIP(hipEventRecord(gs.in, st));
+    REGT_CHECK_HIP(hipStreamWaitEvent(gs.s, gs.in, 0));
+    REGT_CHECK_HIP(hipGraphLaunch(e.exec, gs.s));
+    REGT_CHECK_HIP(hipEventRecord(gs.out, gs.s));
+    REGT_CHECK_HIP(hipStreamWaitEvent(st, gs.out, 0));
     return REGT_OK;
 }
 
@@ -769,8 +797,8 @@ static hipStream_t side_fork(hipStream_t st) {       // returns the stream to la
     if (t_call_flags & REGT_DIMS_NO_SIDE_STREAM) return st;
     if (!option(OPT_SIDE_STREAM) || option(OPT_HIPGRAPH) > 0) return st;        // REGT_SIDE_STREAM=0; never inside a captured graph
     std::lock_guard<std::mutex> lk(g_side_mu);
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return st; }
+    const int dev = current_device();
+    if (dev < 0) return st;
     const auto key = std::make_pair(dev, st);
     auto it = g_sides.find(key);
     if (it == g_sides.end()) {
@@ -792,8 +820,8 @@ static hipStream_t side_fork(hipStream_t st) {       // returns the stream to la
 }
 static int side_join(hipStream_t st) {
     std::lock_guard<std::mutex> lk(g_side_mu);
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return REGT_OK; }
+    const int dev = current_device();
+    if (dev < 0) return REGT_OK;
     auto it = g_sides.find(std::make_pair(dev, st));
     if (it == g_sides.end() || !it->second.forked) return REGT_OK;
     SideStream& ss = it->second;
@@ -807,9 +835,8 @@ static int side_join(hipStream_t st) {
 static void side_resync(hipStream_t st) {
     {
         std::lock_guard<std::mutex> lk(g_side_mu);
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return; }
-        if (g_sides.find(std::make_pair(dev, st)) == g_sides.end()) return;
+        const int dev = current_device();
+        if (dev < 0 || g_sides.find(std::make_pair(dev, st)) == g_sides.end()) return;
     }
     (void)side_fork(st);
 }

@@ -183,8 +183,6 @@ __global__ __launch_bounds__(512, 2) void embed_fp32_kernel(EmbedArgs a) {
 
 }  // namespace
 
-int fused_cus();
-
 // (small problems keep the general core and its 64 x 64 tiles: a persistent kernel of 128-row tiles needs a few tiles per CU)
 bool embed_fp32_ok(long M, int C, int F, int T) { return C == EM_C && F == EM_F && M >= 512L * EM_ROWS && T > 0; }
 
@@ -192,10 +190,10 @@ int launch_embed_fp32(const float* X, const float* LX, const float* A0, const fl
                       float* out, long M, int T, int act, float slope, hipStream_t st) {
     REGT_CHECK_ARG(act == ACT_NONE || act == ACT_LRELU || act == ACT_RELU, "embedding kernel: activation %d not covered", act);
     EmbedArgs a{X, LX, A0, Aall, node_region, bias, out, M, T, act == ACT_NONE ? 1.0f : (act == ACT_LRELU ? slope : 0.0f)};
-    static bool attr_done = false;
-    if (const int rc = set_lds_once(&embed_fp32_kernel, EM_LDS, &attr_done)) return rc;
+    const int dev = current_device();
+    if (const int rc = want_dynamic_lds<&embed_fp32_kernel>(EM_LDS, dev)) return rc;
     const long tiles = (M + EM_ROWS - 1) / EM_ROWS;
-    const long cus = fused_cus();
+    const long cus = device_cus(dev);
     hipLaunchKernelGGL(embed_fp32_kernel, dim3((unsigned)(tiles < cus ? tiles : cus)), dim3(512), EM_LDS, st, a);
     REGT_CHECK_LAUNCH();
     return REGT_OK;

@@ -491,15 +491,6 @@ __global__ __launch_bounds__(256, 2) void fused_fwd_kernel(FusedFwdArgs a) {
 #undef FT_FINE
 }
 
-int fused_cus() {
-    static int cus = 0;
-    if (cus <= 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 static long* g_fused_trace = nullptr;
 static long g_fused_trace_n = 0;
 // REGT_FUSED_TRACE = 1: stamps of the forward kernel, 2: of the backward kernel (8 per tile); nullptr when tracing is off
@@ -862,12 +853,9 @@ int launch_fused_backward(const FusedBwdArgs& a_, int C, hipStream_t st) {
     const long tiles = (a.M + FT_ROWS - 1) / FT_ROWS;
     REGT_CHECK_ARG(tiles < (1L << 31) && a.M < (1L << 31), "fused backward: too many rows");
     using L = FusedBwdLds<256>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_bwd_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
-        attr_done = true;
-    }
-    const long slots = 2L * fused_cus();                        // persistent: two workgroups per CU
+    const int dev = current_device();
+    if (int rc = want_dynamic_lds<&fused_bwd_kernel<256>>(L::BYTES, dev)) return rc;
+    const long slots = 2L * device_cus(dev);                       // persistent: two workgroups per CU
     if (a.tile_ctr) REGT_CHECK_HIP(hipMemsetAsync(a.tile_ctr, 0, sizeof(unsigned), st));
     hipLaunchKernelGGL((fused_bwd_kernel<256>), dim3((unsigned)(tiles < slots ? tiles : slots)), dim3(256), L::BYTES, st, a);
     REGT_CHECK_LAUNCH();
@@ -897,25 +885,16 @@ int launch_fused_forward(const FusedFwdArgs& a_, int C, int F, hipStream_t st, b
     const long tiles = (a.M + FT_ROWS - 1) / FT_ROWS;
     REGT_CHECK_ARG(tiles < (1L << 31), "fused forward: too many tiles");
     using L = FusedFwdLds<256, 64>;              // (the LDS footprint does not depend on F)
-    static bool attr_done = false;
-    if (!attr_done) {
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<256, 64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<256, 32, true>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<256, 64, false>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
-        REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_kernel<256, 32, false>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES));
-        attr_done = true;
-    }
     // persistent: two workgroups per CU (what LDS and registers admit), each walks its tiles with a stride of the grid
-    const long slots = 2L * fused_cus();
+    const int dev = current_device();
+    const long slots = 2L * device_cus(dev);
     const unsigned grid = (unsigned)(tiles < slots ? tiles : slots);
     if (a.tile_ctr) REGT_CHECK_HIP(hipMemsetAsync(a.tile_ctr, 0, sizeof(unsigned), st));
-    if (save) {
-        if (F == 64) hipLaunchKernelGGL((fused_fwd_kernel<256, 64, true>), dim3(grid), dim3(256), L::BYTES, st, a);
-        else hipLaunchKernelGGL((fused_fwd_kernel<256, 32, true>), dim3(grid), dim3(256), L::BYTES, st, a);
-    } else {
-        if (F == 64) hipLaunchKernelGGL((fused_fwd_kernel<256, 64, false>), dim3(grid), dim3(256), L::BYTES, st, a);
-        else hipLaunchKernelGGL((fused_fwd_kernel<256, 32, false>), dim3(grid), dim3(256), L::BYTES, st, a);
-    }
+#define LAUNCH_(F_, S_) do { if (int rc = want_dynamic_lds<&fused_fwd_kernel<256, F_, S_>>(L::BYTES, dev)) return rc; \
+                             hipLaunchKernelGGL((fused_fwd_kernel<256, F_, S_>), dim3(grid), dim3(256), L::BYTES, st, a); } while (0)
+    if (save) { if (F == 64) LAUNCH_(64, true); else LAUNCH_(32, true); }
+    else { if (F == 64) LAUNCH_(64, false); else LAUNCH_(32, false); }
+#undef LAUNCH_
     REGT_CHECK_LAUNCH();
     return REGT_OK;
 }

@@ -559,7 +559,6 @@ __global__ __launch_bounds__(64 * NW, 2) void fused_fwd_rows_kernel(FusedFwdArgs
 }
 
 long* fused_trace_buffer(int which, long tiles);
-int fused_cus();
 
 bool fused_forward_rows_ok(int C, int F, int T) { return C == FR_C && (F == 64 || F == 32) && T <= 16; }
 
@@ -588,19 +587,13 @@ int launch_fused_forward_rows(const FusedFwdArgs& a_, int C, int F, int waves, h
         }
         a.wbase = base;
     }
-    static bool attr_done = false;
-    if (!attr_done) {
-#define ATTR_(F_, NW_, S_) REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_fwd_rows_kernel<F_, NW_, S_>), hipFuncAttributeMaxDynamicSharedMemorySize, FusedRowsLds<NW_>::BYTES))
-        ATTR_(64, 8, true); ATTR_(32, 8, true); ATTR_(64, 4, true); ATTR_(32, 4, true);
-        ATTR_(64, 8, false); ATTR_(32, 8, false); ATTR_(64, 4, false); ATTR_(32, 4, false);
-#undef ATTR_
-        attr_done = true;
-    }
     // persistent: 8 waves per CU (one workgroup of eight or two of four)
-    const long slots = (long)fused_cus() * (8 / nw);
+    const int dev = current_device();
+    const long slots = (long)device_cus(dev) * (8 / nw);
     const unsigned grid = (unsigned)(tiles < slots ? tiles : slots);
     if (a.tile_ctr) REGT_CHECK_HIP(hipMemsetAsync(a.tile_ctr, 0, sizeof(unsigned), st));
-#define LAUNCH_(F_, NW_, S_) hipLaunchKernelGGL((fused_fwd_rows_kernel<F_, NW_, S_>), dim3(grid), dim3(64 * NW_), FusedRowsLds<NW_>::BYTES, st, a)
+#define LAUNCH_(F_, NW_, S_) do { if (int rc = want_dynamic_lds<&fused_fwd_rows_kernel<F_, NW_, S_>>(FusedRowsLds<NW_>::BYTES, dev)) return rc; \
+                                  hipLaunchKernelGGL((fused_fwd_rows_kernel<F_, NW_, S_>), dim3(grid), dim3(64 * NW_), FusedRowsLds<NW_>::BYTES, st, a); } while (0)
     if (save) {
         if (nw == 8) { if (F == 64) LAUNCH_(64, 8, true); else LAUNCH_(32, 8, true); }
         else { if (F == 64) LAUNCH_(64, 4, true); else LAUNCH_(32, 4, true); }

@@ -1001,8 +1001,7 @@ template <class EpiF, class Core>
 static int launch_fast_core(const GemmSegs& S, long M, int N, EpiF f, int relu, hipStream_t st) {
     long tiles = (long)cdiv(M, GBM) * cdiv(N, GBN);
     REGT_CHECK_ARG(tiles < (1L << 31), "gemm: too many tiles");
-    static bool attr_done = false;
-    if (int rc = set_lds_once(&gemm_flat_fast_kernel<EpiF, Core>, G_FAST_LDS_BYTES, &attr_done)) return rc;
+    if (int rc = want_dynamic_lds<&gemm_flat_fast_kernel<EpiF, Core>>(G_FAST_LDS_BYTES)) return rc;
     hipLaunchKernelGGL((gemm_flat_fast_kernel<EpiF, Core>), dim3((unsigned)tiles), dim3(256), G_FAST_LDS_BYTES, st, S, M, N, f,
                        relu);
     REGT_CHECK_LAUNCH();
@@ -1057,8 +1056,7 @@ static int launch_flat(const GemmSegs& S, long M, int N, EpiF f, bool vec, hipSt
         REGT_CHECK_ARG(!(S.seg[q].flags & SEG_A_BF16), "gemm: a bf16-stored operand needs the bf16-operand vector path");
     long tiles = (long)cdiv(M, GBM) * cdiv(N, GBN);
     REGT_CHECK_ARG(tiles < (1L << 31), "gemm: too many tiles");
-    static bool attr_done = false;
-    if (int rc = set_lds_once(&gemm_flat_kernel<EpiF>, G_LDS_BYTES, &attr_done)) return rc;
+    if (int rc = want_dynamic_lds<&gemm_flat_kernel<EpiF>>(G_LDS_BYTES)) return rc;
     hipLaunchKernelGGL(gemm_flat_kernel<EpiF>, dim3((unsigned)tiles), dim3(256), G_LDS_BYTES, st, S, M, N, f, vec ? 1 : 0);
     REGT_CHECK_LAUNCH();
     return REGT_OK;
@@ -1629,12 +1627,11 @@ __global__ __launch_bounds__(256, 3) void gemm_cand_split8_kernel(CandArgs a, in
 // `save` = false: the forward-only kernels (H~ not stored, a.Ht ignored); the choice of core is the same either way
 template <class Core>
 static int launch_cand_flat(const CandArgs& a, bool save, unsigned grid, int lds_bytes, hipStream_t st) {
-    static bool attr_done[2] = {false, false};
     if (save) {
-        if (int rc = set_lds_once(&gemm_cand_flat_kernel<Core, true>, lds_bytes, &attr_done[1])) return rc;
+        if (int rc = want_dynamic_lds<&gemm_cand_flat_kernel<Core, true>>(lds_bytes)) return rc;
         hipLaunchKernelGGL((gemm_cand_flat_kernel<Core, true>), dim3(grid), dim3(256), lds_bytes, st, a);
     } else {
-        if (int rc = set_lds_once(&gemm_cand_flat_kernel<Core, false>, lds_bytes, &attr_done[0])) return rc;
+        if (int rc = want_dynamic_lds<&gemm_cand_flat_kernel<Core, false>>(lds_bytes)) return rc;
         hipLaunchKernelGGL((gemm_cand_flat_kernel<Core, false>), dim3(grid), dim3(256), lds_bytes, st, a);
     }
     return REGT_OK;
@@ -1669,13 +1666,12 @@ int launch_gemm_candidate(const CandArgs& a, hipStream_t st, bool save) {
         } else if (gemm_mode() == 2 && a.act_bf16) {
             for (int q = 0; q < a.S.nseg; ++q)
                 REGT_CHECK_ARG(!(a.S.seg[q].flags & SEG_B_FRAG), "candidate gemm: fragment-order weights need the three-workgroup kernel");
-            static bool attr_done8 = false, attr_done8f = false;
             REGT_CHECK_ARG(a.C % 8 == 0, "candidate gemm: bf16 storage needs C %% 8 == 0");
             if (save) {
-                if (int rc = set_lds_once(&gemm_cand_flat8_kernel<true>, G_FAST_LDS_BYTES, &attr_done8)) return rc;
+                if (int rc = want_dynamic_lds<&gemm_cand_flat8_kernel<true>>(G_FAST_LDS_BYTES)) return rc;
                 hipLaunchKernelGGL(gemm_cand_flat8_kernel<true>, dim3((unsigned)ftiles), dim3(256), G_FAST_LDS_BYTES, st, a);
             } else {
-                if (int rc = set_lds_once(&gemm_cand_flat8_kernel<false>, G_FAST_LDS_BYTES, &attr_done8f)) return rc;
+                if (int rc = want_dynamic_lds<&gemm_cand_flat8_kernel<false>>(G_FAST_LDS_BYTES)) return rc;
                 hipLaunchKernelGGL(gemm_cand_flat8_kernel<false>, dim3((unsigned)ftiles), dim3(256), G_FAST_LDS_BYTES, st, a);
             }
         } else if (gemm_mode() == 2) {
@@ -1689,12 +1685,11 @@ int launch_gemm_candidate(const CandArgs& a, hipStream_t st, bool save) {
     } else {
         for (int q = 0; q < a.S.nseg; ++q)
             REGT_CHECK_ARG(!(a.S.seg[q].flags & SEG_A_BF16), "candidate gemm: a bf16-stored operand needs the bf16-operand vector path");
-        static bool attr_done2 = false, attr_done2f = false;
         if (save) {
-            if (int rc = set_lds_once(&gemm_cand_kernel<true>, G_LDS_BYTES, &attr_done2)) return rc;
+            if (int rc = want_dynamic_lds<&gemm_cand_kernel<true>>(G_LDS_BYTES)) return rc;
             hipLaunchKernelGGL(gemm_cand_kernel<true>, dim3((unsigned)tiles), dim3(256), G_LDS_BYTES, st, a);
         } else {
-            if (int rc = set_lds_once(&gemm_cand_kernel<false>, G_LDS_BYTES, &attr_done2f)) return rc;
+            if (int rc = want_dynamic_lds<&gemm_cand_kernel<false>>(G_LDS_BYTES)) return rc;
             hipLaunchKernelGGL(gemm_cand_kernel<false>, dim3((unsigned)tiles), dim3(256), G_LDS_BYTES, st, a);
         }
     }

@@ -363,8 +363,6 @@ ScLayout sc_layout(const GruDims& s) {
     return L;
 }
 
-bool g_fwd_lds_set = false;
-
 }  // namespace
 
 void gru_sizes(const GruDims& s, size_t* ws_floats, size_t* scratch_floats) {
@@ -396,7 +394,7 @@ int launch_gru_fwd(const GruDims& s, const float* x, const float* w_ih, const fl
     a.gates = s.training ? ws + L.gates : nullptr;
     constexpr int bytes = FWD_LDS_FLOATS * 4;
     static_assert(bytes <= 160 * 1024, "forward LDS");
-    if (int rc = set_lds_once(gru_fwd_kernel, bytes, &g_fwd_lds_set)) return rc;
+    if (int rc = want_dynamic_lds<&gru_fwd_kernel>(bytes)) return rc;
     hipLaunchKernelGGL(gru_fwd_kernel, dim3(cdiv(s.rows, RT)), dim3(THREADS), bytes, st, a);
     REGT_CHECK_LAUNCH();
     return REGT_OK;

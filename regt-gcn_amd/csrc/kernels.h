@@ -1,6 +1,8 @@
 // Internal C++ launcher interface of the regtgcn HIP library (not exported; see include/regtgcn.h
 // for the C ABI).  Every launcher enqueues on the given stream and returns REGT_OK / error code.
 #pragma once
+#include <atomic>
+
 #include "gemm_core.h"
 #include "options.h"
 
@@ -385,13 +387,24 @@ int launch_relu_mask(const float* y, float* d, long n, hipStream_t st);      // 
 int launch_gru_bwd(const GruDims& s, const float* x, const float* w_hh, const float* dout, const float* dh_last, float* const* grads,
                    float* dh0, const float* ws, float* scratch, hipStream_t st);
 
-// hipFuncSetAttribute is a (slow, host-synchronous) driver call: do it once per kernel, not per launch.
-template <class K>
-static int set_lds_once(K kernel, int bytes, bool* done) {
-    if (*done) return REGT_OK;
-    REGT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    *done = true;
+// ---- per-device launch state ------------------------------------------------------------------------------------
+// What a launcher needs to know about the device it is about to launch on is keyed by the device's ordinal, never by the process.
+// A launcher that needs both helpers asks for the ordinal once and passes it on.
+constexpr int MAX_DEVICES = 64;                 // ordinals the caches cover; past them every call asks the runtime
+int current_device();                           // the ordinal current on the calling thread, -1 when no device answers
+int device_cus(int dev = current_device());     // its CU count; 256 (an MI355X) when no device answers: sizes are computed on CPU-only hosts, too
+int set_dynamic_lds(const void* kernel, int bytes);
+// Raises the kernel's dynamic-LDS limit on the current device (= dev) the first time the instantiation is launched there.  Two
+// threads racing on that first launch both raise it (harmless); the bit is only set once the limit stands.
+template <auto Kernel>
+int want_dynamic_lds(int bytes, int dev = current_device()) {
+    static std::atomic<unsigned long long> done{0};
+    const unsigned long long bit = (unsigned)dev < (unsigned)MAX_DEVICES ? 1ull << dev : 0;
+    if (done.load(std::memory_order_acquire) & bit) return REGT_OK;
+    if (int rc = set_dynamic_lds(reinterpret_cast<const void*>(Kernel), bytes)) return rc;
+    done.fetch_or(bit, std::memory_order_release);
     return REGT_OK;
 }
+static_assert(MAX_DEVICES <= 64, "want_dynamic_lds keeps one bit per ordinal");
 
 }  // namespace regt

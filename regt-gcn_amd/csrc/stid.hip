@@ -404,8 +404,6 @@ __global__ void stid_reduce_kernel(const float* __restrict__ slab, int G, int P,
     }
 }
 
-bool g_fwd_lds_set = false, g_bwd_lds_set = false;
-
 int hidden(const StidDims& s) { return s.embed_dim + (s.if_node ? s.node_dim : 0); }
 long param_floats(const StidDims& s) {
     const int hd = hidden(s);
@@ -441,7 +439,7 @@ int launch_stid_fwd(const StidDims& s, const float* x, const float* const* P, co
     a.lds_layers = min(a.NL, (LDS_BYTES / 4 - fixed) / per_layer);
     const int bytes = (fixed + a.lds_layers * per_layer) * 4;
     if (bytes > 64 * 1024)
-        if (int rc = set_lds_once(stid_fwd_kernel, LDS_BYTES, &g_fwd_lds_set)) return rc;
+        if (int rc = want_dynamic_lds<&stid_fwd_kernel>(LDS_BYTES)) return rc;
     hipLaunchKernelGGL(stid_fwd_kernel, dim3(min(a.ntiles, STID_MAX_WGS)), dim3(THREADS), bytes, st, a);
     REGT_CHECK_LAUNCH();
     return REGT_OK;
@@ -460,7 +458,7 @@ int launch_stid_bwd(const StidDims& s, const float* x, const float* const* P, co
     a.lds_layers = min(a.NL, (LDS_BYTES / 4 - fixed) / per_layer);
     const int bytes = (fixed + a.lds_layers * per_layer) * 4;
     if (bytes > 64 * 1024)
-        if (int rc = set_lds_once(stid_bwd_kernel, LDS_BYTES, &g_bwd_lds_set)) return rc;
+        if (int rc = want_dynamic_lds<&stid_bwd_kernel>(LDS_BYTES)) return rc;
     hipLaunchKernelGGL(stid_bwd_kernel, dim3(grid), dim3(THREADS), bytes, st, a);
     REGT_CHECK_LAUNCH();
     Segs sg{};

@@ -754,13 +754,11 @@ void add_seg(Segs& sg, float* p, int size) {
     ++sg.n;
 }
 
-// LDS rows of the head / start-conv backward grow with out_dim / in_dim: past 64 KB the kernel's limit is raised, once, to what
-// ST_MAX_CH needs (hipFuncSetAttribute is a slow, host-synchronous call)
+// LDS rows of the head / start-conv backward grow with out_dim / in_dim: past 64 KB the kernel's limit is raised to what ST_MAX_CH needs
 constexpr int HEAD_LDS_MAX = WV * (ST_MAX_CH + 3 * SC + 1) * (int)sizeof(float);
 constexpr int START_LDS_MAX = WV * (SC + ST_MAX_CH + 1) * (int)sizeof(float);
 static_assert(HEAD_LDS_MAX <= 160 * 1024 && START_LDS_MAX <= 160 * 1024, "LDS rows exceed the CU's 160 KB");
 static_assert(WV * (2 * 3 * SC + 5 * SC + 1) * (int)sizeof(float) <= 64 * 1024, "st_layer_bwd rows exceed 64 KB");
-bool g_head_lds_set = false, g_start_lds_set = false;
 
 template <bool TN, bool SN>
 int layer_fwd_nz(const LayerFwdArgs& a, bool last, hipStream_t st) {
@@ -855,7 +853,7 @@ int launch_stnorm_bwd(const StnDims& s, const float* x, const float* const* P, f
         h.stride = O + 3 * SC + 1;
         const int bytes = WV * h.stride * (int)sizeof(float);
         if (bytes > 64 * 1024)
-            if (int rc = set_lds_once(st_head_bwd, HEAD_LDS_MAX, &g_head_lds_set)) return rc;
+            if (int rc = want_dynamic_lds<&st_head_bwd>(HEAD_LDS_MAX)) return rc;
         hipLaunchKernelGGL(st_head_bwd, dim3(d.nw), dim3(WV), bytes, st, h);
         REGT_CHECK_LAUNCH();
         Segs sg{};
@@ -937,7 +935,7 @@ int launch_stnorm_bwd(const StnDims& s, const float* x, const float* const* P, f
     sb.stride = SC + d.Cin + 1;
     const int bytes = WV * sb.stride * (int)sizeof(float);
     if (bytes > 64 * 1024)
-        if (int rc = set_lds_once(st_start_bwd, START_LDS_MAX, &g_start_lds_set)) return rc;
+        if (int rc = want_dynamic_lds<&st_start_bwd>(START_LDS_MAX)) return rc;
     hipLaunchKernelGGL(st_start_bwd, dim3(d.nw), dim3(WV), bytes, st, sb);
     REGT_CHECK_LAUNCH();
     Segs sg{};

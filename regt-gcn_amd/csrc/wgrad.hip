@@ -15,6 +15,21 @@ static int wgrad_ring_depth() { return option(OPT_WGRAD_RING); }
 static int wgrad_tile_rows() { return option(OPT_WGRAD_TILE); }       // 128 | 256 (default) output rows per tile of the ring kernel
 bool wgrad_ring_active() { return wgrad_ring_depth() > 0; }
 
+// One wave of workgroups: `nch` chunks of kc = roundup32(ceil(M / nch)) rows.  Chunks shorter than `min_rows` are refused (small problems
+// keep many short chunks: the latency-bound regime); chunks past 32768 rows (the kernels' 32-bit row offsets) become whole waves of
+// shorter ones.  false: not applicable, *kchunk / *nchunks keep the caller's chunking.
+static bool wave_chunks(long nch, long M, long min_rows, int* kchunk, int* nchunks) {
+    if (nch < 1) return false;
+    long kc = ((M + nch - 1) / nch + 31) / 32 * 32;
+    if (kc < min_rows) return false;
+    if (kc > 32768) {
+        const long waves = (kc + 32767) / 32768;
+        kc = ((M + nch * waves - 1) / (nch * waves) + 31) / 32 * 32;
+    }
+    *kchunk = (int)kc;
+    *nchunks = (int)((M + kc - 1) / kc);
+    return true;
+}
 // Row chunking for a ring-kernel launch whose workgroups are ALL resident at once and fill every slot: chunks x tiles = CUs x
 // workgroups per CU.  The tiles of a chunk share their operands through L2 only while they walk the chunk in step; started
 // together they do, started as slots free up (1.5 waves of workgroups at 128 chunks x 6 tiles) they do not, and the half-filled
@@ -26,89 +41,36 @@ bool wgrad_ring_active() { return wgrad_ring_depth() > 0; }
 // (profiles/r04_wgrad_wave32_ab.txt; two waves mean more slabs to reduce: slower).
 bool wgrad_wide_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks) {
     if (gemm_mode() == 2 || fp32_core_wide() || Nin <= 32) return false;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
     const int per_cu = gemm_mode() == 1 ? 2 : 3;
     const long tpc = (long)cdiv(Nout, 128) * cdiv(Nin, 128);
-    long nch = (long)cus * per_cu / tpc;       // one wave of workgroups
-    if (nch < 1) return false;
-    long kc = ((M + nch - 1) / nch + 31) / 32 * 32;
-    if (kc < 512) return false;
-    if (kc > 32768) {
-        const long waves = (kc + 32767) / 32768;
-        kc = ((M + nch * waves - 1) / (nch * waves) + 31) / 32 * 32;
-    }
-    *kchunk = (int)kc;
-    *nchunks = (int)((M + kc - 1) / kc);
-    return true;
+    return wave_chunks((long)device_cus() * per_cu / tpc, M, 512, kchunk, nchunks);
 }
 // Skinny gradients (Nin <= 32: wgrad_kernel<32>, HBM-bound on their left operand): chunks x row tiles = two
 // workgroups per CU, all resident at once -- at cfg-3 the layout's 507 chunks are 1.3 (dGh) / 2.6 (dGzr) waves of workgroups.
 bool wgrad_skinny_chunking(int Nout, long M, int* kchunk, int* nchunks) {
     constexpr int per_cu = 2;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
-    const long nch = (long)cus * per_cu / cdiv(Nout, 128);
-    if (nch < 1) return false;
-    long kc = ((M + nch - 1) / nch + 31) / 32 * 32;
-    if (kc < 512) return false;
-    if (kc > 32768) {
-        const long waves = (kc + 32767) / 32768;
-        kc = ((M + nch * waves - 1) / (nch * waves) + 31) / 32 * 32;
-    }
-    *kchunk = (int)kc;
-    *nchunks = (int)((M + kc - 1) / kc);
-    return true;
+    return wave_chunks((long)device_cus() * per_cu / cdiv(Nout, 128), M, 512, kchunk, nchunks);
 }
 bool wgrad_ring_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks) {
     if (!wgrad_ring_active() || !option(OPT_WGRAD_WAVE)) return false;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
     const bool wide = wgrad_tile_rows() == 256 && Nout % 256 == 0;
     const int per_cu = wide || wgrad_ring_depth() >= 8 ? 2 : 3;           // register-limited workgroups per CU of the variant launched
     const long tpc = (long)cdiv(Nout, wide ? 256 : 128) * cdiv(Nin, 128);
-    const long nch = (long)cus * per_cu / tpc;
-    if (nch < 1) return false;
-    long kc = ((M + nch - 1) / nch + 31) / 32 * 32;
-    if (kc < 512) return false;                                            // small problems: many short chunks (latency-bound regime)
-    if (kc > 32768) {                                                      // the kernels' 32-bit row offsets: whole waves of shorter chunks
-        const long waves = (kc + 32767) / 32768;
-        kc = ((M + nch * waves - 1) / (nch * waves) + 31) / 32 * 32;
-    }
-    *kchunk = (int)kc;
-    *nchunks = (int)((M + kc - 1) / kc);
-    return true;
+    return wave_chunks((long)device_cus() * per_cu / tpc, M, 512, kchunk, nchunks);
 }
 // Upper bound of the row chunks ANY of the three per-launch chunkers above can return for a (Nout x Nin) gradient over M rows, whatever
 // the arithmetic / switches at launch time: make_layout sizes the slab regions with it (the layout's own ~128 / ~512 chunks were too few
-// once the launches started to pick their counts: C = 128 in fp32 asks for 768 chunks of dUh).
+// once the launches started to pick their counts: C = 128 in fp32 asks for 768 chunks of dUh).  The same rule over the three largest
+// budgets, with no chunk refused (32 rows is what the rounding gives any M > 0).
 long wgrad_chunk_bound(int Nout, int Nin, long M) {
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    const int skinny = 2, wave32 = 1;
-    const long cand[3] = {(long)cus * 3 * wave32 / ((long)cdiv(Nout, 128) * cdiv(Nin, 128)),      // wide fp32 / bf16x3, ring (128-row tiles)
-                          (long)cus * skinny / cdiv(Nout, 128),                                   // skinny
-                          (long)cus * 3 / ((long)cdiv(Nout, 256) > 0 ? (long)cdiv(Nout, 256) * cdiv(Nin, 128) : 1)};
-    long best = 0;
+    const long cus = device_cus();
+    const long cand[3] = {cus * 3 / ((long)cdiv(Nout, 128) * cdiv(Nin, 128)),      // wide fp32 / bf16x3, ring (128-row tiles)
+                          cus * 2 / cdiv(Nout, 128),                               // skinny
+                          cus * 3 / ((long)cdiv(Nout, 256) * cdiv(Nin, 128))};     // ring (256-row tiles)
+    int best = 0;
     for (long nch : cand) {
-        if (nch < 1) continue;
-        long kc = ((M + nch - 1) / nch + 31) / 32 * 32;
-        if (kc > 32768) {
-            const long waves = (kc + 32767) / 32768;
-            kc = ((M + nch * waves - 1) / (nch * waves) + 31) / 32 * 32;
-        }
-        if (kc < 32) kc = 32;
-        const long n = (M + kc - 1) / kc;
-        best = n > best ? n : best;
+        int kc = 0, n = 0;
+        if (wave_chunks(nch, M, 32, &kc, &n) && n > best) best = n;
     }
     return best;
 }
@@ -1168,6 +1130,12 @@ int launch_wgrad(const WgradArgs& a, hipStream_t st) {
     am.all_csum = a.colsum && a.p_bf16 && a.q_bf16;     // (fp32 kernels: measured no gain, +0.02 ms on the MFMA-bound wgrad3_kernel)
     return launch_wgrad_impl(am, st);
 }
+template <auto Kernel>       // a ring-kernel instantiation: `bytes` of dynamic LDS, raised past the 48 KB any kernel may ask for
+static int launch_ring(const WgradArgs& a, long nblocks, size_t bytes, hipStream_t st) {
+    if (bytes > 48 * 1024) { if (int rc = want_dynamic_lds<Kernel>((int)bytes)) return rc; }
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)nblocks), dim3(256), bytes, st, a);
+    return REGT_OK;
+}
 static int launch_wgrad_impl(const WgradArgs& a, hipStream_t st) {
     REGT_CHECK_ARG(a.Nout > 0 && a.Nin > 0 && a.nchunks > 0, "wgrad: empty problem");
     // a two-part right-hand side runs on the skinny fp32 kernel, except under the bf16 arithmetic with Nin <= 128 (one
@@ -1191,9 +1159,8 @@ static int launch_wgrad_impl(const WgradArgs& a, hipStream_t st) {
     REGT_CHECK_ARG(!a.Q2 || fast, "wgrad: a second right-hand operand needs 16-byte tileable operands and nin_split %% 32 == 0");
     REGT_CHECK_ARG(!(a.p_bf16 || a.q_bf16) || fast, "wgrad: bf16 operands need the vector kernels");
     if (wide) {
-        static bool attr_done = false, attr_done_g = false, attr_done_s = false;
         if (fast && gemm_mode() == 1) {
-            if (int rc = set_lds_once(&wgrad_split_kernel<3>, 4 * 3 * WS_PLANE_B, &attr_done_s)) return rc;
+            if (int rc = want_dynamic_lds<&wgrad_split_kernel<3>>(4 * 3 * WS_PLANE_B)) return rc;
             hipLaunchKernelGGL(wgrad_split_kernel<3>, dim3((unsigned)blocks), dim3(256), 4 * 3 * WS_PLANE_B, st, a);
         } else if (fast && gemm_mode() == 2) {
             REGT_CHECK_ARG(!(a.p_bf16 || a.q_bf16) || (a.Nout % 8 == 0 && a.Nin % 8 == 0 && a.ldp % 8 == 0 && a.ldq % 8 == 0 && !a.q_relu),
@@ -1204,25 +1171,18 @@ static int launch_wgrad_impl(const WgradArgs& a, hipStream_t st) {
             const long ld_max = std::max(a.ldp, std::max(a.ldq, a.Q2 ? a.ldq2 : 0L));
             const long rows_max = a.chunk_tab ? a.M : (long)a.kchunk + 32;
             const bool ring_ok = a.p_bf16 && a.q_bf16 && ring > 0 && (!a.Q2 || a.nin_split % 128 == 0) && 2 * rows_max * ld_max < (1L << 31);
-            auto launch_ring = [&](auto kernel, long nblocks, size_t need) -> int {
-                static bool attr_done_r = false;
-                const size_t bytes = need;
-                if (bytes > 48 * 1024) { if (int rc = set_lds_once(kernel, (int)bytes, &attr_done_r)) return rc; }
-                hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3(256), bytes, st, a);
-                return REGT_OK;
-            };
             // 256-row tiles where the output has them (regt_set_option("wgrad_tile", 128 | 256)); ring of 2 there
             // ("wgrad_ring256" = 2 | 4; 6 half slabs of three 16-byte loads spill).  Two beats four, 0.585 + 0.350
             // against 0.63 + 0.383 ms at the cfg-5 shard: what is in flight (workgroups x slots x 12 KB per XCD) competes with the lines
             // the chunk's other tiles are about to ask for in the 4 MiB L2, and the tile that comes second finds its rows there anyway
             if (ring_ok && wgrad_tile_rows() == 256 && a.Nout % 256 == 0) {
                 const long blocks4 = (long)(a.Nout / 256) * cdiv(a.Nin, 128) * a.nchunks;
-                if (option(OPT_WGRAD_RING256) == 2) { if (int rc = launch_ring(&wgrad_bf16_ring_kernel<2, 4>, blocks4, 2 * 3 * WS_PLANE_B)) return rc; }
-                else if (int rc = launch_ring(&wgrad_bf16_ring_kernel<4, 4>, blocks4, 2 * 3 * WS_PLANE_B)) return rc;
+                if (option(OPT_WGRAD_RING256) == 2) { if (int rc = launch_ring<&wgrad_bf16_ring_kernel<2, 4>>(a, blocks4, 2 * 3 * WS_PLANE_B, st)) return rc; }
+                else if (int rc = launch_ring<&wgrad_bf16_ring_kernel<4, 4>>(a, blocks4, 2 * 3 * WS_PLANE_B, st)) return rc;
             }
-            else if (ring_ok && ring >= 8) { if (int rc = launch_ring(&wgrad_bf16_ring_kernel<8, 2>, blocks, lb)) return rc; }
-            else if (ring_ok && ring >= 6) { if (int rc = launch_ring(&wgrad_bf16_ring_kernel<6, 2>, blocks, lb)) return rc; }
-            else if (ring_ok) { if (int rc = launch_ring(&wgrad_bf16_ring_kernel<4, 2>, blocks, lb)) return rc; }
+            else if (ring_ok && ring >= 8) { if (int rc = launch_ring<&wgrad_bf16_ring_kernel<8, 2>>(a, blocks, lb, st)) return rc; }
+            else if (ring_ok && ring >= 6) { if (int rc = launch_ring<&wgrad_bf16_ring_kernel<6, 2>>(a, blocks, lb, st)) return rc; }
+            else if (ring_ok) { if (int rc = launch_ring<&wgrad_bf16_ring_kernel<4, 2>>(a, blocks, lb, st)) return rc; }
             else if (a.p_bf16 && a.q_bf16) hipLaunchKernelGGL((wgrad_split_kernel<1, true, true>), dim3((unsigned)blocks), dim3(256), lb, st, a);
             else if (a.p_bf16) hipLaunchKernelGGL((wgrad_split_kernel<1, true, false>), dim3((unsigned)blocks), dim3(256), lb, st, a);
             else if (a.q_bf16) hipLaunchKernelGGL((wgrad_split_kernel<1, false, true>), dim3((unsigned)blocks), dim3(256), lb, st, a);
@@ -1232,18 +1192,17 @@ static int launch_wgrad_impl(const WgradArgs& a, hipStream_t st) {
             hipLaunchKernelGGL(wgrad3_kernel, dim3((unsigned)blocks), dim3(256), 4 * 16 * 132 * 4, st, a);
         } else if (fast) {
             REGT_CHECK_ARG(!(a.p_bf16 || a.q_bf16), "wgrad: bf16-stored operands with the fp32 wide kernel");
-            if (int rc = set_lds_once(&wgrad_kernel<128>, (int)lds, &attr_done)) return rc;
+            if (int rc = want_dynamic_lds<&wgrad_kernel<128>>((int)lds)) return rc;
             hipLaunchKernelGGL(wgrad_kernel<128>, dim3((unsigned)blocks), dim3(256), lds, st, a);
         } else {
-            if (int rc = set_lds_once(&wgrad_kernel_generic<128>, (int)lds, &attr_done_g)) return rc;
+            if (int rc = want_dynamic_lds<&wgrad_kernel_generic<128>>((int)lds)) return rc;
             hipLaunchKernelGGL(wgrad_kernel_generic<128>, dim3((unsigned)blocks), dim3(256), lds, st, a);
         }
     } else if (fast) {
         REGT_CHECK_ARG(!a.q_bf16 && (!a.p_bf16 || (a.Nout % 8 == 0 && a.ldp % 8 == 0)), "wgrad: skinny kernel takes a bf16-stored P only");
         if (a.p_bf16) hipLaunchKernelGGL((wgrad_kernel<32, true>), dim3((unsigned)blocks), dim3(256), lds, st, a);
         else if (mid) {
-            static bool attr_done_m = false;
-            if (int rc = set_lds_once(&wgrad_kernel<64>, (int)lds, &attr_done_m)) return rc;      // 51 200 B of dynamic LDS
+            if (int rc = want_dynamic_lds<&wgrad_kernel<64>>((int)lds)) return rc;      // 51 200 B of dynamic LDS
             hipLaunchKernelGGL(wgrad_kernel<64>, dim3((unsigned)blocks), dim3(256), lds, st, a);
         }
         else hipLaunchKernelGGL(wgrad_kernel<32>, dim3((unsigned)blocks), dim3(256), lds, st, a);

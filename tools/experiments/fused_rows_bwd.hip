@@ -379,7 +379,6 @@ __global__ __launch_bounds__(512, 2) void fused_bwd_rows_kernel(FusedRowsBwdArgs
 }
 
 long* fused_trace_buffer(int which, long tiles);
-int fused_cus();
 
 bool fused_backward_rows_ok(int C, int T) { return C == FB_C && T > 0; }
 
@@ -406,9 +405,9 @@ int launch_fused_backward_rows(const FusedBwdArgs& a_, int C, hipStream_t st) {
         aa.wbase = base;
     }
     using L = FusedRowsBwdLds;
-    static bool attr_done = false;
-    if (const int rc = set_lds_once(&fused_bwd_rows_kernel, L::BYTES, &attr_done)) return rc;
-    const long slots = fused_cus();
+    const int dev = current_device();
+    if (const int rc = want_dynamic_lds<&fused_bwd_rows_kernel>(L::BYTES, dev)) return rc;
+    const long slots = device_cus(dev);
     const unsigned grid = (unsigned)(tiles < slots ? tiles : slots);
     if (aa.b.tile_ctr) REGT_CHECK_HIP(hipMemsetAsync(aa.b.tile_ctr, 0, sizeof(unsigned), st));
     hipLaunchKernelGGL(fused_bwd_rows_kernel, dim3(grid), dim3(512), L::BYTES, st, aa);
