@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import check_grads_against_golden, load_npz
+from grad_bars import assert_grads_to_scale
 from oracle import graph_ops as G
 from oracle import model as M
 
@@ -82,6 +83,7 @@ def test_convstack_matches_oracle_on_directed_synthetic_graph(R, collapse):
             continue
         want = po[k].grad
         np.testing.assert_allclose(q.grad.cpu().numpy(), want.numpy(), atol=TOL * max(1.0, float(want.abs().max())), rtol=1e-4, err_msg=k)
+    assert_grads_to_scale({k: q.grad for k, q in mod.named_parameters()}, {k: v.grad for k, v in po.items()}, what="directed synthetic graph")
 
 
 @pytest.mark.parametrize("n,e,width", [(300, 2500, 6144), (5000, 40000, 3072), (64, 200, 2052)])

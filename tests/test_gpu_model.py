@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, check_grads_against_golden, load_npz, region_lists
+from grad_bars import assert_grads_to_scale
 from oracle import model as M
 
 pytestmark = pytest.mark.gpu
@@ -45,6 +46,13 @@ def _oracle_once(key, fn):
     if key not in _ORACLE_CACHE:
         _ORACLE_CACHE[key] = fn()
     return _ORACLE_CACHE[key]
+
+
+def _grads_of(model):
+    """name -> gradient (None where there is none) of a module or of the oracle's parameter dict: what grad_bars compares.  The
+    fp32 oracle lies within 5e-6 of its float64 run relative to every block's scale, far below the bars."""
+    named = model.named_parameters() if hasattr(model, "named_parameters") else model.items()
+    return {k: (None if q.grad is None else q.grad.detach().cpu()) for k, q in named}
 
 
 def _run_regt(R, params, x, y, fx, num_regions=5):
@@ -167,6 +175,7 @@ def test_regt_matches_oracle_on_synthetic_regional_graph(R, arith, n, e, regions
             assert q.grad is None
             continue
         np.testing.assert_allclose(q.grad.cpu().numpy(), po[k].grad.numpy(), atol=TOL, rtol=1e-4, err_msg=k)
+    assert_grads_to_scale(_grads_of(mod), _grads_of(po), what="synthetic regional graph")
 
 
 @pytest.mark.parametrize("n,e,regions,f,t,o", [(900, 6000, 5, 8, 6, 1), (3000, 30000, 3, 32, 12, 2)])
@@ -204,6 +213,7 @@ def test_overlapping_random_decomposition_matches_oracle(R, arith, n, e, regions
         if k in M.UNUSED_PARAMS:
             continue
         np.testing.assert_allclose(q.grad.cpu().numpy(), po[k].grad.numpy(), atol=TOL, rtol=1e-4, err_msg=k)
+    assert_grads_to_scale(_grads_of(mod), _grads_of(po), what="overlapping random decomposition")
 
 
 def test_forward_is_deterministic_and_graph_is_cached(R, tpims):
@@ -271,6 +281,7 @@ def test_hidden_gradient_path(R, tpims):
         if k in M.UNUSED_PARAMS:
             continue
         np.testing.assert_allclose(q.grad.cpu().numpy(), po[k].grad.numpy(), atol=2e-5, rtol=1e-4, err_msg=k)
+    assert_grads_to_scale(_grads_of(mod), _grads_of(po), what="hidden gradient path")
 
 
 def test_region_sharded_path_matches_single_gpu(R):
@@ -392,6 +403,7 @@ def test_other_hidden_widths_match_oracle(R, hidden, mode):
         if k in M.UNUSED_PARAMS:
             continue
         np.testing.assert_allclose(q.grad.cpu().numpy(), po[k].grad.numpy(), atol=TOL, rtol=1e-4, err_msg=k)
+    assert_grads_to_scale(_grads_of(mod), _grads_of(po), what=f"hidden width {hidden}")
 
 
 @pytest.mark.parametrize("model_name", ["RegionalTemporalGCN", "TemporalGCN"])

@@ -5,6 +5,7 @@ import pytest
 import torch
 from hypothesis import given, settings, strategies as st
 
+from grad_bars import assert_grads_to_scale
 from oracle import model as M
 
 pytestmark = pytest.mark.gpu
@@ -45,3 +46,4 @@ def test_arbitrary_small_shapes_match_oracle(R, n, t, f, o, regions, hidden, mod
         if k in M.UNUSED_PARAMS:
             continue
         np.testing.assert_allclose(q.grad.cpu().numpy(), po[k].grad.numpy(), atol=TOL, rtol=1e-4, err_msg=k)
+    assert_grads_to_scale({k: q.grad for k, q in mod.named_parameters()}, {k: v.grad for k, v in po.items()}, what=f"property shape n={n} t={t} f={f} o={o} regions={regions} hidden={hidden} mode={mode}")

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, check_grads_against_golden, load_npz, region_lists
+from grad_bars import assert_grads_to_scale
 from oracle import model as M
 
 pytestmark = pytest.mark.gpu
@@ -104,3 +105,4 @@ def test_split_matches_oracle_on_synthetic_regional_graph(split_mode):
         if k in M.UNUSED_PARAMS:
             continue
         np.testing.assert_allclose(q.grad.cpu().numpy(), po[k].grad.numpy(), atol=TOL, rtol=1e-4, err_msg=k)
+    assert_grads_to_scale({k: q.grad for k, q in mod.named_parameters()}, {k: v.grad for k, v in po.items()}, what="bf16x3 split, synthetic regional graph")

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import check_grads_against_golden, load_npz
+from grad_bars import assert_grads_to_scale
 from oracle import graph_ops as G
 from oracle import model as M
 
@@ -134,6 +135,7 @@ def test_zero_hidden_models_match_oracle_on_synthetic_graphs(R, name, n, e, f, t
             assert q.grad is None, k
             continue
         np.testing.assert_allclose(q.grad.cpu().numpy(), po[k].grad.numpy(), atol=TOL, rtol=1e-4, err_msg=k)
+    assert_grads_to_scale({k: q.grad for k, q in mod.named_parameters()}, {k: v.grad for k, v in po.items()}, what=name)
 
 
 @pytest.mark.parametrize("name", ["GraphSAGETemporalGCN", "GATTemporal"])
