@@ -73,7 +73,10 @@ struct OpBlocks {
     int nblk, E;
 };
 
-// Each lane owns entries lane, lane + 64, ... of the wave's slab row and adds rows [0, nvalid) of the staged LDS rows, in order.
+// Each lane owns entries lane, lane + 64, ... of the wave's slab row and adds rows [0, nvalid) of the staged LDS rows in a fixed
+// order: four interleaved partial sums over the rows, combined pairwise, then added to the entry.  One running sum through every
+// row of every column instead is a chain of B * L * 64 additions, and where a normalisation's 1 / sqrt(var + eps) makes the
+// terms large and cancelling (start_conv.bias under left padding) its rounding grows with that length.
 __device__ void op_accumulate(const float* rows, int stride, int nvalid, const OpBlocks& ob, float* slab_row) {
     const int lane = threadIdx.x;
     for (int e = lane; e < ob.E; e += WV) {
@@ -82,9 +85,16 @@ __device__ void op_accumulate(const float* rows, int stride, int nvalid, const O
         const int loc = e - base, i = loc / ob.nb[k], j = loc - (loc / ob.nb[k]) * ob.nb[k];
         const float* pa = rows + ob.a[k] + i;
         const float* pb = rows + ob.b[k] + j;
-        float s = slab_row[e];
-        for (int r = 0; r < nvalid; ++r) s = fmaf(pa[r * stride], pb[r * stride], s);
-        slab_row[e] = s;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        int r = 0;
+        for (; r + 4 <= nvalid; r += 4) {
+            s0 = fmaf(pa[r * stride], pb[r * stride], s0);
+            s1 = fmaf(pa[(r + 1) * stride], pb[(r + 1) * stride], s1);
+            s2 = fmaf(pa[(r + 2) * stride], pb[(r + 2) * stride], s2);
+            s3 = fmaf(pa[(r + 3) * stride], pb[(r + 3) * stride], s3);
+        }
+        for (; r < nvalid; ++r) s0 = fmaf(pa[r * stride], pb[r * stride], s0);
+        slab_row[e] += (s0 + s1) + (s2 + s3);
     }
 }
 

@@ -41,8 +41,9 @@ def tnorm(x, gamma, beta, rm, rv, training, group):
 
 
 def snorm(x, gamma, beta):
+    """gamma, beta (C,); a (B, C) tensor gives every batch element its own copy (tests that take one element's share of a gradient)."""
     xn = (x - x.mean(2, keepdim=True)) / (x.var(2, keepdim=True, unbiased=True) + EPS) ** 0.5
-    return xn * gamma.view(1, -1, 1, 1) + beta.view(1, -1, 1, 1)
+    return xn * gamma.view(-1, gamma.shape[-1], 1, 1) + beta.view(-1, beta.shape[-1], 1, 1)
 
 
 def stnorm(p, x, blocks=4, layers=2, tnorm_bool=True, snorm_bool=True, training=True, tnorm_group=None, dtype=torch.float64):

@@ -1,6 +1,10 @@
 """SpatialGCN on the HIP path: the reference module's goldens (eval, and train with the recorded dropout masks), the fused first-layer
 kernel pair against a float64 restatement on awkward graphs, reproducibility, the drawn dropout mask, snapshot batching, the cfg-3
-shape, and the train / evaluate command lines."""
+shape, and the train / evaluate command lines.
+
+Next to every gradient comparison stands grad_bars.assert_grads_conditioned: every block (gcn.lins.0 and gcn.lins.1 by 16-feature
+accumulator) against the float64 restatement -- for the goldens, which store only summaries of the large gradients, the one
+full reference -- at a bar relative to the block's OWN scale; no block of these cases is ill-conditioned."""
 import os
 import time
 
@@ -9,11 +13,14 @@ import pytest
 import torch
 
 from conftest import GOLDEN, check_grads_against_golden, load_npz
+from grad_bars import REL, assert_grads_conditioned
 from oracle import graph_ops as G
-from spatial_math import unpack_keep
+from spatial_math import spatial_gcn, unpack_keep
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
+K_GAP = 4                     # what an ill-conditioned block's fp32 gap is multiplied by: the summation-order allowance of the
+                              # STNorm and STID tests (torch sums pairwise; the kernels add tiles, waves and chunks in sequence)
 
 
 @pytest.fixture(scope="module")
@@ -26,6 +33,23 @@ def R():
 def _golden(tag):
     g = load_npz(f"golden_spatial_{tag}.npz")
     return g, {str(k): torch.from_numpy(g[f"p__{k}"]) for k in g["state_dict_keys"]}
+
+
+def golden_case(tpims, tag, mode):
+    """The float64 and fp32 restatement gradients of the golden's step (its parameters, window, recorded keep mask and loss).  The
+    goldens keep only summaries of the large gradients: the float64 restatement is the one full reference."""
+    g, params = _golden(tag)
+    t_in, t_out, w0 = int(g["t_in"]), int(g["t_out"]), int(g["window"])
+    x = tpims["node_data"][:, :, w0:w0 + t_in].contiguous()
+    y = tpims["node_data"][:, -1, w0 + t_in:w0 + t_in + t_out].contiguous()
+    keep = g["train__keep"] if mode == "train" else None
+    out = []
+    for dtype in (torch.float64, torch.float32):
+        p = {k: v.to(dtype).requires_grad_(True) for k, v in params.items()}
+        pred, _hidden = spatial_gcn(p, x, tpims["edge_index"], tpims["edge_attr"], keep, dtype=dtype)
+        torch.mean((pred - y.to(dtype)) ** 2).backward()
+        out.append({k: v.grad for k, v in p.items()})
+    return out
 
 
 @pytest.mark.parametrize("mode", ["eval", "train"])
@@ -54,6 +78,9 @@ def test_spatial_matches_reference_goldens(R, tpims, tag, mode):
     assert abs(float(loss.detach()) - float(rec["loss"][0])) < TOL
     grads = {k: (None if q.grad is None else q.grad.cpu()) for k, q in mod.named_parameters()}
     check_grads_against_golden(rec, grads, atol=TOL, rtol=1e-4)
+    g64, g32 = golden_case(tpims, tag, mode)
+    ill, _ = assert_grads_conditioned(grads, g64, g32, K_GAP, REL, f"golden {tag} {mode}")
+    assert ill == []
 
 
 def _awkward_graph(R, n, e, seed):
@@ -65,22 +92,21 @@ def _awkward_graph(R, n, e, seed):
     return ei, ea
 
 
-def _embed_reference(x, ei, ea, w0, w1, b, keep, ds):
+def _embed_reference(x, ei, ea, w0, w1, b, keep, ds, dtype=torch.float64):
     """float64 S, (dW0, dW1, db), the absolute-value sums that bound their fp32 rounding, and the allowance for ReLU decisions that
     fp32 may take either way (|pre| within fp32 rounding of 0: the whole row term may or may not count), in the reference's order."""
     n, f, t = x.shape
-    x, w0, w1, b, ds = x.double(), w0.double(), w1.double(), b.double(), ds.double()
-    src, dst, w = G.cheb_norm_edges(ei, ea.double(), n, torch.float64)
-    km = None if keep is None else unpack_keep(keep.cpu().numpy(), n, t).double() * 2
-    s = torch.zeros(n, 64, dtype=torch.float64)
-    grads = [torch.zeros(64, f, dtype=torch.float64), torch.zeros(64, f, dtype=torch.float64), torch.zeros(64, dtype=torch.float64)]
-    bounds = [torch.zeros(64, f, dtype=torch.float64), torch.zeros(64, f, dtype=torch.float64), torch.zeros(64, dtype=torch.float64)]
-    allow = [torch.zeros(64, f, dtype=torch.float64), torch.zeros(64, f, dtype=torch.float64), torch.zeros(64, dtype=torch.float64)]
+    x, w0, w1, b, ds = x.to(dtype), w0.to(dtype), w1.to(dtype), b.to(dtype), ds.to(dtype)
+    src, dst, w = G.cheb_norm_edges(ei, ea.to(dtype), n, dtype)
+    km = None if keep is None else unpack_keep(keep.cpu().numpy(), n, t).to(dtype) * 2
+    zeros = lambda: [torch.zeros(64, f, dtype=dtype), torch.zeros(64, f, dtype=dtype), torch.zeros(64, dtype=dtype)]
+    s = torch.zeros(n, 64, dtype=dtype)
+    grads, bounds, allow = zeros(), zeros(), zeros()
     for p in range(t):
         xt = x[:, :, p]
         lxt = G.propagate(src, dst, w, xt, n)
         pre = xt @ w0.t() + lxt @ w1.t() + b
-        m = (pre > 0).double() if km is None else (pre > 0).double() * km[:, p, :]
+        m = (pre > 0).to(dtype) if km is None else (pre > 0).to(dtype) * km[:, p, :]
         s += torch.relu(pre) * (1.0 if km is None else km[:, p, :])
         dg = ds * m
         grads[0] += dg.t() @ xt
@@ -90,7 +116,7 @@ def _embed_reference(x, ei, ea, w0, w1, b, keep, ds):
         bounds[1] += dg.abs().t() @ lxt.abs()
         bounds[2] += dg.abs().sum(0)
         size = xt.abs() @ w0.abs().t() + lxt.abs() @ w1.abs().t() + b.abs()
-        amb = (pre.abs() <= 4e-6 * size).double() * (ds.abs() if km is None else ds.abs() * km[:, p, :])
+        amb = (pre.abs() <= 4e-6 * size).to(dtype) * (ds.abs() if km is None else ds.abs() * km[:, p, :])
         allow[0] += amb.t() @ xt.abs()
         allow[1] += amb.t() @ lxt.abs()
         allow[2] += amb.sum(0)
@@ -117,6 +143,17 @@ def _inputs(n, t, f, seed):
     return x, w0, w1, b, ds
 
 
+EMBED_NAMES = ("gcn.lins.0.weight", "gcn.lins.1.weight", "gcn.bias")            # what the kernel pair's dW0, dW1, db are gradients of
+
+
+def embed_case(x, ei, ea, w0, w1, b, keep, ds):
+    """(float64 reference of _check, {name: float64 gradient}, {name: fp32 restatement gradient}, {name: ReLU allowance}): the
+    restatement runs once per arithmetic and serves both assertions."""
+    ref = _embed_reference(x, ei, ea, w0, w1, b, keep, ds)
+    g32 = _embed_reference(x, ei, ea, w0, w1, b, keep, ds, dtype=torch.float32)[1]
+    return ref, dict(zip(EMBED_NAMES, ref[1])), dict(zip(EMBED_NAMES, g32)), dict(zip(EMBED_NAMES, ref[3]))
+
+
 def _check(s, grads, s_ref, g_ref, bounds, allow):
     scale = max(1.0, float(s_ref.abs().max()))
     assert float((s.cpu().double() - s_ref).abs().max()) < TOL * scale
@@ -125,14 +162,31 @@ def _check(s, grads, s_ref, g_ref, bounds, allow):
         assert bool((err <= TOL * bnd + alw + 1e-6).all()), (name, float(err.max()), float(bnd.max()))
 
 
-@pytest.mark.parametrize("masked", [False, True], ids=["eval", "train"])
-@pytest.mark.parametrize("n,t,f", [(40, 1, 4), (300, 12, 32), (1000, 6, 8), (257, 13, 64)])
-def test_kernel_pair_matches_restatement(R, n, t, f, masked):
+def _check_to_scale(grads, g64, g32, allow, what):
+    """Every block of dW0, dW1, db within its own scale of float64; an element whose ReLU decision fp32 may take either way
+    (`allow`, from the float64 pre-activations alone) keeps the allowance _check gives it."""
+    got = dict(zip(EMBED_NAMES, (g.cpu() for g in grads)))
+    return assert_grads_conditioned(got, g64, g32, K_GAP, REL, what, allow=allow)
+
+
+KERNEL_PAIR_SHAPES = [(40, 1, 4), (300, 12, 32), (1000, 6, 8), (257, 13, 64)]
+
+
+def kernel_pair_inputs(R, n, t, f):
     ei, ea = _awkward_graph(R, n, 6 * n, seed=n + t)
-    x, w0, w1, b, ds = _inputs(n, t, f, seed=7 * n + f)
+    return (ei, ea) + _inputs(n, t, f, seed=7 * n + f)
+
+
+@pytest.mark.parametrize("masked", [False, True], ids=["eval", "train"])
+@pytest.mark.parametrize("n,t,f", KERNEL_PAIR_SHAPES)
+def test_kernel_pair_matches_restatement(R, n, t, f, masked):
+    ei, ea, x, w0, w1, b, ds = kernel_pair_inputs(R, n, t, f)
     keep = R.nn.draw_keep_mask(n * t, "cuda") if masked else None
     s, grads = _embed_gpu(R, x, ei, ea, w0, w1, b, keep, ds)
-    _check(s, grads, *_embed_reference(x, ei, ea, w0, w1, b, keep, ds))
+    ref, g64, g32, allow = embed_case(x, ei, ea, w0, w1, b, keep, ds)
+    _check(s, grads, *ref)
+    ill, _ = _check_to_scale(grads, g64, g32, allow, f"n {n} t {t} f {f} masked {masked}")
+    assert ill == []
 
 
 def test_forward_backward_bit_identical(R):
@@ -192,7 +246,10 @@ def test_cfg3_shape_matches_restatement(R):
     x, w0, w1, b, ds = _inputs(n, t, f, seed=32)
     keep = R.nn.draw_keep_mask(n * t, "cuda")
     s, grads = _embed_gpu(R, x, g.edge_index, g.edge_attr, w0, w1, b, keep, ds)
-    _check(s, grads, *_embed_reference(x, g.edge_index, g.edge_attr, w0, w1, b, keep, ds))
+    ref, g64, g32, allow = embed_case(x, g.edge_index, g.edge_attr, w0, w1, b, keep, ds)
+    _check(s, grads, *ref)
+    ill, _ = _check_to_scale(grads, g64, g32, allow, "cfg-3 shape")
+    assert ill == []
     assert time.time() - t0 < 120
 
 

@@ -8,7 +8,12 @@ fp32-vs-float64 gap of the restatement on the goldens, tests/test_stid_cpu.py) a
 After the RMSprop step: the bound of test_three_window_trajectory_matches_reference_golden.  Against the float64 restatement:
 1e-5 + K_GAP x the fp32-vs-float64 gap of the same restatement evaluated in fp32 on the same inputs, per tensor, with
 K_GAP = 4 as for STNorm: torch sums in pairwise blocks, the kernels add a tile's 64 nodes in sequence on the matrix unit, then a
-workgroup's tiles in sequence, then the workgroups in sequence."""
+workgroup's tiles in sequence, then the workgroups in sequence.
+
+Next to every one of these gradient comparisons stands grad_bars.assert_grads_conditioned: every block (node_emb by 64-node
+tile, the ragged last tile on its own; the embedding weight by input step; the 64 x 64 weights by wave quadrant) against the
+float64 restatement at a bar relative to the block's OWN scale; no block of these cases is ill-conditioned.  The restatements
+run once per case on the host and serve both assertions."""
 import os
 import subprocess
 import sys
@@ -18,7 +23,8 @@ import pytest
 import torch
 
 from conftest import load_npz
-from stid_math import stid, unpack_keep
+from grad_bars import REL, assert_grads_conditioned
+from stid_math import pack_keep, stid, unpack_keep
 from test_stid_cpu import GRAD_GAP
 
 pytestmark = pytest.mark.gpu
@@ -49,6 +55,28 @@ def _close(a, b, atol=1e-5, rtol=0.0, what=""):
     np.testing.assert_allclose(a, b, atol=atol, rtol=rtol, err_msg=what)
 
 
+def _restated_grads(params, x, input_dim, keep, loss, dtype):
+    """({name: gradient}, output) of the restatement in `dtype`; `loss(out)` -> scalar."""
+    p = {k: v.detach().to(dtype).requires_grad_(True) for k, v in params.items()}
+    out = stid(p, x, input_dim, keep=keep, dtype=dtype)
+    loss(out).backward()
+    return {k: v.grad for k, v in p.items()}, out.detach()
+
+
+def golden_case(tag):
+    """The float64 and fp32 restatement gradients of the golden's training step (its parameters, input, keep mask and loss)."""
+    g, keys = _golden(tag)
+    params = {k: torch.from_numpy(g[f"p__{k}"]) for k in keys}
+    x, y, keep = torch.from_numpy(g["x"]), torch.from_numpy(g["y"]), unpack_keep(torch.from_numpy(g["train__keep"]))
+    g64, _ = _restated_grads(params, x, 3, keep, lambda o: torch.mean((o - y.double()) ** 2), torch.float64)
+    g32, _ = _restated_grads(params, x, 3, keep, lambda o: torch.mean((o - y) ** 2), torch.float32)
+    return g64, g32
+
+
+def _hip_grads(mod):
+    return {k: (None if p.grad is None else p.grad.detach().cpu()) for k, p in mod.named_parameters()}
+
+
 @pytest.mark.parametrize("tag", TAGS)
 def test_train_mode_matches_reference_golden(tag):
     g, keys = _golden(tag)
@@ -62,6 +90,9 @@ def test_train_mode_matches_reference_golden(tag):
     for k, p in mod.named_parameters():
         assert p.grad is not None, k
         _close(p.grad, g[f"train__g__{k}"], atol=1e-5 + GRAD_GAP, what=k)
+    g64, g32 = golden_case(tag)
+    ill, _ = assert_grads_conditioned(_hip_grads(mod), g64, g32, K_GAP, REL, f"golden {tag}", input_dim=3)
+    assert ill == []
 
 
 @pytest.mark.parametrize("tag", TAGS)
@@ -130,31 +161,60 @@ def _random_biases(mod, seed):
                 p.copy_((torch.rand(p.shape, generator=gen) - 0.5) * 0.4)
 
 
-def _against_restatement(n, b=1, l=6, c=8, d=3, o=1, nl=3, if_node=True, seed=0, training=True):
+def restatement_case(n, b=1, l=6, c=8, d=3, o=1, nl=3, if_node=True, seed=0, training=True):
+    """What the host alone computes of one comparison: the module with its parameters, the input, the keep mask, the loss weights,
+    and the restatement's output and gradients in float64 and in fp32 (computed once, shared by every assertion)."""
     import regtgcn_amd as R
     torch.manual_seed(seed)
     mod = R.STID(num_nodes=n, input_len=l, output_len=o, input_dim=d, num_layer=nl, if_node=if_node, **OFF)
     _random_biases(mod, seed)
-    ref = {k: v.detach().clone().double().requires_grad_(True) for k, v in mod.state_dict().items()}
+    sd = {k: v.detach().clone() for k, v in mod.state_dict().items()}
     x = torch.randn(b, l, n, c, generator=torch.Generator().manual_seed(seed + 1))
     keep = (torch.rand(nl, b, n, mod.hidden_dim, generator=torch.Generator().manual_seed(seed + 3)) < 0.85) if training else None
-    mod = mod.to(DEV).train(training)
-    from stid_math import pack_keep
-    out = mod(x.to(DEV), keep=None if keep is None else pack_keep(keep).to(DEV))
-    w = torch.randn(out.shape, generator=torch.Generator().manual_seed(seed + 2))
-    (out * w.to(DEV)).sum().backward()
-    ro = stid(ref, x, d, keep=keep)
-    (ro * w.double()).sum().backward()
+    w = torch.randn(b, o, n, 1, generator=torch.Generator().manual_seed(seed + 2))
+    g64, ro = _restated_grads(sd, x, d, keep, lambda out: (out * w.double()).sum(), torch.float64)
     # the same restatement in fp32 gives the per-tensor gap of the bound (module docstring)
-    r32 = {k: v.detach().float().requires_grad_(True) for k, v in ref.items()}
-    o32 = stid(r32, x, d, keep=keep, dtype=torch.float32)
-    (o32 * w).sum().backward()
+    g32, o32 = _restated_grads(sd, x, d, keep, lambda out: (out * w).sum(), torch.float32)
+    return dict(mod=mod, x=x, keep=keep, w=w, ro=ro, o32=o32, g64=g64, g32=g32, input_dim=d)
+
+
+def _against_restatement(n, b=1, l=6, c=8, d=3, o=1, nl=3, if_node=True, seed=0, training=True, ill_share=0.0):
+    case = restatement_case(n, b, l, c, d, o, nl, if_node, seed, training)
+    x, keep, w, ro, o32, g64, g32 = (case[k] for k in ("x", "keep", "w", "ro", "o32", "g64", "g32"))
+    mod = case["mod"].to(DEV).train(training)
+    out = mod(x.to(DEV), keep=None if keep is None else pack_keep(keep).to(DEV))
+    (out * w.to(DEV)).sum().backward()
     assert tuple(out.shape) == (b, o, n, 1) == tuple(ro.shape)
-    _close(out, ro.detach(), atol=1e-5 + K_GAP * float((o32.detach().double() - ro.detach()).abs().max()), what="out")
+    _close(out, ro, atol=1e-5 + K_GAP * float((o32.double() - ro).abs().max()), what="out")
     for k, p in mod.named_parameters():
-        gap = float((r32[k].grad.double() - ref[k].grad).abs().max())
-        _close(p.grad, ref[k].grad, atol=1e-5 + K_GAP * gap, what=k)
+        gap = float((g32[k].double() - g64[k]).abs().max())
+        _close(p.grad, g64[k], atol=1e-5 + K_GAP * gap, what=k)
+    ill, nblocks = assert_grads_conditioned(_hip_grads(mod), g64, g32, K_GAP, REL, f"n {n} b {b} l {l} d {d} o {o} nl {nl} node {if_node}",
+                                            input_dim=d)
+    assert len(ill) <= ill_share * nblocks, ill
     return mod
+
+
+def _node_count_seed(n, b):
+    """30 + n + b, but for (1000, 3): under seed 1033 one fc1 pre-activation of the last layer lies within fp32 rounding of zero, the
+    fp32 restatement takes its ReLU the other way than float64 and 37 of the 62 gradient blocks move by up to 7e-3 of their scale
+    (tests/test_baseline_bars_cpu.py shows the ill-conditioned list): a comparison of two ReLU decisions, not of gradients."""
+    return 2033 if (n, b) == (1000, 3) else 30 + n + b
+
+
+# every comparison against the restatement that the tests below run (tests/test_baseline_bars_cpu.py proves the bars on them)
+RESTATEMENT_CASES = ([dict(n=104, b=2, l=l, seed=l) for l in (1, 3, 6, 12, 24)] +
+                     [dict(n=104, b=1, l=24 if d == 8 else 6, c=8, d=d, o=3, seed=10 + d) for d in (1, 3, 8)] +
+                     [dict(n=130, b=1, l=6, o=o, seed=20 + o) for o in (1, 3, 12, 64)] +
+                     [dict(n=n, b=b, l=12, o=3, seed=_node_count_seed(n, b)) for b in (1, 3) for n in (1, 2, TILE - 1, TILE + 1, 1000)] +
+                     [dict(n=200, b=2, l=6, o=2, nl=nl, seed=40 + nl) for nl in (1, 3, 8)] +
+                     [dict(n=150, b=2, l=6, o=33, nl=nl, if_node=False, seed=50 + nl) for nl in (1, 3, 8)] +
+                     [dict(n=300, b=3, l=12, o=3, seed=60, training=False)])
+CFG3_CASE = dict(n=100_000, b=1, l=12, c=8, d=3, o=1, seed=9)
+# Among the cfg-3 shape's 19 million fc1 pre-activations one lies within fp32 rounding of zero: the fp32 restatement takes that ReLU
+# the other way than float64, and the blocks it reaches (17 of 1609: one node_emb tile, the embedding and first-layer weights) are
+# ill-conditioned (tests/grad_bars.py), held to K_GAP x their fp32 gap.  Other seeds move the coin to the kernels' side instead.
+CFG3_ILL_SHARE = 0.05
 
 
 @pytest.mark.parametrize("l", [1, 3, 6, 12, 24])
@@ -175,7 +235,13 @@ def test_kernels_match_restatement_over_output_lengths(o):
 @pytest.mark.parametrize("n", [1, 2, TILE - 1, TILE + 1, 1000])
 @pytest.mark.parametrize("b", [1, 3])
 def test_small_and_ragged_node_counts(n, b):
-    _against_restatement(n, b=b, l=12, o=3, seed=30 + n + b)
+    _against_restatement(n, b=b, l=12, o=3, seed=_node_count_seed(n, b))
+
+
+def test_relu_within_rounding_of_zero_keeps_its_absolute_bar():
+    """Seed 1033 of the (1000, 3) case (see _node_count_seed): the fp32 restatement and float64 disagree on one ReLU.  The absolute
+    bars built on the fp32 gap hold as they did; the blocks that decision reaches are ill-conditioned and held to K_GAP x their gap."""
+    _against_restatement(1000, b=3, l=12, o=3, seed=1033, ill_share=1.0)
 
 
 @pytest.mark.parametrize("nl", [1, 3, 8])
@@ -262,17 +328,31 @@ def test_backward_is_bit_reproducible():
         assert torch.equal(a, b)
 
 
-def test_snapshot_batching_equals_sequential_calls():
-    """(B, T, N, F) == B sequential calls with B = 1 when both get the same keep bits: losses and accumulated gradients."""
+def snapshot_batching_case():
+    """The module, eight snapshots (N, F, T) with targets (N, O) and keep bits, and the restatement's accumulated gradients of
+    train_epoch_stid on them: the sum over the snapshots of each one's mean-squared loss."""
     import regtgcn_amd as R
-    from regtgcn_amd.nn import draw_stid_keep
-    from regtgcn_amd.train import WindowStore, train_epoch_stid
     torch.manual_seed(1)
     base = R.STID(num_nodes=104, input_len=6, output_len=2, **OFF)
     _random_biases(base, 1)
-    xs = [torch.randn(104, 8, 6, device=DEV) for _ in range(8)]
-    ys = [torch.randn(104, 2, device=DEV) for _ in range(8)]
-    keeps = draw_stid_keep(3, 8, 104, 64, DEV)
+    gen = torch.Generator().manual_seed(11)
+    xs = [torch.randn(104, 8, 6, generator=gen) for _ in range(8)]
+    ys = [torch.randn(104, 2, generator=gen) for _ in range(8)]
+    keep = torch.rand(3, 8, 104, 64, generator=gen) < 0.85
+    x, y = torch.stack(xs).permute(0, 3, 1, 2), torch.stack(ys)               # (8, T, N, F), (8, N, O)
+    loss = lambda out: ((out - y.to(out.dtype).unsqueeze(1)) ** 2).mean(dim=(1, 2, 3)).sum()
+    sd = {k: v.detach().clone() for k, v in base.state_dict().items()}
+    g64, _ = _restated_grads(sd, x, 3, keep, loss, torch.float64)
+    g32, _ = _restated_grads(sd, x, 3, keep, loss, torch.float32)
+    return base, xs, ys, pack_keep(keep), g64, g32
+
+
+def test_snapshot_batching_equals_sequential_calls():
+    """(B, T, N, F) == B sequential calls with B = 1 when both get the same keep bits: losses and accumulated gradients."""
+    import regtgcn_amd as R
+    from regtgcn_amd.train import WindowStore, train_epoch_stid
+    base, xs, ys, keeps, g64, g32 = snapshot_batching_case()
+    xs, ys, keeps = [x.to(DEV) for x in xs], [y.to(DEV) for y in ys], keeps.to(DEV)
     res = []
     for sb in (1, 4):
         mod = R.STID(num_nodes=104, input_len=6, output_len=2, **OFF)
@@ -292,11 +372,14 @@ def test_snapshot_batching_equals_sequential_calls():
     _close(res[0][0], res[1][0].cpu(), atol=1e-6, what="losses")
     for k in res[0][1]:
         _close(res[0][1][k], res[1][1][k].cpu(), atol=1e-5, what=k)
+    for sb, (_l, grads) in zip((1, 4), res):
+        ill, _ = assert_grads_conditioned(grads, g64, g32, K_GAP, REL, f"snapshot batch {sb}", input_dim=3)
+        assert ill == []
 
 
 def test_cfg3_shape_against_restatement():
     """The cfg-3 shape: N = 100 000 nodes, C = 8, L = 12, O = 1 (forward and gradients; the weight gradients sum 100 000 nodes)."""
-    _against_restatement(100_000, b=1, l=12, c=8, d=3, o=1, seed=9)
+    _against_restatement(**CFG3_CASE, ill_share=CFG3_ILL_SHARE)
 
 
 @pytest.mark.parametrize("t_out", [1, 3])
