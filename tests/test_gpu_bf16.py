@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import op_bars as B
 from fused_math import bf16_round, dense_ops, forward_fused
 from oracle import model as M
 from test_gpu_model import _synthetic
@@ -52,6 +53,8 @@ def test_bf16_linear_is_the_rounded_operand_product(bf16_mode, m, k, n, act):
     got = R.ops.linear(a.cuda(), w.cuda(), b.cuda(), act).cpu().double()
     # exactly the product of the bf16-rounded operands, accumulated in fp32
     assert float((got - ref(bf16_round(a), bf16_round(w))).abs().max()) < 2e-5
+    assert B.arithmetic_of(B.expected_kernel("linear", 2, (m, k, n))) == 2
+    assert B.linear_ratio(got, a, w, b, act, rounded=True) <= B.BAR["linear"]       # products of bf16 values are exact in fp32: the fp32 bar
     # and within the derived bound of the unrounded product: 2u * sum|a_k w_k|
     bound = 2.2 * BF16_U * (a.abs().double() @ w.abs().double().t()) + 1e-6
     assert bool(((got - ref(a, w)).abs() <= bound).all())
@@ -67,6 +70,8 @@ def test_bf16_wgrad_is_the_rounded_operand_product(bf16_mode, m, n, k):
     want = bf16_round(d).double().t() @ bf16_round(a).double()
     scale = float(want.abs().max())
     assert float((dw.cpu().double() - want).abs().max()) < 1e-5 * scale + 1e-4
+    assert B.arithmetic_of(B.expected_kernel("wgrad", 2, (m, n, k))) == 2
+    assert B.wgrad_ratio(dw.cpu(), d, a, rounded=True) <= B.BAR["wgrad"] and B.dbias_ratio(db.cpu(), d) <= B.BAR["wgrad_bias"]
     np.testing.assert_allclose(db.cpu().numpy(), d.sum(0).numpy(), rtol=1e-4, atol=1e-3)      # bias gradient stays fp32
 
 

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+import op_bars as B
 from conftest import region_lists
 from oracle import graph_ops as G
 
@@ -89,6 +90,7 @@ def test_spmm_matches_oracle(R, width):
     assert float((got - want).abs().max()) < 2e-6
     want64 = G.dense_gcn_operator(ei, w, n, torch.float64) @ x.double()
     assert float((got.double() - want64).abs().max()) < 5e-6
+    assert B.spmm_ratio(got, B.csr_reference(rp.cpu(), col.cpu(), val.cpu(), x)) <= B.BAR["spmm"]       # per element, from the CSR itself
 
 
 @pytest.mark.parametrize("width", [160, 192])      # 160: 128-byte panels; 192 (a multiple of 64 floats): 256-byte panels
@@ -105,6 +107,7 @@ def test_spmm_panel_variant_large_graph(R, width):
     assert float((got.double() - want).abs().max()) < 4e-6 * max(1.0, float(want.abs().max()) / 8)
     again = R.ops.spmm_csr(rp, col, val, x.cuda()).cpu()
     assert torch.equal(got, again)
+    assert B.spmm_ratio(got, B.csr_reference(rp.cpu(), col.cpu(), val.cpu(), x)) <= B.BAR["spmm"]
 
 
 def test_spmm_dual_matches_two_single_operator_passes(R):
@@ -116,6 +119,8 @@ def test_spmm_dual_matches_two_single_operator_passes(R):
     ya, yl = R.ops.spmm_dual(pg.m_rowptr, pg.m_col, pg.m_val_a, pg.m_val_l, x)
     assert float((ya - stacked[:n]).abs().max()) < 2e-6
     assert float((yl - stacked[n:]).abs().max()) < 2e-6
+    for y, val in ((ya, pg.m_val_a), (yl, pg.m_val_l)):        # and each against float64 from the merged CSR, per element
+        assert B.spmm_ratio(y, B.csr_reference(pg.m_rowptr, pg.m_col, val, x)) <= B.BAR["spmm"]
     # the merged pattern is the union: no more entries than the two operators together, at least as many as A_hat
     assert pg.nnz_gcn <= pg.m_col.numel() <= pg.nnz_gcn + pg.nnz_cheb
 
@@ -133,6 +138,7 @@ def test_spmm_empty_rows_and_hub(R):
     want[0] = (wt.double().view(-1, 1) * x[1:].double()).sum(0).float()
     assert float((got - want).abs().max()) < 1e-4      # 299-term fp32 sum in edge order
     assert float(got[1:].abs().max()) == 0.0
+    assert B.spmm_ratio(got, B.csr_reference(rp.cpu(), col.cpu(), val.cpu(), x)) <= B.BAR["spmm"]       # empty rows: exactly 0
 
 
 def test_pack_x(R):
@@ -155,6 +161,7 @@ def test_linear_matches_torch_fp32(R, m, k, n, act):
         want = torch.relu(want)
     # fp32 MFMA = k-ordered fp32 fma chain: error ~ 1e-7 * sum|a*w|
     assert float((got.double() - want).abs().max()) < 2e-5
+    assert B.linear_ratio(got, a, w, b, act) <= B.BAR["linear"]          # ... held per element
 
 
 @pytest.mark.parametrize("mode", [0, 1])
@@ -180,6 +187,7 @@ def test_linear_full_tiles_every_row_every_run(R, mode, act):
             assert float((got - want).abs().max()) < 2e-5
             if first is None:
                 first = got.clone()
+                assert B.linear_ratio(got, a, w, b, act, ref=(z, a.abs().double() @ w.abs().double().t() + b.abs().double())) <= B.BAR["linear"]
             else:
                 assert torch.equal(got, first)
     finally:
@@ -204,6 +212,7 @@ def test_wgrad_matches_torch(R, m, n, k):
     scale = max(1.0, m ** 0.5)
     assert float((dw.cpu().double() - want).abs().max()) < 3e-5 * scale
     assert float((db.cpu().double() - d.double().sum(0)).abs().max()) < 3e-5 * scale
+    assert B.wgrad_ratio(dw.cpu(), d, a) <= B.BAR["wgrad"] and B.dbias_ratio(db.cpu(), d) <= B.BAR["wgrad_bias"]     # per element
     dw2, db2 = R.ops.wgrad(d.cuda(), a.cuda())
     assert torch.equal(dw, dw2) and torch.equal(db, db2)   # slab reduction is deterministic
 

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, check_grads_against_golden, load_npz, region_lists
+import op_bars as B
 from grad_bars import assert_grads_to_scale
 from oracle import model as M
 
@@ -45,6 +46,7 @@ def test_split_linear_is_as_accurate_as_fp32_mfma(split_mode, m, k, n, act):
     err_fp32 = float((R.ops.linear(a.cuda(), w.cuda(), b.cuda(), act).cpu().double() - want).abs().max())
     lib.regt_set_gemm_mode(1)
     assert err_split < 2e-5                         # the bar of test_linear_matches_torch_fp32
+    assert B.linear_ratio(got, a, w, b, act) <= B.BAR["linear"]          # per element: a lost partial product is ~2^-16 of a product
     assert err_split <= 2.0 * err_fp32 + 1e-7       # and no worse than the fp32 matrix pipe itself
 
 
