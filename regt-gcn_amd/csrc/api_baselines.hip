@@ -1,0 +1,198 @@
+// Entry points of the four baselines with their argument checks: SpatialGCN, STNorm, STID, StackedGRU.
+#include "api_internal.h"
+
+using namespace regt;
+
+extern "C" {
+
+size_t regt_spatial_embed_slab_floats(int32_t N, int32_t T, int32_t F) { return T > 255 ? 0 : spatial_slab_floats(N, T, F); }
+
+static int spatial_check_dims(const char* what, int32_t N, int32_t T, int32_t F) {
+    REGT_CHECK_ARG(N >= 1, "%s: num_nodes must be >= 1, got %d", what, N);
+    REGT_CHECK_ARG(T >= 1 && T <= 255, "%s: periods must be in [1, 255], got %d", what, T);
+    REGT_CHECK_ARG(F >= 4 && F <= 64 && F % 4 == 0, "%s: num_features must be a multiple of 4 in [4, 64], got %d", what, F);
+    return REGT_OK;
+}
+
+int32_t regt_spatial_embed_forward(const float* x, const float* lx, const float* w0, const float* w1, const float* b, const uint32_t* keep,
+                                   int32_t N, int32_t T, int32_t F, float* s_out, regt_stream_t st) {
+    REGT_CHECK_ARG(x && lx && w0 && w1 && b && s_out, "regt_spatial_embed_forward: NULL pointer");
+    if (int rc = spatial_check_dims("regt_spatial_embed_forward", N, T, F)) return rc;
+    REGT_CHECK_ARG(al16(x) && al16(lx) && al16(b) && al16(s_out) && (!keep || (reinterpret_cast<uintptr_t>(keep) & 7) == 0),
+                   "regt_spatial_embed_forward: x, lx, bias, s_out must be 16-byte aligned, keep 8-byte aligned");
+    return launch_spatial_fwd(x, lx, w0, w1, b, keep, N, T, F, s_out, (hipStream_t)st);
+}
+
+int32_t regt_spatial_embed_backward(const float* x, const float* lx, const float* w0, const float* w1, const float* b,
+                                    const uint32_t* keep, const float* ds, int32_t N, int32_t T, int32_t F, float* dw0, float* dw1,
+                                    float* db, float* slab, regt_stream_t st) {
+    REGT_CHECK_ARG(x && lx && w0 && w1 && b && ds && dw0 && dw1 && db && slab, "regt_spatial_embed_backward: NULL pointer");
+    if (int rc = spatial_check_dims("regt_spatial_embed_backward", N, T, F)) return rc;
+    REGT_CHECK_ARG(al16(x) && al16(lx) && al16(ds) && (!keep || (reinterpret_cast<uintptr_t>(keep) & 7) == 0),
+                   "regt_spatial_embed_backward: x, lx, ds must be 16-byte aligned, keep 8-byte aligned");
+    return launch_spatial_bwd(x, lx, w0, w1, b, keep, ds, N, T, F, dw0, dw1, db, slab, (hipStream_t)st);
+}
+
+static int stnorm_check(const char* what, const regt_stnorm_dims* d, regt::StnDims* s) {
+    REGT_CHECK_ARG(d != nullptr, "%s: dims is NULL", what);
+    REGT_CHECK_ARG(d->num_nodes >= 2, "%s: num_nodes must be >= 2 (SNorm's unbiased variance), got %d", what, d->num_nodes);
+    REGT_CHECK_ARG(d->batch >= 1 && d->seq_len >= 1, "%s: batch and seq_len must be >= 1, got %d, %d", what, d->batch, d->seq_len);
+    REGT_CHECK_ARG(d->tnorm_group >= 1 && d->batch % d->tnorm_group == 0, "%s: tnorm_group %d must divide batch %d", what,
+                   d->tnorm_group, d->batch);
+    REGT_CHECK_ARG(d->in_dim >= 1 && d->in_dim <= regt::ST_MAX_CH && d->out_dim >= 1 && d->out_dim <= regt::ST_MAX_CH,
+                   "%s: in_dim and out_dim must be in [1, %d], got %d, %d", what, regt::ST_MAX_CH, d->in_dim, d->out_dim);
+    REGT_CHECK_ARG(d->blocks >= 1 && d->layers >= 1 && d->layers <= 8 && (long)d->blocks * d->layers <= 64,
+                   "%s: need 1 <= layers <= 8 and 1 <= blocks * layers <= 64, got blocks %d layers %d", what, d->blocks, d->layers);
+    *s = regt::StnDims{d->num_nodes, d->batch, d->tnorm_group, d->seq_len, d->in_dim, d->out_dim, d->blocks, d->layers,
+                       d->tnorm ? 1 : 0, d->snorm ? 1 : 0, d->training ? 1 : 0};
+    return REGT_OK;
+}
+
+static int stnorm_check_params(const char* what, const regt::StnDims& s, const void* const* p, const void* const* run, bool need_run) {
+    REGT_CHECK_ARG(p != nullptr, "%s: parameter table is NULL", what);
+    for (int k = 0; k < regt::ST_HEAD_PARAMS; ++k) REGT_CHECK_ARG(p[k] != nullptr, "%s: head entry %d is NULL", what, k);
+    for (int i = 0; i < s.blocks * s.layers; ++i) {
+        const void* const* q = p + regt::ST_HEAD_PARAMS + regt::ST_LAYER_PARAMS * i;
+        for (int k = 0; k < 8; ++k) REGT_CHECK_ARG(q[k] != nullptr, "%s: layer %d entry %d is NULL", what, i, k);
+        if (s.tnorm) REGT_CHECK_ARG(q[8] && q[9], "%s: layer %d TNorm gamma / beta is NULL", what, i);
+        if (s.snorm) REGT_CHECK_ARG(q[10] && q[11], "%s: layer %d SNorm gamma / beta is NULL", what, i);
+        if (s.tnorm && run) REGT_CHECK_ARG(run[2 * i] && run[2 * i + 1], "%s: layer %d running buffers are NULL", what, i);
+    }
+    if (s.tnorm && need_run) REGT_CHECK_ARG(run != nullptr, "%s: running-buffer table is NULL", what);
+    return REGT_OK;
+}
+
+int32_t regt_stnorm_sizes(const regt_stnorm_dims* d, size_t* ws, size_t* scratch) {
+    regt::StnDims s;
+    if (int rc = stnorm_check("regt_stnorm_sizes", d, &s)) return rc;
+    REGT_CHECK_ARG(regt::stnorm_sizes(s, ws, scratch), "regt_stnorm_sizes: unsupported dims");
+    return REGT_OK;
+}
+
+int32_t regt_stnorm_forward(const regt_stnorm_dims* d, const float* x, const float* const* params, float* const* running, float* out,
+                            float* ws, regt_stream_t st) {
+    regt::StnDims s;
+    if (int rc = stnorm_check("regt_stnorm_forward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && out && ws, "regt_stnorm_forward: NULL pointer");
+    if (int rc = stnorm_check_params("regt_stnorm_forward", s, reinterpret_cast<const void* const*>(params),
+                                     reinterpret_cast<const void* const*>(running), true))
+        return rc;
+    return regt::launch_stnorm_fwd(s, x, params, running, out, ws, (hipStream_t)st);
+}
+
+int32_t regt_stnorm_backward(const regt_stnorm_dims* d, const float* x, const float* const* params, float* const* running,
+                             const float* dout, float* const* grads, const float* ws, float* scratch, regt_stream_t st) {
+    regt::StnDims s;
+    if (int rc = stnorm_check("regt_stnorm_backward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && dout && grads && ws && scratch, "regt_stnorm_backward: NULL pointer");
+    if (int rc = stnorm_check_params("regt_stnorm_backward", s, reinterpret_cast<const void* const*>(params),
+                                     reinterpret_cast<const void* const*>(running), true))
+        return rc;
+    if (int rc = stnorm_check_params("regt_stnorm_backward (grads)", s, reinterpret_cast<const void* const*>(grads), nullptr, false)) return rc;
+    return regt::launch_stnorm_bwd(s, x, params, running, dout, grads, ws, scratch, (hipStream_t)st);
+}
+
+static int stid_check(const char* what, const regt_stid_dims* d, regt::StidDims* s) {
+    REGT_CHECK_ARG(d != nullptr, "%s: dims is NULL", what);
+    REGT_CHECK_ARG(d->num_nodes >= 1, "%s: num_nodes must be >= 1, got %d", what, d->num_nodes);
+    REGT_CHECK_ARG(d->batch >= 1, "%s: batch must be >= 1, got %d", what, d->batch);
+    REGT_CHECK_ARG(d->embed_dim == 32, "%s: embed_dim must be 32, got %d", what, d->embed_dim);
+    REGT_CHECK_ARG(d->node_dim == 32, "%s: node_dim must be 32, got %d", what, d->node_dim);
+    REGT_CHECK_ARG(d->num_layer >= 1 && d->num_layer <= regt::STID_MAX_LAYERS, "%s: num_layer must be in [1, %d], got %d", what,
+                   regt::STID_MAX_LAYERS, d->num_layer);
+    REGT_CHECK_ARG(d->input_len >= 1 && d->input_len <= 255, "%s: input_len must be in [1, 255], got %d", what, d->input_len);
+    REGT_CHECK_ARG(d->in_features >= 1 && d->in_features <= 256, "%s: in_features must be in [1, 256], got %d", what, d->in_features);
+    REGT_CHECK_ARG(d->input_dim >= 1 && d->input_dim <= d->in_features, "%s: input_dim must be in [1, in_features = %d], got %d", what,
+                   d->in_features, d->input_dim);
+    REGT_CHECK_ARG((long)d->input_dim * d->input_len <= regt::STID_MAX_KIN, "%s: input_dim * input_len must be <= %d, got %d * %d", what,
+                   regt::STID_MAX_KIN, d->input_dim, d->input_len);
+    REGT_CHECK_ARG(d->output_len >= 1 && d->output_len <= regt::STID_MAX_OUT, "%s: output_len must be in [1, %d], got %d", what,
+                   regt::STID_MAX_OUT, d->output_len);
+    REGT_CHECK_ARG(d->dropout_p >= 0.f && d->dropout_p < 1.f, "%s: dropout_p must be in [0, 1), got %g", what, (double)d->dropout_p);
+    REGT_CHECK_ARG((long)d->batch * d->num_nodes * 64 * (2 * d->num_layer + 1) < (1L << 40), "%s: batch * num_nodes is too large", what);
+    *s = regt::StidDims{d->num_nodes, d->batch, d->input_len, d->in_features, d->input_dim, d->embed_dim, d->node_dim, d->num_layer,
+                        d->output_len, d->if_node ? 1 : 0, d->dropout_p};
+    return REGT_OK;
+}
+
+static int stid_check_table(const char* what, const regt::StidDims& s, const void* const* p) {
+    REGT_CHECK_ARG(p != nullptr, "%s: table is NULL", what);
+    if (s.if_node) REGT_CHECK_ARG(p[0] != nullptr, "%s: entry 0 (node_emb) is NULL", what);
+    for (int k = 1; k < 3 + 4 * s.num_layer + 2; ++k) REGT_CHECK_ARG(p[k] != nullptr, "%s: entry %d is NULL", what, k);
+    return REGT_OK;
+}
+
+int32_t regt_stid_sizes(const regt_stid_dims* d, size_t* ws, size_t* scratch) {
+    regt::StidDims s;
+    if (int rc = stid_check("regt_stid_sizes", d, &s)) return rc;
+    REGT_CHECK_ARG(regt::stid_sizes(s, ws, scratch), "regt_stid_sizes: unsupported dims");
+    return REGT_OK;
+}
+
+int32_t regt_stid_forward(const regt_stid_dims* d, const float* x, const float* const* params, const uint32_t* keep, float* out, float* ws,
+                          regt_stream_t st) {
+    regt::StidDims s;
+    if (int rc = stid_check("regt_stid_forward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && out, "regt_stid_forward: x or out is NULL");
+    if (int rc = stid_check_table("regt_stid_forward: params", s, reinterpret_cast<const void* const*>(params))) return rc;
+    return regt::launch_stid_fwd(s, x, params, keep, out, ws, (hipStream_t)st);
+}
+
+int32_t regt_stid_backward(const regt_stid_dims* d, const float* x, const float* const* params, const uint32_t* keep, const float* dout,
+                           float* const* grads, const float* ws, float* scratch, regt_stream_t st) {
+    regt::StidDims s;
+    if (int rc = stid_check("regt_stid_backward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && dout && ws && scratch, "regt_stid_backward: x, dout, workspace or scratch is NULL");
+    if (int rc = stid_check_table("regt_stid_backward: params", s, reinterpret_cast<const void* const*>(params))) return rc;
+    if (int rc = stid_check_table("regt_stid_backward: grads", s, reinterpret_cast<const void* const*>(grads))) return rc;
+    return regt::launch_stid_bwd(s, x, params, keep, dout, grads, ws, scratch, (hipStream_t)st);
+}
+
+static int gru_check(const char* what, const regt_gru_dims* d, regt::GruDims* s) {
+    REGT_CHECK_ARG(d != nullptr, "%s: dims is NULL", what);
+    REGT_CHECK_ARG(d->hidden == regt::GRU_HIDDEN, "%s: hidden must be %d, got %d", what, regt::GRU_HIDDEN, d->hidden);
+    REGT_CHECK_ARG(d->input_size >= 1 && d->input_size <= regt::GRU_MAX_INPUT, "%s: input_size must be in [1, %d], got %d", what,
+                   regt::GRU_MAX_INPUT, d->input_size);
+    REGT_CHECK_ARG(d->seq_len >= 1, "%s: seq_len must be >= 1, got %d", what, d->seq_len);
+    REGT_CHECK_ARG(d->rows >= 1, "%s: rows must be >= 1, got %d", what, d->rows);
+    REGT_CHECK_ARG((long)d->seq_len * d->rows < (1L << 31) - d->rows, "%s: seq_len * rows must be below 2^31, got %d * %d", what, d->seq_len,
+                   d->rows);
+    REGT_CHECK_ARG(d->x_stride_seq >= 0 && d->x_stride_row >= 0 && d->x_stride_t >= 0, "%s: x strides must be >= 0", what);
+    *s = regt::GruDims{d->seq_len, d->rows, d->input_size, d->hidden, d->training ? 1 : 0, (long)d->x_stride_seq, (long)d->x_stride_row,
+                       (long)d->x_stride_t};
+    return REGT_OK;
+}
+
+int32_t regt_gru_sizes(const regt_gru_dims* d, size_t* ws, size_t* scratch) {
+    regt::GruDims s;
+    if (int rc = gru_check("regt_gru_sizes", d, &s)) return rc;
+    regt::gru_sizes(s, ws, scratch);
+    return REGT_OK;
+}
+
+int32_t regt_gru_forward(const regt_gru_dims* d, const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                         const float* h0, float* out, float* h_last, float* ws, regt_stream_t st) {
+    regt::GruDims s;
+    if (int rc = gru_check("regt_gru_forward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh, "regt_gru_forward: x or a weight is NULL");
+    REGT_CHECK_ARG(ws != nullptr, "regt_gru_forward: workspace is NULL");
+    REGT_CHECK_ARG(out || h_last, "regt_gru_forward: out and h_last are both NULL");
+    REGT_CHECK_ARG(((uintptr_t)ws & 15) == 0, "regt_gru_forward: workspace must be 16-byte aligned");
+    return regt::launch_gru_fwd(s, x, w_ih, w_hh, b_ih, b_hh, h0, out, h_last, ws, (hipStream_t)st);
+}
+
+int32_t regt_gru_backward(const regt_gru_dims* d, const float* x, const float* const* weights, const float* h0, const float* dout,
+                          const float* dh_last, float* const* grads, float* dh0, const float* ws, float* scratch, regt_stream_t st) {
+    regt::GruDims s;
+    if (int rc = gru_check("regt_gru_backward", d, &s)) return rc;
+    (void)h0;                                                   // the workspace holds it as step 0's previous state
+    REGT_CHECK_ARG(s.training, "regt_gru_backward: dims.training must be 1 (the forward saves nothing otherwise)");
+    REGT_CHECK_ARG(x && ws && scratch, "regt_gru_backward: x, workspace or scratch is NULL");
+    REGT_CHECK_ARG(weights && grads, "regt_gru_backward: weights or grads table is NULL");
+    for (int k = 0; k < 4; ++k) REGT_CHECK_ARG(weights[k] && grads[k], "regt_gru_backward: weights or grads entry %d is NULL", k);
+    REGT_CHECK_ARG(dout || dh_last, "regt_gru_backward: dout and dh_last are both NULL");
+    REGT_CHECK_ARG((((uintptr_t)ws | (uintptr_t)scratch) & 15) == 0, "regt_gru_backward: workspace and scratch must be 16-byte aligned");
+    return regt::launch_gru_bwd(s, x, weights[1], dout, dh_last, grads, dh0, ws, scratch, (hipStream_t)st);
+}
+
+}  // extern "C"

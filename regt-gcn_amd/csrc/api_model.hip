@@ -1,0 +1,190 @@
+// Entry points of the RegT-GCN / TemporalGCN step: checks, layout and format of the call, then api_step.hip eagerly or as a captured graph.
+#include "api_internal.h"
+
+namespace regt { namespace {
+
+// q crosses from regt_forward to regt_backward: remember per workspace how the forward stored it, so that a mode change in
+// between is caught instead of misread.
+std::mutex g_qfmt_mu;
+std::unordered_map<const void*, int> g_qfmt;
+void note_q_format(const void* ws, int bf16) {
+    std::lock_guard<std::mutex> lk(g_qfmt_mu);
+    if (g_qfmt.size() > 4096) g_qfmt.clear();
+    g_qfmt[ws] = bf16;
+}
+int q_format(const void* ws) {
+    std::lock_guard<std::mutex> lk(g_qfmt_mu);
+    auto it = g_qfmt.find(ws);
+    return it == g_qfmt.end() ? 0 : it->second;
+}
+
+int check_ptrs(const regt_params* p, const regt_dims& d, bool cell_only = false) {
+    REGT_CHECK_ARG(p != nullptr, "params is NULL");
+    bool ok = p->attention && p->head1_w && p->head1_b && p->head2_w && p->head2_b;
+    if (!cell_only) ok = ok && p->cheb_w0 && p->cheb_w1 && p->cheb_bias;
+    for (int k = 0; k < 3; ++k) ok = ok && p->conv_lin_w[k] && p->conv_bias[k] && p->gate_w[k] && p->gate_b[k];
+    if (d.regional && !cell_only) ok = ok && p->region_w && p->region_b;
+    REGT_CHECK_ARG(ok, "params: a required tensor pointer is NULL");
+    return REGT_OK;
+}
+
+}}  // namespace regt::(anonymous)
+
+using namespace regt;
+
+extern "C" {
+
+static int32_t forward_common(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const float* x,
+                              const float* xp_ext, int32_t x_rows, float* pred, float* hidden, void* ws, size_t ws_bytes,
+                              regt_stream_t st, bool xp_is_bf16 = false) {
+    TRY(check_dims(dims));
+    CallScope call(dims);
+    REGT_CHECK_ARG(graph && graph->rowptr && graph->col && graph->val && (graph->node_region || graph->overlap), "regt_forward: graph incomplete");
+    TRY(check_ptrs(params, *dims));
+    REGT_CHECK_ARG((x || xp_ext) && pred && hidden && ws, "regt_forward: NULL pointer");
+    REGT_CHECK_ARG(al16(x) && al16(xp_ext) && al16(hidden) && al16(ws),
+                   "regt_forward: x, hidden and workspace must be 16-byte aligned");
+    REGT_CHECK_ARG(!xp_ext || x_rows >= dims->N, "regt_forward_packed: x_rows=%d < N=%d", x_rows, dims->N);
+    hipStream_t hs = (hipStream_t)st;
+    int fmt = forward_format(*dims, *graph, xp_ext ? x_rows : dims->N, xp_ext && !xp_is_bf16, xp_is_bf16);
+    REGT_CHECK_ARG(!xp_is_bf16 || (fmt & FMT_XBF), "regt_forward_packed_bf16: bf16 input rows need REGT_GEMM_MODE=bf16 and a shape the fused "
+                   "forward covers (C = 256, F = 64, node-disjoint regions, merged operator)");
+    Layout L;
+    if (dims->flags & REGT_DIMS_FORWARD_ONLY) {
+        L = forward_only_layout(*dims, *graph, xp_ext != nullptr, x_rows, xp_is_bf16, (char*)ws, &fmt);
+        REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_forward (REGT_DIMS_FORWARD_ONLY): workspace %zu < required %zu bytes (%s)", ws_bytes, L.bytes,
+                       xp_ext ? "regt_forward_only_packed_workspace_bytes" : "regt_forward_only_workspace_bytes");
+        fmt |= FMT_FWDONLY;
+    } else {
+        L = make_layout(*dims, graph->n_chunks, graph->overlap, (char*)ws);
+        REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_forward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
+    }
+    note_q_format(ws, fmt);
+    if (!graphs_wanted((long)dims->N * dims->T))
+        return forward_impl(*dims, *graph, *params, x, xp_ext, x_rows, pred, hidden, L, hs, false, nullptr, fmt);
+    // the snapshot changes every step: pack it with a plain launch, replay everything behind it
+    if (!xp_ext) {
+        if (fmt & FMT_XBF) TRY(launch_pack_x_bf16(x, L.Xp, dims->N, dims->F, dims->T, hs));
+        else TRY(launch_pack_x(x, L.Xp, dims->N, dims->F, dims->T, hs));
+    } else if ((fmt & FMT_XBF) && !(fmt & FMT_XCALLER)) {
+        TRY(launch_cvt_rows_bf16(xp_ext, L.Xp, (long)x_rows * dims->T * dims->F, hs));
+    }
+    unsigned long long key = hash_bytes(dims, sizeof(*dims), 0xcbf29ce484222325ull);
+    key = hash_bytes(graph, sizeof(*graph), key);
+    key = hash_bytes(params, sizeof(*params), key);
+    const void* ptrs[6] = {xp_ext, pred, hidden, ws, (const void*)(long)x_rows, (const void*)(long)fmt};
+    key = hash_bytes(ptrs, sizeof(ptrs), key);
+    const regt_dims dd = *dims; const regt_graph gg = *graph; const regt_params pp = *params;
+    return run_maybe_graphed(g_fwd_graphs, key, hs, [=](hipStream_t s) {
+        return forward_impl(dd, gg, pp, x, xp_ext, x_rows, pred, hidden, L, s, /*skip_pack=*/true, nullptr, fmt);
+    });
+}
+
+int32_t regt_forward(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const float* x, float* pred,
+                     float* hidden, void* ws, size_t ws_bytes, regt_stream_t st) {
+    REGT_CHECK_ARG(x != nullptr, "regt_forward: x is NULL");
+    return forward_common(dims, graph, params, x, nullptr, 0, pred, hidden, ws, ws_bytes, st);
+}
+
+int32_t regt_forward_packed(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const float* x_packed,
+                            int32_t x_rows, float* pred, float* hidden, void* ws, size_t ws_bytes, regt_stream_t st) {
+    REGT_CHECK_ARG(x_packed != nullptr, "regt_forward_packed: x_packed is NULL");
+    return forward_common(dims, graph, params, nullptr, x_packed, x_rows, pred, hidden, ws, ws_bytes, st);
+}
+
+int32_t regt_forward_packed_bf16(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const void* x_packed_bf16,
+                                 int32_t x_rows, float* pred, float* hidden, void* ws, size_t ws_bytes, regt_stream_t st) {
+    REGT_CHECK_ARG(x_packed_bf16 != nullptr, "regt_forward_packed_bf16: x_packed is NULL");
+    return forward_common(dims, graph, params, nullptr, static_cast<const float*>(x_packed_bf16), x_rows, pred, hidden, ws, ws_bytes, st, true);
+}
+
+int32_t regt_backward(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const regt_grads* grads,
+                      const float* dpred, const float* dhidden, const float* hidden, const float* x_packed, void* ws,
+                      size_t ws_bytes, regt_stream_t st) {
+    TRY(check_dims(dims));
+    CallScope call(dims);
+    REGT_CHECK_ARG(graph && graph->rowptr && (graph->node_region || graph->overlap), "regt_backward: graph incomplete");
+    TRY(check_ptrs(params, *dims));
+    REGT_CHECK_ARG(grads && dpred && hidden && ws, "regt_backward: NULL pointer");
+    {
+        const regt_grads& g = *grads;
+        bool ok = g.cheb_w0 && g.cheb_w1 && g.cheb_bias && g.head1_w && g.head1_b && g.head2_w && g.head2_b;
+        for (int k = 0; k < 3; ++k) ok = ok && g.conv_lin_w[k] && g.conv_bias[k] && g.gate_w[k] && g.gate_b[k];
+        if (dims->regional) ok = ok && g.region_w && g.region_b;
+        REGT_CHECK_ARG(ok, "regt_backward: a required gradient pointer is NULL (only `attention` may be NULL)");
+    }
+    const int qbf = q_format(ws);
+    REGT_CHECK_ARG(!(qbf & FMT_FWDONLY), "regt_backward: the last forward on this workspace ran with REGT_DIMS_FORWARD_ONLY and kept no activations; "
+                   "run the forward without that flag on a workspace of regt_workspace_bytes");
+    Layout L = make_layout(*dims, graph->n_chunks, graph->overlap, (char*)ws);
+    REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_backward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
+    hipStream_t hs = (hipStream_t)st;
+    REGT_CHECK_ARG((qbf & FMT_QBF) == (bf16_intermediates(*dims) ? 1 : 0),
+                   "regt_backward: the GEMM arithmetic changed since the forward on this workspace (another regt_dims.arith, or regt_set_gemm_mode between forward and backward)");
+    REGT_CHECK_ARG(!(qbf & FMT_XCALLER) || x_packed, "regt_backward: the forward ran on the caller's bf16 packed input; pass the same buffer as x_packed");
+    if (!graphs_wanted((long)dims->N * dims->T))
+        return backward_impl(*dims, *graph, *params, *grads, dpred, dhidden, hidden, x_packed, L, hs, qbf);
+    unsigned long long key = hash_bytes(dims, sizeof(*dims), 0x84222325cbf29ce4ull);
+    key = hash_bytes(graph, sizeof(*graph), key);
+    key = hash_bytes(params, sizeof(*params), key);
+    key = hash_bytes(grads, sizeof(*grads), key);
+    const void* ptrs[6] = {dpred, dhidden, hidden, x_packed, ws, (const void*)(long)qbf};
+    key = hash_bytes(ptrs, sizeof(ptrs), key);
+    const regt_dims dd = *dims; const regt_graph gg = *graph; const regt_params pp = *params; const regt_grads gr = *grads;
+    return run_maybe_graphed(g_bwd_graphs, key, hs, [=](hipStream_t s) {
+        return backward_impl(dd, gg, pp, gr, dpred, dhidden, hidden, x_packed, L, s, qbf);
+    });
+}
+
+/* ---- TGCN cell + attention + head on a caller-supplied hidden input (regtgcn.h) --------------------------------- */
+int32_t regt_cell_forward(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const float* x,
+                          const float* h_in, float* pred, float* hidden, void* ws, size_t ws_bytes, regt_stream_t st) {
+    TRY(check_dims(dims));
+    CallScope call(dims);
+    REGT_CHECK_ARG(dims->regional == 0, "regt_cell_forward: dims.regional must be 0");
+    REGT_CHECK_ARG(graph && graph->rowptr && graph->col && graph->val && !graph->overlap, "regt_cell_forward: graph incomplete");
+    TRY(check_ptrs(params, *dims, true));
+    REGT_CHECK_ARG(x && h_in && pred && hidden && ws, "regt_cell_forward: NULL pointer");
+    REGT_CHECK_ARG(al16(x) && al16(h_in) && al16(hidden) && al16(ws), "regt_cell_forward: x, h_in, hidden and workspace must be 16-byte aligned");
+    int fmt = bf16_intermediates(*dims) ? FMT_QBF : 0;
+    Layout L;
+    if (dims->flags & REGT_DIMS_FORWARD_ONLY) {
+        L = make_layout_fwd(*dims, 0, false, dims->N, (char*)ws);
+        REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_cell_forward (REGT_DIMS_FORWARD_ONLY): workspace %zu < required %zu bytes (regt_forward_only_workspace_bytes)",
+                       ws_bytes, L.bytes);
+        fmt |= FMT_FWDONLY;
+    } else {
+        L = make_layout(*dims, 0, 0, (char*)ws);
+        REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_cell_forward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
+    }
+    note_q_format(ws, fmt);
+    return forward_impl(*dims, *graph, *params, x, nullptr, 0, pred, hidden, L, (hipStream_t)st, false, h_in, fmt);
+}
+
+int32_t regt_cell_backward(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const regt_grads* grads,
+                           const float* dpred, const float* dhidden, const float* hidden, const float* h_in, float* dh_in,
+                           void* ws, size_t ws_bytes, regt_stream_t st) {
+    TRY(check_dims(dims));
+    CallScope call(dims);
+    REGT_CHECK_ARG(dims->regional == 0, "regt_cell_backward: dims.regional must be 0");
+    REGT_CHECK_ARG(graph && graph->rowptr && !graph->overlap, "regt_cell_backward: graph incomplete");
+    TRY(check_ptrs(params, *dims, true));
+    REGT_CHECK_ARG(grads && dpred && hidden && h_in && dh_in && ws, "regt_cell_backward: NULL pointer");
+    REGT_CHECK_ARG(al16(h_in) && al16(dh_in), "regt_cell_backward: h_in and dh_in must be 16-byte aligned");
+    {
+        const regt_grads& g = *grads;
+        bool ok = g.head1_w && g.head1_b && g.head2_w && g.head2_b;
+        for (int k = 0; k < 3; ++k) ok = ok && g.conv_lin_w[k] && g.conv_bias[k] && g.gate_w[k] && g.gate_b[k];
+        REGT_CHECK_ARG(ok, "regt_cell_backward: a required gradient pointer is NULL (only `attention` may be NULL)");
+    }
+    const int qbf = q_format(ws);
+    REGT_CHECK_ARG(!(qbf & FMT_FWDONLY), "regt_cell_backward: the last forward on this workspace ran with REGT_DIMS_FORWARD_ONLY and kept no activations; "
+                   "run the forward without that flag on a workspace of regt_workspace_bytes");
+    Layout L = make_layout(*dims, 0, 0, (char*)ws);
+    REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_cell_backward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
+    REGT_CHECK_ARG((qbf & FMT_QBF) == (bf16_intermediates(*dims) ? 1 : 0),
+                   "regt_cell_backward: the GEMM arithmetic changed since the forward on this workspace");
+    return backward_impl(*dims, *graph, *params, *grads, dpred, dhidden, hidden, nullptr, L, (hipStream_t)st, qbf, h_in, dh_in);
+}
+
+}  // extern "C"

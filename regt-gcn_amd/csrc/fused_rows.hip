@@ -575,7 +575,7 @@ int launch_fused_forward_rows(const FusedFwdArgs& a_, int C, int F, int waves, h
     const long tiles = (a.M + 16 * nw - 1) / (16 * nw);
     REGT_CHECK_ARG(a.M < (1L << 31), "fused forward: too many rows");
     a.trace = fused_trace_buffer(1, tiles);
-    {   // the weight blocks live in one workspace buffer (api.hip wb_ptrs): one base + 32-bit offsets
+    {   // the weight blocks live in one workspace buffer (api_layout.hip wb_ptrs): one base + 32-bit offsets
         const char* ptrs[7] = {(const char*)a.Uzf, (const char*)a.Urf, (const char*)a.Uhf, (const char*)a.Gzrf, (const char*)a.Ghf, (const char*)a.A0f, (const char*)a.Aallf};
         const char* base = ptrs[0];
         for (int i = 1; i < 7; ++i) base = ptrs[i] < base ? ptrs[i] : base;

@@ -112,7 +112,7 @@ bool gemm_dgrad1_gen_ok(long M, int C, int num_nodes);
 bool wgrad_ring_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks);
 bool wgrad_skinny_chunking(int Nout, long M, int* kchunk, int* nchunks);            // skinny (Nin <= 32) fp32-MFMA kernel
 bool wgrad_wide_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks);   // wide fp32 / bf16x3 kernels (experiment)
-long wgrad_chunk_bound(int Nout, int Nin, long M);   // upper bound of what the three can return (slab sizing, api.hip make_layout)
+long wgrad_chunk_bound(int Nout, int Nin, long M);   // upper bound of what the three can return (slab sizing, api_layout.hip make_layout)
 bool wgrad_ring_active();             // the ring kernel takes the bf16-stored weight gradients (pairs pay off with it)
 int launch_gemm_dgrad1_gen(const GemmSegs& S, long M, int N, const EpiDgrad1& e, hipStream_t st);
 int launch_gemm_dgrad2(const GemmSegs& S, long M, int N, const EpiDgrad2& e, hipStream_t st);

@@ -39,7 +39,7 @@ inputs of ``split_sensitive_inputs`` / ``wgrad_sensitive_inputs``, where any los
 
 The HIP kernels' own r per case is in profiles/op_bars.txt (tools/op_bars.py writes it).
 
-``expected_kernel`` restates the host-side dispatch of csrc/gemm.hip, wgrad.hip, spmm.hip and api.hip; the GPU cases are labelled
+``expected_kernel`` restates the host-side dispatch of csrc/gemm.hip, wgrad.hip, spmm.hip and api_ops.hip; the GPU cases are labelled
 with its result and tests/test_op_bars_cpu.py asserts that the tables reach every kernel name of KERNELS.
 """
 from __future__ import annotations
@@ -233,7 +233,7 @@ def linear_restatement(a, w, b, arith: int, **corrupt) -> torch.Tensor:
 
 
 def wgrad_chunks(m: int) -> Tuple[int, int]:
-    """api.hip wgrad_chunks: (rows per chunk, chunks) of regt_wgrad."""
+    """api_ops.hip wgrad_chunks: (rows per chunk, chunks) of regt_wgrad."""
     kc = ((m + 127) // 128 + 31) // 32 * 32
     kc = max(kc, 512)
     return kc, (m + kc - 1) // kc
@@ -462,7 +462,7 @@ def expected_kernel(op: str, mode: int, shape, options: Optional[Dict] = None) -
     o.update(options or {})
     if op == "linear":
         m, k, n = shape
-        # gemm.hip launch_gemm_bias_act: contiguous fp32 tensors, ldo = N; api.hip make_seg: SEG_VEC_A / _B need lda = ldb = K % 4 == 0
+        # gemm.hip launch_gemm_bias_act: contiguous fp32 tensors, ldo = N; api_internal.h make_seg: SEG_VEC_A / _B need lda = ldb = K % 4 == 0
         vec = n % 4 == 0
         # gemm.hip fast_class: one BT segment, no region, no relu on A
         fast = vec and k % 4 == 0 and _cdiv(k, GBK) <= G_MAX_ITERS and k < (1 << 22)
@@ -479,7 +479,7 @@ def expected_kernel(op: str, mode: int, shape, options: Optional[Dict] = None) -
         return f"gemm_flat_split_kernel<{(0, 3, 1)[mode]}>/{'scalar' if uniform else 'table'}"
     if op == "wgrad":
         m, nout, nin = shape
-        # api.hip wgrad_chunks + wgrad_full: one right-hand side, fp32 rows, ldp = Nout, ldq = Nin
+        # api_ops.hip wgrad_chunks + api_step.hip wgrad_full: one right-hand side, fp32 rows, ldp = Nout, ldq = Nin
         kc, nc = wgrad_chunks(m)
         # wgrad.hip launch_wgrad_impl
         wide = nin > 32
@@ -500,7 +500,7 @@ def expected_kernel(op: str, mode: int, shape, options: Optional[Dict] = None) -
     if op == "spmm_csr":
         nrows, x_rows, w = shape
         w4 = w // 4
-        # spmm.hip launch_spmm_csr.  regt_spmm_csr (api.hip) always passes nstack = 1, so a stacked operator runs as a plain CSR of
+        # spmm.hip launch_spmm_csr.  regt_spmm_csr (api_ops.hip) always passes nstack = 1, so a stacked operator runs as a plain CSR of
         # 2 n rows over n rows of X: the nstack > 1 indexing of spmm_panel_kernel cannot be reached from the op site
         if w4 % 8 == 0 and x_rows * w * 4 > (24 << 20) and nrows >= 4096:
             pl = 16 if panel_wide(nrows) and w4 % 16 == 0 else 8

@@ -81,7 +81,7 @@ SHAPES = [(1500, 15000, 8, 32, 12, 1), (2048, 20000, 64, 64, 12, 1), (1200, 9000
 
 
 def _rows_bf16(f, t, regions):
-    """Where the library keeps x / A_hat x / L~ x as bf16 rows and runs the fused forward kernel (api.hip: xbf_ok)."""
+    """Where the library keeps x / A_hat x / L~ x as bf16 rows and runs the fused forward kernel (api_step.hip: xbf_ok)."""
     return f in (32, 64) and regions > 1 and (t * f) % 64 == 0
 
 

@@ -221,7 +221,7 @@ def test_ring_weight_gradient_other_hidden_widths(bf16_mode, hidden):
 
 
 def test_one_wave_row_chunking_of_the_paired_weight_gradients(bf16_mode):
-    """The paired ring-kernel launches cut the rows into as many chunks as fill the GPU once (api.hip / wgrad_ring_chunking) instead
+    """The paired ring-kernel launches cut the rows into as many chunks as fill the GPU once (api_step.hip / wgrad_ring_chunking) instead
     of the layout's ~128: the same products summed over other chunk boundaries -- gradients within 2e-5 of their scale, the
     rest of the step untouched.  40 000 x 12 rows: 170 / 85 chunks of 2 848 / 5 664 rows instead of 128 of 3 776."""
     R = bf16_mode

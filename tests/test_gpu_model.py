@@ -653,7 +653,7 @@ def test_arithmetic_is_per_call_two_models_of_one_process():
 
 def test_two_launch_streams_have_side_streams_of_their_own():
     """Two models driven from two torch streams, steps interleaved on the host: each launch stream forks / joins a side stream of its
-    own (api.hip: one per (device, stream)), so both reproduce their single-stream results bit for bit."""
+    own (api_runtime.hip: one per (device, stream)), so both reproduce their single-stream results bit for bit."""
     import regtgcn_amd as R
     R.load_library()
     n, e, regions, f, t, o = 4000, 30000, 8, 32, 12, 1

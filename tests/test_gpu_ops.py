@@ -340,7 +340,7 @@ def test_sixty_four_wide_weight_gradient_tile_equals_two_of_thirty_two(n, e, reg
 @pytest.mark.parametrize("n,e,f,t,o", [(3000, 24000, 32, 12, 1), (1409, 9000, 8, 6, 2), (104, 400, 8, 12, 1)])
 def test_temporal_gcn_collapsed_gates_equal_the_uncollapsed_form(n, e, f, t, o):
     """TemporalGCN's hidden input has no activation (models/TemporalGCN.py:88), so the gates' use of it folds into x and L~ x
-    (api.hip: FMT_TCOLLAPSE -- gate GEMM at K = 3F, no K = 2C data gradient, no (2C x C) weight gradient in the backward pass).
+    (api_step.hip: FMT_TCOLLAPSE -- gate GEMM at K = 3F, no K = 2C data gradient, no (2C x C) weight gradient in the backward pass).
     Same function, reassociated: outputs within 2e-6, every gradient within 2e-5 of its scale of the uncollapsed form
     (regt_set_option("tgcn_collapse", 0)); F = 32 (two-part right-hand side), F = 8 (one launch per part), a TPIMS-sized graph."""
     import regtgcn_amd as R

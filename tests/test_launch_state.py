@@ -1,5 +1,5 @@
 """The native library's launch state is keyed by device (kernels.h want_dynamic_lds / device_cus, the per-device graph stream of
-api.hip).  Without a GPU: the workspace sizes, which go through the one chunk calculator of wgrad.hip, are pinned to
+api_runtime.hip).  Without a GPU: the workspace sizes, which go through the one chunk calculator of wgrad.hip, are pinned to
 recorded numbers.  With two GPUs: one process drives both and gets the same bits from each."""
 import ctypes as C
 import os
@@ -32,6 +32,70 @@ def test_workspace_bytes_are_what_they_were(shape):
     d = _lib.Dims(n, t, f, c, r, 1, 128, 1, 0.01, 0, 0)
     got = [lib.regt_workspace_bytes(C.byref(d), n_chunks, overlap) for n_chunks in (0, 1, 40) for overlap in (0, 1)]
     assert got == WORKSPACE_BYTES[shape]
+
+
+# The sizers the table above does not cover, recorded the same way from the library as it was while its host layer was one file.
+# regt_forward_only_workspace_bytes of the same shapes, regional, 40 region chunks and a merged operator (so that the fused form
+# can be asked for), for arith = default, bf16: (3000, 12, 32, 256, 4) and cfg-3 take the fused form under bf16.
+FORWARD_ONLY_BYTES = {
+    (104, 6, 8, 256, 5): [3867904, 3867904],
+    (3000, 12, 32, 256, 4): [164395776, 9894656],
+    (100000, 12, 32, 256, 8): [5428976384, 283243264],
+    (40000, 12, 32, 128, 4): [1188368128, 1188368128],
+}
+# regt_forward_only_packed_workspace_bytes at (3000, 12, 32, 256, 4): (x_rows, x_is_bf16, arith) -> bytes.  bf16 rows under fp32
+# arithmetic are refused; fp32 rows under bf16 are converted into the workspace, all x_rows of them.
+PACKED_SHAPE = (3000, 12, 32, 256, 4)
+PACKED_REFUSED = b"regt_forward_only_packed_workspace_bytes: bf16 input rows need bf16 arithmetic and a shape the fused forward covers"
+FORWARD_ONLY_PACKED_BYTES = {
+    (3000, 0, _lib.ARITH_DEFAULT): 164395776, (3000, 0, _lib.ARITH_BF16): 9894656,
+    (3000, 1, _lib.ARITH_DEFAULT): 0, (3000, 1, _lib.ARITH_BF16): 9894656,
+    (4500, 0, _lib.ARITH_DEFAULT): 164395776, (4500, 0, _lib.ARITH_BF16): 11046656,
+    (4500, 1, _lib.ARITH_DEFAULT): 0, (4500, 1, _lib.ARITH_BF16): 9894656,
+}
+# regt_cell0_workspace_bytes of (N, T, C) with O = 1, H1 = 128 for (kz, kh) = (8, 8), (32, 64)
+CELL0_BYTES = {(104, 6, 256): [2997504, 3407104], (3000, 12, 128): [82595328, 94146048]}
+
+
+def _merged_graph():
+    """A regt_graph whose every pointer is set: the sizers decide from NULL / non-NULL and n_chunks alone and read nothing."""
+    buf = (C.c_int32 * 4)()
+    g = _lib.Graph()
+    for name in ("rowptr", "col", "val", "node_region", "chunk_tab", "chunk_region", "m_rowptr", "m_col", "m_val_a", "m_val_l"):
+        setattr(g, name, C.addressof(buf))
+    g.n_chunks = 40
+    return g, buf
+
+
+@pytest.mark.parametrize("shape", list(FORWARD_ONLY_BYTES), ids=lambda s: "N%d_T%d_F%d_C%d_R%d" % s)
+def test_forward_only_workspace_bytes_are_what_they_were(shape):
+    lib = _lib.load()
+    g, _keep = _merged_graph()
+    got = []
+    for arith in (_lib.ARITH_DEFAULT, _lib.ARITH_BF16):
+        d = _lib.Dims(*shape, 1, 128, 1, 0.01, arith, 0)
+        got.append(lib.regt_forward_only_workspace_bytes(C.byref(d), C.byref(g)))
+    assert got == FORWARD_ONLY_BYTES[shape]
+
+
+@pytest.mark.parametrize("case", list(FORWARD_ONLY_PACKED_BYTES), ids=lambda c: "rows%d_bf16rows%d_arith%d" % c)
+def test_forward_only_packed_workspace_bytes_are_what_they_were(case):
+    lib = _lib.load()
+    g, _keep = _merged_graph()
+    x_rows, x_is_bf16, arith = case
+    d = _lib.Dims(*PACKED_SHAPE, 1, 128, 1, 0.01, arith, 0)
+    got = lib.regt_forward_only_packed_workspace_bytes(C.byref(d), C.byref(g), x_rows, x_is_bf16)
+    assert got == FORWARD_ONLY_PACKED_BYTES[case]
+    if got == 0:
+        assert lib.regt_last_error() == PACKED_REFUSED
+
+
+@pytest.mark.parametrize("shape", list(CELL0_BYTES), ids=lambda s: "N%d_T%d_C%d" % s)
+def test_cell0_workspace_bytes_are_what_they_were(shape):
+    lib = _lib.load()
+    n, t, c = shape
+    d = _lib.Dims(n, t, 32, c, 1, 1, 128, 0, 0.01, 0, 0)
+    assert [lib.regt_cell0_workspace_bytes(C.byref(d), kz, kh) for kz, kh in ((8, 8), (32, 64))] == CELL0_BYTES[shape]
 
 
 def _snapshot(dev, arith, calls, n):
