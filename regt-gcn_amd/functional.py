@@ -1,6 +1,7 @@
 """autograd bridge: one Function = one regt_forward / regt_backward pair of the C ABI."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, List, Optional
 
@@ -8,6 +9,7 @@ import torch
 
 from . import _lib
 from .graph import PreparedGraph
+from .ops import _stream
 
 HEAD_HIDDEN = 128
 
@@ -53,10 +55,6 @@ def _fill(struct, tensors: Dict[str, Optional[torch.Tensor]], regional: bool):
     return struct
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 class _WorkspacePool:
     """The forward leaves its activations in a multi-GB workspace that the backward reads.  Blocks are recycled
     here (keyed by device and size) instead of going back to the allocator after every step: a step then never
@@ -86,10 +84,16 @@ _POOL = _WorkspacePool()
 
 
 class _WsHandle:
-    """Returns the block to the pool when the autograd node that owns it goes away."""
+    """A pooled block of ``nbytes``; returns it to the pool when the autograd node that owns it goes away."""
 
-    def __init__(self, ws):
-        self.ws = ws
+    def __init__(self, nbytes: int, device):
+        self.ws = _POOL.acquire(nbytes, device)
+
+    def release_now(self):
+        """A forward-only call gives its block back when it returns.  Stream-ordered: the pool hands the block out again on this
+        stream only."""
+        _POOL.release(self.ws)
+        self.ws = None
 
     def __del__(self):
         try:
@@ -97,6 +101,14 @@ class _WsHandle:
                 _POOL.release(self.ws)
         except Exception:  # interpreter shutdown
             pass
+
+
+def _workspace_bytes(sizer: str, *args) -> int:
+    """What the library's ``sizer`` asks for ``args``; it returns 0 for dims it refuses (the reason is in regt_last_error)."""
+    nbytes = getattr(_lib.load(), sizer)(*args)
+    if nbytes == 0:
+        _lib.check(1, sizer)
+    return nbytes
 
 
 def _graph_struct(graph: PreparedGraph, periods: int) -> _lib.Graph:
@@ -134,6 +146,42 @@ def set_grad_accumulation_in_backward(flag: bool) -> bool:
     return prev
 
 
+@contextlib.contextmanager
+def grad_accumulation_in_backward():
+    """:func:`set_grad_accumulation_in_backward` on for the body (a plain ``loss.backward()`` loop); the previous setting is back on exit."""
+    prev = set_grad_accumulation_in_backward(True)
+    try:
+        yield
+    finally:
+        set_grad_accumulation_in_backward(prev)
+
+
+def _deliver_grads(params, grads):
+    """Gradients of ``params`` as autograd's return values, or, under :func:`set_grad_accumulation_in_backward`, added to ``.grad``
+    here (one fused add) with None returned for each."""
+    live = [(p, g) for p, g in zip(params, grads) if p is not None and g is not None]
+    if _ACCUMULATE_IN_BACKWARD and all(p.is_leaf and p.requires_grad for p, _ in live):
+        have, new = [], []
+        for p, g in live:
+            if p.grad is None:
+                p.grad = g                       # (this call's own buffer, which nothing else refers to)
+            else:
+                have.append(p.grad)
+                new.append(g)
+        if have:
+            torch._foreach_add_(have, new)
+        return (None,) * len(params)
+    return tuple(grads)
+
+
+def _upstream_grads(dpred, dhidden, dims, device):
+    """The gradients of ``(pred, hidden)`` as the library reads them: contiguous, zeros for a ``pred`` the loss did not use; the
+    gradient of an unused ``hidden`` stays None (the Functions do not materialise it)."""
+    if dpred is None:
+        dpred = torch.zeros(dims.N, dims.O, dtype=torch.float32, device=device)
+    return dpred.contiguous(), None if dhidden is None else dhidden.contiguous()
+
+
 # Evaluation (train.evaluate*, evaluate.predict_metrics*, a plain model(x) under torch.no_grad()) needs no backward: the modules then
 # call the library with REGT_DIMS_FORWARD_ONLY -- same pred / hidden bit for bit, no activation stores, a workspace of
 # regt_forward_only_workspace_bytes (no M x C array at all on the fused bf16 forward, four instead of nine elsewhere) that goes back
@@ -157,8 +205,14 @@ def wants_forward_only(*tensors) -> bool:
 
 
 class _FwdState:
-    """What one regt_forward call leaves for its backward."""
-    __slots__ = ("graph", "regional", "dims", "handle", "wsb", "ps", "gs", "xp", "names", "f_real", "f_pad", "params")
+    """What one regt_forward / regt_cell_forward call leaves for its backward; the Function keeps it on ``ctx`` as it is.  ``graph``
+    is the prepared graph or operator (the pointer structs point into its tensors), ``saved`` the tensors that go to
+    ``save_for_backward`` after ``hidden``; the cell fills only the first five."""
+    __slots__ = ("graph", "dims", "handle", "wsb", "saved", "regional", "ps", "gs", "xp", "names", "f_real", "f_pad")
+
+    def __init__(self, **fields):
+        for k, v in fields.items():
+            setattr(self, k, v)
 
 
 def _regt_forward_call(x: torch.Tensor, graph: PreparedGraph, regional: bool, slope: float, packed, params, forward_only: bool):
@@ -226,22 +280,17 @@ def _regt_forward_call(x: torch.Tensor, graph: PreparedGraph, regional: bool, sl
                 raise ValueError(f"parameter {k} has shape {tuple(tens[k].shape)}, expected {shp}")
         dims = _lib.Dims(N, T, F, Cdim, R, O, H1, 1 if regional else 0, float(slope), int(arith), int(flags))
         gs = _graph_struct(graph, T)
-        if forward_only and packed:
-            sizer = "regt_forward_only_packed_workspace_bytes"        # (x_rows and the row type enter the form and the layout)
-            wsb = lib.regt_forward_only_packed_workspace_bytes(C.byref(dims), C.byref(gs), x_rows, 1 if xbf else 0)
+        if forward_only and packed:                   # (x_rows and the row type enter the form and the layout)
+            wsb = _workspace_bytes("regt_forward_only_packed_workspace_bytes", C.byref(dims), C.byref(gs), x_rows, 1 if xbf else 0)
         elif forward_only:
-            sizer = "regt_forward_only_workspace_bytes"
-            wsb = lib.regt_forward_only_workspace_bytes(C.byref(dims), C.byref(gs))
+            wsb = _workspace_bytes("regt_forward_only_workspace_bytes", C.byref(dims), C.byref(gs))
         else:
-            sizer = "regt_workspace_bytes"
-            wsb = lib.regt_workspace_bytes(C.byref(dims), gs.n_chunks, gs.overlap)
-        if wsb == 0:
-            _lib.check(1, sizer)
+            wsb = _workspace_bytes("regt_workspace_bytes", C.byref(dims), gs.n_chunks, gs.overlap)
         if len(plans) > 16:
             plans.clear()
         plan = plans[plan_key] = (dims, gs, wsb, _fill(_lib.Params(), tens, regional), Cdim, O)
     dims, gs, wsb, ps, Cdim, O = plan
-    handle = _WsHandle(_POOL.acquire(wsb, x.device))
+    handle = _WsHandle(wsb, x.device)
     ws = handle.ws
     pred = torch.empty(N, O, dtype=torch.float32, device=x.device)
     hidden = torch.empty(N, Cdim, dtype=torch.float32, device=x.device)
@@ -255,15 +304,11 @@ def _regt_forward_call(x: torch.Tensor, graph: PreparedGraph, regional: bool, sl
         _lib.check(lib.regt_forward(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), _lib.ptr(pred),
                                     _lib.ptr(hidden), _lib.ptr(ws), wsb, _stream()), "regt_forward")
     if forward_only:
-        _POOL.release(handle.ws)             # stream-ordered: the pool hands the block out again on this stream only
-        handle.ws = None
+        handle.release_now()
         return pred, hidden, None
-    st = _FwdState()
-    st.graph, st.regional, st.dims, st.handle, st.wsb = graph, regional, dims, handle, wsb
-    st.ps, st.gs = ps, gs                    # parameter / graph pointer structs: unchanged until backward
-    st.xp = x if packed else None
-    st.names, st.f_real, st.f_pad, st.params = names, f_real, f_pad, params
-    return pred, hidden, st
+    # (ps, gs: the parameter / graph pointer structs, unchanged until backward)
+    return pred, hidden, _FwdState(graph=graph, dims=dims, handle=handle, wsb=wsb, saved=params, regional=regional, ps=ps, gs=gs,
+                                   xp=x if packed else None, names=names, f_real=f_real, f_pad=f_pad)
 
 
 def regt_run(x: torch.Tensor, graph: PreparedGraph, regional: bool, slope: float, packed, *params: torch.Tensor):
@@ -288,27 +333,18 @@ class RegTGCNFunction(torch.autograd.Function):
         ctx.leaf_params = params                 # the caller's tensors (before any padding): whose .grad an accumulating backward updates
         ctx.set_materialize_grads(False)         # an output the loss does not use arrives as None in backward, not as a tensor of zeros
                                                  # (N x C floats filled and read back for nothing: `hidden` in every training loop)
-        pred, hidden, st = _regt_forward_call(x, graph, regional, slope, packed, params, False)
-        ctx.graph, ctx.regional, ctx.dims, ctx.ws, ctx.wsb = st.graph, st.regional, st.dims, st.handle.ws, st.wsb
-        ctx.ws_handle = st.handle
-        ctx.ps, ctx.gs = st.ps, st.gs
-        ctx.xp = st.xp
-        ctx.names = st.names
-        ctx.f_real, ctx.f_pad = st.f_real, st.f_pad
-        ctx.save_for_backward(hidden, *st.params)
+        pred, hidden, ctx.st = _regt_forward_call(x, graph, regional, slope, packed, params, False)
+        ctx.save_for_backward(hidden, *ctx.st.saved)
         return pred, hidden
 
     @staticmethod
     def backward(ctx, dpred, dhidden):
         lib = _lib.load()
         hidden, *params = ctx.saved_tensors
-        names, regional, dims = ctx.names, ctx.regional, ctx.dims
-        tens = dict(zip(names, params))
+        st = ctx.st
+        names, regional, dims = st.names, st.regional, st.dims
         dev = hidden.device
-        if dpred is None:
-            dpred = torch.zeros(dims.N, dims.O, dtype=torch.float32, device=dev)
-        dpred = dpred.contiguous()
-        dhid = None if dhidden is None else dhidden.contiguous()
+        dpred, dhid = _upstream_grads(dpred, dhidden, dims, dev)
         # one allocation for all gradients (16-byte aligned views), not one per parameter
         sizes = [(p_.numel() + 3) & ~3 for p_ in params]
         flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
@@ -317,25 +353,13 @@ class RegTGCNFunction(torch.autograd.Function):
             grads[n_] = flat[off:off + p_.numel()].view_as(p_)
             off += sz
         gr = _fill(_lib.Grads(), grads, regional)
-        _lib.check(lib.regt_backward(C.byref(dims), C.byref(ctx.gs), C.byref(ctx.ps), C.byref(gr), _lib.ptr(dpred), _lib.ptr(dhid),
-                                     _lib.ptr(hidden), _lib.ptr(ctx.xp), _lib.ptr(ctx.ws), ctx.wsb, _stream()), "regt_backward")
-        if ctx.f_pad:
+        _lib.check(lib.regt_backward(C.byref(dims), C.byref(st.gs), C.byref(st.ps), C.byref(gr), _lib.ptr(dpred), _lib.ptr(dhid),
+                                     _lib.ptr(hidden), _lib.ptr(st.xp), _lib.ptr(st.handle.ws), st.wsb, _stream()), "regt_backward")
+        if st.f_pad:
             for n_ in F_WIDE_PARAMS:
                 if n_ in grads:
-                    grads[n_] = grads[n_][:, :ctx.f_real].contiguous()
-        leaves = ctx.leaf_params
-        if _ACCUMULATE_IN_BACKWARD and all(p_.is_leaf and p_.requires_grad for p_ in leaves):
-            have, new = [], []
-            for n_, p_ in zip(names, leaves):
-                if p_.grad is None:
-                    p_.grad = grads[n_]          # (a view of this call's buffer, which nothing else refers to)
-                else:
-                    have.append(p_.grad)
-                    new.append(grads[n_])
-            if have:
-                torch._foreach_add_(have, new)
-            return (None, None, None, None, None) + (None,) * len(names)
-        return (None, None, None, None, None) + tuple(grads[n_] for n_ in names)
+                    grads[n_] = grads[n_][:, :st.f_real].contiguous()
+        return (None, None, None, None, None) + _deliver_grads(ctx.leaf_params, [grads[n_] for n_ in names])
 
 
 class MseLossFunction(torch.autograd.Function):
@@ -399,9 +423,7 @@ class FusedTrainStep:
         self.dims = _lib.Dims(N, T, F, Cdim, graph.num_regions, O, H1, 1 if self.regional else 0, float(slope), arith,
                               int(getattr(model, "call_flags", 0)))
         self.gs = _graph_struct(graph, T)
-        self.wsb = lib.regt_workspace_bytes(C.byref(self.dims), self.gs.n_chunks, self.gs.overlap)
-        if self.wsb == 0:
-            _lib.check(1, "regt_workspace_bytes")
+        self.wsb = _workspace_bytes("regt_workspace_bytes", C.byref(self.dims), self.gs.n_chunks, self.gs.overlap)
         self.ws = torch.empty(self.wsb, dtype=torch.uint8, device=dev)
         total = sum(p_.numel() for p_ in self.params)
         pad = [(-p_.numel()) % 4 for p_ in self.params]              # keep every view 16-byte aligned
@@ -457,14 +479,8 @@ class FusedTrainStep:
 
 # ---- models whose embedding stage is not the regional one: cell on a caller-supplied hidden input ---------------------
 
-PARAM_NAMES_CELL = (
-    ["tgnn._attention"]
-    + [f"tgnn._base_tgcn.conv_{k}.lin.weight" for k in GATES]
-    + [f"tgnn._base_tgcn.conv_{k}.bias" for k in GATES]
-    + [f"tgnn._base_tgcn.linear_{k}.weight" for k in GATES]
-    + [f"tgnn._base_tgcn.linear_{k}.bias" for k in GATES]
-    + PARAM_NAMES_HEAD
-)
+# the common list without the Chebyshev embedding ("tgnn.conv.*"), then the head
+PARAM_NAMES_CELL = [n_ for n_ in PARAM_NAMES_COMMON if not n_.startswith("tgnn.conv.")] + PARAM_NAMES_HEAD
 
 
 def _gcn_graph_struct(op) -> _lib.Graph:
@@ -474,8 +490,8 @@ def _gcn_graph_struct(op) -> _lib.Graph:
 
 
 def _cell_forward_call(x, h_in, op, params, forward_only: bool):
-    """regt_cell_forward behind :class:`CellFunction` and :func:`cell_run`: ``(pred, hidden, h_in, dims, handle, wsb)``; the
-    workspace block of a forward-only call is back in the pool (handle None)."""
+    """regt_cell_forward behind :class:`CellFunction` and :func:`cell_run`: returns ``(pred, hidden, state)``; ``state`` is None for
+    a forward-only call (its workspace block is back in the pool)."""
     lib = _lib.load()
     if not x.is_cuda:
         raise _lib.RegtError("RegT-GCN forward needs CUDA/HIP tensors: there is no CPU path in this package")
@@ -494,22 +510,19 @@ def _cell_forward_call(x, h_in, op, params, forward_only: bool):
     dims = _lib.Dims(N, T, F, Cdim, 1, O, H1, 0, 0.0, 0, _lib.DIMS_FORWARD_ONLY if forward_only else 0)
     gs = _gcn_graph_struct(op)
     if forward_only:
-        wsb = lib.regt_forward_only_workspace_bytes(C.byref(dims), C.byref(gs))
+        wsb = _workspace_bytes("regt_forward_only_workspace_bytes", C.byref(dims), C.byref(gs))
     else:
-        wsb = lib.regt_workspace_bytes(C.byref(dims), 0, 0)
-    if wsb == 0:
-        _lib.check(1, "regt_forward_only_workspace_bytes" if forward_only else "regt_workspace_bytes")
-    handle = _WsHandle(_POOL.acquire(wsb, x.device))
+        wsb = _workspace_bytes("regt_workspace_bytes", C.byref(dims), 0, 0)
+    handle = _WsHandle(wsb, x.device)
     pred = torch.empty(N, O, dtype=torch.float32, device=x.device)
     hidden = torch.empty(N, Cdim, dtype=torch.float32, device=x.device)
     ps = _fill(_lib.Params(), tens, False)
     _lib.check(lib.regt_cell_forward(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), _lib.ptr(h_in), _lib.ptr(pred),
                                      _lib.ptr(hidden), _lib.ptr(handle.ws), wsb, _stream()), "regt_cell_forward")
     if forward_only:
-        _POOL.release(handle.ws)             # stream-ordered, as in _regt_forward_call
-        handle.ws = None
-        handle = None
-    return pred, hidden, h_in, dims, handle, wsb
+        handle.release_now()
+        return pred, hidden, None
+    return pred, hidden, _FwdState(graph=op, dims=dims, handle=handle, wsb=wsb, saved=(h_in, *params))
 
 
 def cell_run(x, h_in, op, *params):
@@ -525,9 +538,8 @@ class CellFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h_in, op, *params):
-        pred, hidden, h_in, dims, handle, wsb = _cell_forward_call(x, h_in, op, params, False)
-        ctx.op, ctx.dims, ctx.ws_handle, ctx.wsb = op, dims, handle, wsb
-        ctx.save_for_backward(hidden, h_in, *params)
+        pred, hidden, ctx.st = _cell_forward_call(x, h_in, op, params, False)
+        ctx.save_for_backward(hidden, *ctx.st.saved)
         ctx.set_materialize_grads(False)         # an unused output (hidden) arrives as None in backward, not as zeros
         return pred, hidden
 
@@ -535,20 +547,17 @@ class CellFunction(torch.autograd.Function):
     def backward(ctx, dpred, dhidden):
         lib = _lib.load()
         hidden, h_in, *params = ctx.saved_tensors
-        names, dims = PARAM_NAMES_CELL, ctx.dims
+        names, st = PARAM_NAMES_CELL, ctx.st
+        dims = st.dims
         tens = dict(zip(names, params))
-        dev = hidden.device
-        if dpred is None:
-            dpred = torch.zeros(dims.N, dims.O, dtype=torch.float32, device=dev)
-        dpred = dpred.contiguous()
-        dhid = None if dhidden is None else dhidden.contiguous()
+        dpred, dhid = _upstream_grads(dpred, dhidden, dims, hidden.device)
         grads = {n_: torch.empty_like(p_) for n_, p_ in tens.items()}
         dh_in = torch.empty_like(h_in)
-        gs = _gcn_graph_struct(ctx.op)
+        gs = _gcn_graph_struct(st.graph)
         ps = _fill(_lib.Params(), tens, False)
         gr = _fill(_lib.Grads(), grads, False)
         _lib.check(lib.regt_cell_backward(C.byref(dims), C.byref(gs), C.byref(ps), C.byref(gr), _lib.ptr(dpred), _lib.ptr(dhid),
-                                          _lib.ptr(hidden), _lib.ptr(h_in), _lib.ptr(dh_in), _lib.ptr(ctx.ws_handle.ws), ctx.wsb,
+                                          _lib.ptr(hidden), _lib.ptr(h_in), _lib.ptr(dh_in), _lib.ptr(st.handle.ws), st.wsb,
                                           _stream()), "regt_cell_backward")
         return (None, dh_in, None) + tuple(grads[n_] for n_ in names)
 
@@ -612,10 +621,8 @@ class Cell0Function(torch.autograd.Function):
         dims = _lib.Dims(num_nodes, T, max(kz, kh), Cdim, 1, O, H1, 0, 0.0)
         args = _lib.Cell0Args(a_z.data_ptr(), a_h.data_ptr(), kz, kh, gz.data_ptr(), gh.data_ptr(), cz.data_ptr(), ch.data_ptr(),
                               att.data_ptr(), l1w.data_ptr(), l1b.data_ptr(), l2w.data_ptr(), l2b.data_ptr())
-        wsb = lib.regt_cell0_workspace_bytes(C.byref(dims), kz, kh)
-        if wsb == 0:
-            raise _lib.RegtError("regt_cell0_workspace_bytes: bad dims")
-        handle = _WsHandle(_POOL.acquire(wsb, a_z.device))
+        wsb = _workspace_bytes("regt_cell0_workspace_bytes", C.byref(dims), kz, kh)
+        handle = _WsHandle(wsb, a_z.device)
         pred = torch.empty(num_nodes, O, dtype=torch.float32, device=a_z.device)
         hidden = torch.empty(num_nodes, Cdim, dtype=torch.float32, device=a_z.device)
         _lib.check(lib.regt_cell0_forward(C.byref(dims), C.byref(args), _lib.ptr(pred), _lib.ptr(hidden), _lib.ptr(handle.ws), wsb,
@@ -630,11 +637,7 @@ class Cell0Function(torch.autograd.Function):
         lib = _lib.load()
         hidden, a_z, a_h, gz, gh, cz, ch, att, l1w, l1b, l2w, l2b = ctx.saved_tensors
         dims = ctx.dims
-        dev = hidden.device
-        if dpred is None:
-            dpred = torch.zeros(dims.N, dims.O, dtype=torch.float32, device=dev)
-        dpred = dpred.contiguous()
-        dhid = None if dhidden is None else dhidden.contiguous()
+        dpred, dhid = _upstream_grads(dpred, dhidden, dims, hidden.device)
         need_az, need_ah = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         d_az = torch.empty_like(a_z) if need_az else None
         d_ah = torch.empty_like(a_h) if need_ah else None
@@ -714,37 +717,7 @@ class STNormFunction(torch.autograd.Function):
         # the last layer's residual conv feeds nothing: None, as autograd gives the reference module (no weight decay step either)
         last = ops.STNORM_HEAD + ops.STNORM_PER_LAYER * (ctx.dims.blocks * ctx.dims.layers - 1)
         grads[last + 4] = grads[last + 5] = None
-        live = [(p, g) for p, g in zip(params, grads) if p is not None and g is not None]
-        if _ACCUMULATE_IN_BACKWARD and all(p.is_leaf and p.requires_grad for p, _ in live):
-            have, new = [], []
-            for p, g in live:
-                if p.grad is None:
-                    p.grad = g
-                else:
-                    have.append(p.grad)
-                    new.append(g)
-            if have:
-                torch._foreach_add_(have, new)
-            return (None, None, None) + (None,) * len(params)
-        return (None, None, None) + tuple(grads)
-
-
-def _deliver_grads(params, grads):
-    """Gradients of ``params`` as autograd's return values, or, under :func:`set_grad_accumulation_in_backward`, added to ``.grad``
-    here (one fused add) with None returned for each."""
-    live = [(p, g) for p, g in zip(params, grads) if p is not None and g is not None]
-    if _ACCUMULATE_IN_BACKWARD and all(p.is_leaf and p.requires_grad for p, _ in live):
-        have, new = [], []
-        for p, g in live:
-            if p.grad is None:
-                p.grad = g
-            else:
-                have.append(p.grad)
-                new.append(g)
-        if have:
-            torch._foreach_add_(have, new)
-        return (None,) * len(params)
-    return tuple(grads)
+        return (None, None, None) + _deliver_grads(params, grads)
 
 
 class STIDFunction(torch.autograd.Function):

@@ -29,27 +29,25 @@ def pack_x(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def pack_x_into(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-    """(N,F,T) -> rows [0, N) of ``out`` (>= N rows of (T,F)); the remaining rows are left alone (halo slots)."""
+def _pack_into(name: str, dtype, short: str, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     x = _f32c(x, "x")
     n, f, t = x.shape
-    if (out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device or out.dim() != 3
+    if (out.dtype != dtype or not out.is_contiguous() or out.device != x.device or out.dim() != 3
             or out.shape[0] < n or tuple(out.shape[1:]) != (t, f)):
-        raise ValueError(f"pack_x_into: out must be a contiguous fp32 (>= {n}, {t}, {f}) tensor on {x.device}")
-    _lib.check(_lib.load().regt_pack_x(_lib.ptr(x), _lib.ptr(out), n, f, t, _stream()), "regt_pack_x")
+        raise ValueError(f"{name}_into: out must be a contiguous {short} (>= {n}, {t}, {f}) tensor on {x.device}")
+    _lib.check(getattr(_lib.load(), "regt_" + name)(_lib.ptr(x), _lib.ptr(out), n, f, t, _stream()), "regt_" + name)
     return out
+
+
+def pack_x_into(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """(N,F,T) -> rows [0, N) of ``out`` (>= N rows of (T,F)); the remaining rows are left alone (halo slots)."""
+    return _pack_into("pack_x", torch.float32, "fp32", x, out)
 
 
 def pack_x_bf16_into(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """(N,F,T) fp32 -> rows [0, N) of the bf16 tensor ``out`` (>= N rows of (T,F)), rounded to nearest even (REGT_GEMM_MODE=bf16:
     the packed rows a region shard exchanges and hands to ``forward_packed``); F % 8 == 0."""
-    x = _f32c(x, "x")
-    n, f, t = x.shape
-    if (out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != x.device or out.dim() != 3
-            or out.shape[0] < n or tuple(out.shape[1:]) != (t, f)):
-        raise ValueError(f"pack_x_bf16_into: out must be a contiguous bf16 (>= {n}, {t}, {f}) tensor on {x.device}")
-    _lib.check(_lib.load().regt_pack_x_bf16(_lib.ptr(x), _lib.ptr(out), n, f, t, _stream()), "regt_pack_x_bf16")
-    return out
+    return _pack_into("pack_x_bf16", torch.bfloat16, "bf16", x, out)
 
 
 def spmm_dual_bf16(rowptr, col, val_a, val_l, x: torch.Tensor):
@@ -210,15 +208,46 @@ def stnorm_dims(n: int, batch: int, tnorm_group: int, seq_len: int, in_dim: int,
                            int(bool(training)))
 
 
+def _sizes(entry: str, dims):
+    ws, sc = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(getattr(_lib.load(), entry)(ctypes.byref(dims), ctypes.byref(ws), ctypes.byref(sc)), entry)
+    return ws.value, sc.value
+
+
 def stnorm_sizes(dims: _lib.StnormDims):
     """(workspace floats, scratch floats) of regt_stnorm_forward / _backward."""
-    ws, sc = ctypes.c_size_t(), ctypes.c_size_t()
-    _lib.check(_lib.load().regt_stnorm_sizes(ctypes.byref(dims), ctypes.byref(ws), ctypes.byref(sc)), "regt_stnorm_sizes")
-    return ws.value, sc.value
+    return _sizes("regt_stnorm_sizes", dims)
 
 
 def _ptr_table(tensors):
     return (ctypes.c_void_p * max(1, len(tensors)))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _check_table(what: str, kind: str, tensors, shapes, device, off: str = ""):
+    """RegtError unless every entry of ``tensors`` is a contiguous float32 tensor of its shape in ``shapes`` on ``device``, or None
+    where the shape is None (``off`` names the switch that is off there): the kernels read the entries through raw device pointers."""
+    for i, (t, shape) in enumerate(zip(tensors, shapes)):
+        if shape is None:
+            if t is not None:
+                raise _lib.RegtError(f"{what}: {kind} entry {i} must be None ({off})")
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise _lib.RegtError(f"{what}: {kind} entry {i} is missing")
+        if t.dtype != torch.float32 or t.device != torch.device(device) or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise _lib.RegtError(f"{what}: {kind} entry {i} must be a contiguous float32 {shape} tensor on {device}, got "
+                                 f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else " (not contiguous)"))
+
+
+def _check_dout(dout: torch.Tensor, shape, device):
+    if tuple(dout.shape) != shape or dout.device != device:
+        raise ValueError(f"dout must be {shape} on {device}, got {tuple(dout.shape)} on {dout.device}")
+
+
+def _check_ws(ws: Optional[torch.Tensor], floats: int, device, source: str, saved=True):
+    """``ws`` has to be what ``source`` left for the backward: the kernels read ``floats`` floats of it (``saved``: the forward's
+    dims said so)."""
+    if not saved or ws is None or ws.dtype != torch.float32 or ws.device != device or ws.numel() != floats or not ws.is_contiguous():
+        raise ValueError(f"ws must be the workspace {source} returned for these dims")
 
 
 def stnorm_out_len(seq_len: int, blocks: int, layers: int) -> int:
@@ -245,17 +274,8 @@ def stnorm_check_tables(dims: _lib.StnormDims, device, params, running, what: st
     shapes, rshapes = stnorm_table_shapes(dims)
     if len(params) != len(shapes) or len(running) != len(rshapes):
         raise _lib.RegtError(f"{what}: expected {len(shapes)} parameter and {len(rshapes)} buffer entries, got {len(params)}, {len(running)}")
-    for kind, tabs, exp in (("parameter", params, shapes), ("running buffer", running, rshapes)):
-        for i, (t, shape) in enumerate(zip(tabs, exp)):
-            if shape is None:
-                if t is not None:
-                    raise _lib.RegtError(f"{what}: {kind} entry {i} must be None (TNorm / SNorm off)")
-                continue
-            if t is None or not isinstance(t, torch.Tensor):
-                raise _lib.RegtError(f"{what}: {kind} entry {i} is missing")
-            if t.dtype != torch.float32 or t.device != torch.device(device) or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise _lib.RegtError(f"{what}: {kind} entry {i} must be a contiguous float32 {shape} tensor on {device}, got "
-                                     f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else " (not contiguous)"))
+    _check_table(what, "parameter", params, shapes, device, "TNorm / SNorm off")
+    _check_table(what, "running buffer", running, rshapes, device)
 
 
 def stnorm_forward(dims: _lib.StnormDims, x: torch.Tensor, params, running):
@@ -282,10 +302,8 @@ def stnorm_backward(dims: _lib.StnormDims, x: torch.Tensor, params, running, dou
     stnorm_check_tables(dims, x.device, params, running, "regt_stnorm_backward")
     ws_n, sc_n = stnorm_sizes(dims)
     out_shape = (dims.batch, dims.out_dim, dims.num_nodes, stnorm_out_len(dims.seq_len, dims.blocks, dims.layers))
-    if tuple(dout.shape) != out_shape or dout.device != x.device:
-        raise ValueError(f"dout must be {out_shape} on {x.device}, got {tuple(dout.shape)} on {dout.device}")
-    if ws.dtype != torch.float32 or ws.device != x.device or ws.numel() != ws_n or not ws.is_contiguous():
-        raise ValueError("ws must be the workspace stnorm_forward returned for these dims")
+    _check_dout(dout, out_shape, x.device)
+    _check_ws(ws, ws_n, x.device, "stnorm_forward")
     sc = torch.empty(sc_n, dtype=torch.float32, device=x.device)
     grads = [None if p is None else torch.empty_like(p) for p in params]
     pt, rt, gt = _ptr_table(params), _ptr_table(running), _ptr_table(grads)
@@ -330,9 +348,7 @@ def stid_hidden(dims: _lib.StidDims) -> int:
 
 def stid_sizes(dims: _lib.StidDims):
     """(workspace floats, scratch floats) of regt_stid_forward / _backward."""
-    ws, sc = ctypes.c_size_t(), ctypes.c_size_t()
-    _lib.check(_lib.load().regt_stid_sizes(ctypes.byref(dims), ctypes.byref(ws), ctypes.byref(sc)), "regt_stid_sizes")
-    return ws.value, sc.value
+    return _sizes("regt_stid_sizes", dims)
 
 
 def stid_table_shapes(dims: _lib.StidDims):
@@ -351,16 +367,7 @@ def stid_check_tables(dims: _lib.StidDims, device, params, what: str = "STID"):
     shapes = stid_table_shapes(dims)
     if len(params) != len(shapes):
         raise _lib.RegtError(f"{what}: expected {len(shapes)} parameter entries, got {len(params)}")
-    for i, (t, shape) in enumerate(zip(params, shapes)):
-        if shape is None:
-            if t is not None:
-                raise _lib.RegtError(f"{what}: parameter entry {i} must be None (if_node off)")
-            continue
-        if t is None or not isinstance(t, torch.Tensor):
-            raise _lib.RegtError(f"{what}: parameter entry {i} is missing")
-        if t.dtype != torch.float32 or t.device != torch.device(device) or not t.is_contiguous() or tuple(t.shape) != shape:
-            raise _lib.RegtError(f"{what}: parameter entry {i} must be a contiguous float32 {shape} tensor on {device}, got "
-                                 f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else " (not contiguous)"))
+    _check_table(what, "parameter", params, shapes, device, "if_node off")
 
 
 def stid_keep_shape(dims: _lib.StidDims):
@@ -406,10 +413,8 @@ def stid_backward(dims: _lib.StidDims, x: torch.Tensor, params, keep: Optional[t
     kp = _stid_keep_ptr(dims, keep, x.device)
     ws_n, sc_n = stid_sizes(dims)
     out_shape = (dims.batch, dims.output_len, dims.num_nodes, 1)
-    if tuple(dout.shape) != out_shape or dout.device != x.device:
-        raise ValueError(f"dout must be {out_shape} on {x.device}, got {tuple(dout.shape)} on {dout.device}")
-    if ws is None or ws.dtype != torch.float32 or ws.device != x.device or ws.numel() != ws_n or not ws.is_contiguous():
-        raise ValueError("ws must be the workspace stid_forward(save=True) returned for these dims")
+    _check_dout(dout, out_shape, x.device)
+    _check_ws(ws, ws_n, x.device, "stid_forward(save=True)")
     sc = torch.empty(sc_n, dtype=torch.float32, device=x.device)
     grads = [None if p is None else torch.empty_like(p) for p in params]
     _lib.check(_lib.load().regt_stid_backward(ctypes.byref(dims), _lib.ptr(x), _ptr_table(params), kp, _lib.ptr(dout), _ptr_table(grads),
@@ -439,9 +444,7 @@ def gru_dims(seq_len: int, rows: int, input_size: int, x_strides=None, training:
 
 def gru_sizes(dims: _lib.GruDims):
     """(workspace floats, scratch floats) of regt_gru_forward / _backward."""
-    ws, sc = ctypes.c_size_t(), ctypes.c_size_t()
-    _lib.check(_lib.load().regt_gru_sizes(ctypes.byref(dims), ctypes.byref(ws), ctypes.byref(sc)), "regt_gru_sizes")
-    return ws.value, sc.value
+    return _sizes("regt_gru_sizes", dims)
 
 
 def _gru_x(x: torch.Tensor) -> torch.Tensor:
@@ -461,12 +464,7 @@ def gru_check_weights(input_size: int, device, weights, what: str = "GRU"):
     shapes = [(g, input_size), (g, GRU_HIDDEN), (g,), (g,)]
     if len(weights) != 4:
         raise _lib.RegtError(f"{what}: expected weight_ih, weight_hh, bias_ih, bias_hh, got {len(weights)} entries")
-    for i, (t, shape) in enumerate(zip(weights, shapes)):
-        if not isinstance(t, torch.Tensor):
-            raise _lib.RegtError(f"{what}: weight entry {i} is missing")
-        if t.dtype != torch.float32 or t.device != torch.device(device) or not t.is_contiguous() or tuple(t.shape) != shape:
-            raise _lib.RegtError(f"{what}: weight entry {i} must be a contiguous float32 {shape} tensor on {device}, got "
-                                 f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else " (not contiguous)"))
+    _check_table(what, "weight", weights, shapes, device)
 
 
 def _gru_state(t: Optional[torch.Tensor], rows: int, dev, name: str) -> Optional[torch.Tensor]:
@@ -510,14 +508,12 @@ def gru_backward(dims: _lib.GruDims, x: torch.Tensor, weights, dout: Optional[to
     gru_check_weights(dims.input_size, x.device, weights, "regt_gru_backward")
     if dout is not None:
         dout = _f32c(dout, "dout")
-        if tuple(dout.shape) != (dims.seq_len, dims.rows, GRU_HIDDEN) or dout.device != x.device:
-            raise ValueError(f"dout must be {(dims.seq_len, dims.rows, GRU_HIDDEN)} on {x.device}, got {tuple(dout.shape)} on {dout.device}")
+        _check_dout(dout, (dims.seq_len, dims.rows, GRU_HIDDEN), x.device)
     dh_last = _gru_state(dh_last, dims.rows, x.device, "dh_last")
     if dout is None and dh_last is None:
         raise ValueError("gru_backward: dout and dh_last are both None")
     ws_n, sc_n = gru_sizes(dims)
-    if ws is None or ws.dtype != torch.float32 or ws.device != x.device or ws.numel() != ws_n or not ws.is_contiguous() or not dims.training:
-        raise ValueError("ws must be the workspace gru_forward(save=True) returned for these dims")
+    _check_ws(ws, ws_n, x.device, "gru_forward(save=True)", dims.training)
     sc = torch.empty(sc_n, dtype=torch.float32, device=x.device)
     grads = [torch.empty_like(w) for w in weights]
     dh0 = torch.empty(1, dims.rows, GRU_HIDDEN, dtype=torch.float32, device=x.device) if want_dh0 else None

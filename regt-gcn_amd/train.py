@@ -44,15 +44,12 @@ def train_epoch(model, xs: Sequence[torch.Tensor], ys: Sequence[torch.Tensor], g
         return losses[-1][0], [l[0] for l in losses]
     # (the gradients of the epoch's snapshots add up in .grad, run.py:178-194: the model's backward does that addition itself, one
     # multi-tensor add instead of one autograd add per parameter -- functional.set_grad_accumulation_in_backward)
-    prev = F_.set_grad_accumulation_in_backward(True)
-    try:
+    with F_.grad_accumulation_in_backward():
         for x, y in zip(xs, ys):
             out, _ = model.forward_prepared(x, graph)
             loss = F_.mse_loss(out, y)               # torch.mean((out - y) ** 2), run.py:180, value and gradient in one kernel
             loss.backward()
             losses.append(loss.detach())
-    finally:
-        F_.set_grad_accumulation_in_backward(prev)
     allreduce_gradients(list(model.parameters()))
     optimizer.step()
     optimizer.zero_grad()
@@ -87,6 +84,11 @@ class WindowStore:
     def __len__(self):
         return self.X.shape[0]
 
+    def batches(self, snap_batch: int):
+        """(first snapshot i, count b) of every batch of ``snap_batch`` consecutive snapshots; the last one may be shorter."""
+        for i in range(0, len(self), snap_batch):
+            yield i, min(snap_batch, len(self) - i)
+
     def batch(self, i: int, b: int):
         x, y = self.X[i:i + b], self.Y[i:i + b]
         return x.reshape(-1, x.shape[2], x.shape[3]), y.reshape(-1, y.shape[2])
@@ -109,16 +111,12 @@ def train_epoch_batched(model, store: WindowStore, graphs: BatchedGraphs, optimi
     model.train()
     losses = []
     n_o = store.Y.shape[1] * store.Y.shape[2]                 # entries of ONE snapshot: the divisor of run.py:180's mean
-    prev = F_.set_grad_accumulation_in_backward(True)
-    try:
-        for i in range(0, len(store), snap_batch):
-            b = min(snap_batch, len(store) - i)
+    with F_.grad_accumulation_in_backward():
+        for i, b in store.batches(snap_batch):
             x, y = store.batch(i, b)
             out, _ = model.forward_prepared(x, graphs.get(b))
             F_.mse_loss(out, y, n_o).backward()               # = the sum of the b snapshot means: gradients add up as in run.py
             losses.append(((out.detach() - y) ** 2).view(b, -1).mean(dim=1))
-    finally:
-        F_.set_grad_accumulation_in_backward(prev)
     allreduce_gradients(list(model.parameters()))
     optimizer.step()
     optimizer.zero_grad()
@@ -131,8 +129,7 @@ def evaluate_batched(model, store: WindowStore, graphs: BatchedGraphs, snap_batc
     """run.py::test() with ``snap_batch`` snapshots per forward: (rmse, mse)."""
     model.eval()
     se = torch.zeros((), dtype=torch.float64, device=store.X.device)
-    for i in range(0, len(store), snap_batch):
-        b = min(snap_batch, len(store) - i)
+    for i, b in store.batches(snap_batch):
         x, y = store.batch(i, b)
         se += ((model.forward_prepared(x, graphs.get(b))[0] - y) ** 2).sum(dtype=torch.float64)
     m = float(se) / float(store.Y.numel())
@@ -150,8 +147,7 @@ def train_epoch_sharded(model, xs: Sequence[torch.Tensor], ys: Sequence[torch.Te
     losses = []
     if len(xs):
         pipe.submit(0, xs[0])
-    prev = F_.set_grad_accumulation_in_backward(True)
-    try:
+    with F_.grad_accumulation_in_backward():
         for i, (x, y) in enumerate(zip(xs, ys)):
             buf = pipe.acquire(i % 2)
             if i + 1 < len(xs):
@@ -161,8 +157,6 @@ def train_epoch_sharded(model, xs: Sequence[torch.Tensor], ys: Sequence[torch.Te
             loss.backward()
             pipe.release(i % 2)
             losses.append(loss.detach())
-    finally:
-        F_.set_grad_accumulation_in_backward(prev)
     allreduce_gradients(list(model.parameters()), group)
     tot = allreduce_sum(torch.stack(losses), group)
     optimizer.step()
@@ -213,21 +207,17 @@ def stnorm_batch(store: "WindowStore", i: int, b: int):
     return store.X[i:i + b].permute(0, 3, 1, 2), store.Y[i:i + b]
 
 
-def _train_epoch_windows(model, store: "WindowStore", optimizer, snap_batch: int, call) -> Tuple[torch.Tensor, List[torch.Tensor]]:
-    """run.py::train() for the models fed (b, T, N, F) windows; ``call(x, i, b)`` runs the model on snapshots i .. i+b-1."""
+def _train_epoch_windows(model, store: "WindowStore", optimizer, snap_batch: int, batch, losses_of) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """run.py::train() for the models without a graph: gradients accumulate over the epoch, one optimizer step at its end; returns
+    (last snapshot's loss, all per-snapshot losses).  ``batch(store, i, b)`` gives snapshots i .. i+b-1 as the model's input and
+    their targets, ``losses_of(x, y, i, b)`` runs the model on them and returns the b per-snapshot losses."""
     model.train()
     losses = []
-    prev = F_.set_grad_accumulation_in_backward(True)
-    try:
-        for i in range(0, len(store), snap_batch):
-            b = min(snap_batch, len(store) - i)
-            x, y = stnorm_batch(store, i, b)
-            out = call(x, i, b)
-            per = ((out - y.unsqueeze(1)) ** 2).mean(dim=(1, 2, 3))       # run.py:184 / :186 per snapshot
+    with F_.grad_accumulation_in_backward():
+        for i, b in store.batches(snap_batch):
+            per = losses_of(*batch(store, i, b), i, b)
             per.sum().backward()
             losses.append(per.detach())
-    finally:
-        F_.set_grad_accumulation_in_backward(prev)
     optimizer.step()
     optimizer.zero_grad()
     all_l = torch.cat(losses)
@@ -235,42 +225,46 @@ def _train_epoch_windows(model, store: "WindowStore", optimizer, snap_batch: int
 
 
 @torch.no_grad()
-def _evaluate_windows(model, store: "WindowStore", snap_batch: int, call) -> Tuple[float, float]:
-    """run.py::test() for the same models: (rmse, mse) of out[0][0] against y."""
+def _evaluate_windows(model, store: "WindowStore", snap_batch: int, batch, errors_of) -> Tuple[float, float]:
+    """run.py::test() for the same models: (rmse, mse) over all snapshots; ``errors_of(x, y, i, b)`` runs the model on a batch
+    and returns prediction - target for every entry run.py compares."""
     model.eval()
     se = torch.zeros((), dtype=torch.float64, device=store.X.device)
     count = 0
-    for i in range(0, len(store), snap_batch):
-        b = min(snap_batch, len(store) - i)
-        x, y = stnorm_batch(store, i, b)
-        e = (call(x, i, b)[:, 0] - y) ** 2
+    for i, b in store.batches(snap_batch):
+        e = errors_of(*batch(store, i, b), i, b) ** 2
         se += e.sum(dtype=torch.float64)
         count += e.numel()
     m = float(se) / float(max(count, 1))
     return m ** 0.5, m
 
 
+def _window_losses(out: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    return ((out - y.unsqueeze(1)) ** 2).mean(dim=(1, 2, 3))              # run.py:184 / :186 per snapshot
+
+
 def train_epoch_stnorm(model, store: "WindowStore", optimizer, snap_batch: int) -> Tuple[torch.Tensor, List[torch.Tensor]]:
     """run.py::train() for STNorm; returns (last snapshot's loss, all per-snapshot losses)."""
-    return _train_epoch_windows(model, store, optimizer, snap_batch, lambda x, i, b: model(x, tnorm_group=1))
+    return _train_epoch_windows(model, store, optimizer, snap_batch, stnorm_batch,
+                                lambda x, y, i, b: _window_losses(model(x, tnorm_group=1), y))
 
 
 def evaluate_stnorm(model, store: "WindowStore", snap_batch: int) -> Tuple[float, float]:
     """run.py::test() for STNorm: (rmse, mse) of out[0][0] against y."""
-    return _evaluate_windows(model, store, snap_batch, lambda x, i, b: model(x, tnorm_group=1))
+    return _evaluate_windows(model, store, snap_batch, stnorm_batch, lambda x, y, i, b: model(x, tnorm_group=1)[:, 0] - y)
 
 
 def train_epoch_stid(model, store: "WindowStore", optimizer, snap_batch: int,
                      keeps: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[torch.Tensor]]:
     """run.py::train() for STID; returns (last snapshot's loss, all per-snapshot losses).  ``keeps``: the dropout keep bits of all
     snapshots, int32 (num_layer, len(store), N, hidden / 32), instead of a fresh draw per call."""
-    return _train_epoch_windows(model, store, optimizer, snap_batch,
-                                lambda x, i, b: model(x, keep=None if keeps is None else keeps[:, i:i + b].contiguous()))
+    return _train_epoch_windows(model, store, optimizer, snap_batch, stnorm_batch, lambda x, y, i, b: _window_losses(
+        model(x, keep=None if keeps is None else keeps[:, i:i + b].contiguous()), y))
 
 
 def evaluate_stid(model, store: "WindowStore", snap_batch: int) -> Tuple[float, float]:
     """run.py::test() for STID: (rmse, mse) of out[0][0] (N, 1) against y (N, O)."""
-    return _evaluate_windows(model, store, snap_batch, lambda x, i, b: model(x))
+    return _evaluate_windows(model, store, snap_batch, stnorm_batch, lambda x, y, i, b: model(x)[:, 0] - y)
 
 
 # ---- StackedGRU (run.py:174-176, 210-212) --------------------------------------------------------------------------------------------
@@ -295,38 +289,13 @@ def _gru_last_rows(out: torch.Tensor, b: int) -> torch.Tensor:
 def train_epoch_gru(model, store: "WindowStore", optimizer, snap_batch: int) -> Tuple[torch.Tensor, List[torch.Tensor]]:
     """run.py::train() for StackedGRU: gradients accumulate over the epoch, one optimizer step at its end; returns (last snapshot's
     loss, all per-snapshot losses)."""
-    model.train()
-    losses = []
-    prev = F_.set_grad_accumulation_in_backward(True)
-    try:
-        for i in range(0, len(store), snap_batch):
-            b = min(snap_batch, len(store) - i)
-            x, y = gru_batch(store, i, b)
-            per = ((_gru_last_rows(model(x), b) - y) ** 2).mean(dim=(1, 2))      # run.py:176 per snapshot
-            per.sum().backward()
-            losses.append(per.detach())
-    finally:
-        F_.set_grad_accumulation_in_backward(prev)
-    optimizer.step()
-    optimizer.zero_grad()
-    all_l = torch.cat(losses)
-    return all_l[-1], list(all_l.unbind(0))
+    return _train_epoch_windows(model, store, optimizer, snap_batch, gru_batch,                # (run.py:176 per snapshot)
+                                lambda x, y, i, b: ((_gru_last_rows(model(x), b) - y) ** 2).mean(dim=(1, 2)))
 
 
-@torch.no_grad()
 def evaluate_gru(model, store: "WindowStore", snap_batch: int) -> Tuple[float, float]:
     """run.py::test() for StackedGRU: (rmse, mse) of out[:, -1, :] against y."""
-    model.eval()
-    se = torch.zeros((), dtype=torch.float64, device=store.X.device)
-    count = 0
-    for i in range(0, len(store), snap_batch):
-        b = min(snap_batch, len(store) - i)
-        x, y = gru_batch(store, i, b)
-        e = (_gru_last_rows(model(x), b) - y) ** 2
-        se += e.sum(dtype=torch.float64)
-        count += e.numel()
-    m = float(se) / float(max(count, 1))
-    return m ** 0.5, m
+    return _evaluate_windows(model, store, snap_batch, gru_batch, lambda x, y, i, b: _gru_last_rows(model(x), b) - y)
 
 
 def build_parser() -> argparse.ArgumentParser:

@@ -206,6 +206,31 @@ def test_backward_is_bit_identical_across_runs():
     assert all(torch.equal(a, b) for a, b in zip(*runs))
 
 
+def test_accumulation_in_backward_gives_the_same_bits():
+    """GRUFunction and MLPHeadFunction under set_grad_accumulation_in_backward: two backwards in turn (the first hands its gradient
+    tensors over as ``.grad``, the second adds to them) leave the ``.grad`` autograd's own accumulation leaves.  Nine rows cross the
+    8-row tile a workgroup owns, nine steps make a real recurrence."""
+    import regtgcn_amd as R
+    torch.manual_seed(7)
+    mod = R.StackedGRU(6, 8, 6, 1).to(DEV)
+    gen = torch.Generator().manual_seed(17)
+    xs = [torch.randn(9, 9, 6, generator=gen).to(DEV) for _ in range(2)]
+    assert not torch.equal(xs[0], xs[1])
+    runs = {}
+    for flag in (False, True):
+        prev = R.functional.set_grad_accumulation_in_backward(flag)
+        try:
+            mod.zero_grad(set_to_none=True)
+            for x in xs:
+                mod(x).square().sum().backward()
+        finally:
+            R.functional.set_grad_accumulation_in_backward(prev)
+        runs[flag] = {k: p.grad.clone() for k, p in mod.named_parameters()}
+    assert list(runs[True]) == KEYS and len(KEYS) == 12
+    for k in KEYS:
+        assert float(runs[False][k].abs().max()) > 0 and torch.equal(runs[True][k], runs[False][k]), k
+
+
 @pytest.mark.parametrize("snap_batch", [4, 64])
 def test_snap_batch_equals_sequential_calls(snap_batch):
     import regtgcn_amd as R
