@@ -438,6 +438,52 @@ int32_t regt_gru_backward(const regt_gru_dims* dims, const float* x, const float
                           const float* dh_last, float* const* grads, float* dh0, const float* workspace, float* scratch,
                           regt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * STAEformer (models/STAEformer.py), INFERENCE only (dropout is the identity; nothing is kept for a backward), with
+ * use_mixed_proj = True.  run.py:132 builds it with tod_embedding_dim = 0: model_dim = 24 + 24 + 80 = 128, 4 heads of 32.
+ *   x (batch, in_steps, num_nodes, in_features) -- the reference's forward input; the first input_dim features feed input_proj,
+ *   feature 1 * steps_per_day indexes tod_embedding and feature 2 indexes dow_embedding, truncated toward zero as .long() does
+ *   and then CLAMPED into the table (negative or NaN -> row 0, too large -> the last row; the reference raises there): nothing
+ *   outside a table is read.  out (batch, out_steps, num_nodes, output_dim).
+ *   model_dim = input_embedding_dim + tod_embedding_dim + dow_embedding_dim + spatial_embedding_dim + adaptive_embedding_dim,
+ *   concatenated in that order; a block of width 0 is absent.
+ *   params: device pointers in state_dict order: node_emb (num_nodes, spatial), adaptive_embedding (in_steps, num_nodes,
+ *   adaptive), input_proj.weight (input_embedding_dim, input_dim), .bias, tod_embedding.weight (steps_per_day, tod),
+ *   dow_embedding.weight (days_per_week, dow) -- NULL where the width is 0 --, output_proj.weight (out_steps * output_dim,
+ *   in_steps * model_dim), .bias; then 16 per layer, the num_layers temporal layers first, then the num_layers spatial ones:
+ *   attn.FC_Q.weight, .bias, attn.FC_K.*, attn.FC_V.*, attn.out_proj.*, feed_forward.0.*, feed_forward.2.*, ln1.weight, .bias,
+ *   ln2.weight, .bias: 8 + 32 * num_layers entries.
+ *   workspace: workspace_floats floats from regt_stae_sizes (REGT_ERR_ARG outside the limits), 16-byte aligned: two activation
+ *   buffers, Q|K|V, the attention output and the feed-forward hidden.
+ *   Limits: head width model_dim / num_heads == 32; model_dim % 32 == 0, model_dim <= 256; feed_forward_dim % 32 == 0,
+ *   feed_forward_dim <= 1024; 1 <= in_steps <= 255; 1 <= num_layers <= 8; 1 <= input_dim <= in_features <= 256 (in_features >= 2
+ *   / >= 3 with a time-of-day / day-of-week embedding); out_steps * output_dim <= 64; use_mixed_proj == 1; input_embedding_dim >= 1;
+ *   steps_per_day, days_per_week, batch, num_nodes >= 1; ln_eps > 0.  Every table entry must be a contiguous fp32 device tensor of
+ *   the reference's shape (regtgcn_amd.ops checks that before the call).  Sums run in a fixed order without float atomics:
+ *   bit-reproducible.
+ *
+ * regt_stae_attention: multi-head self-attention softmax(Q K^T / sqrt(32)) V along one axis of a (B, T, N, 32 * heads) tensor whose
+ *   rows (b T + t) N + n lie ld floats apart in q, k and v (three pointers, possibly column windows of one buffer) and ldo floats
+ *   apart in out.  axis = 1: along T, one sequence per (b, n); axis = 2: along N, one sequence per (b, t).  Head h owns columns
+ *   [32 h, 32 h + 32).  Any sequence length; no score matrix is formed in memory; no mask.  heads <= 8; ld, ldo multiples of 4 and
+ *   >= 32 * heads; q, k, v, out 16-byte aligned.  Only the M x 32 * heads window of out is written.
+ * regt_stae_add_layernorm: out = LayerNorm(residual + y) * gamma + beta over rows of D floats (biased variance, eps inside the
+ *   root, as nn.LayerNorm); dense rows; out may alias residual.  D % 32 == 0, 32 <= D <= 256; 1 <= M < 2^31.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t batch, in_steps, num_nodes, in_features, input_dim;
+    int32_t input_embedding_dim, tod_embedding_dim, dow_embedding_dim, spatial_embedding_dim, adaptive_embedding_dim;
+    int32_t steps_per_day, days_per_week, num_heads, feed_forward_dim, num_layers, out_steps, output_dim, use_mixed_proj;
+    float ln_eps;
+} regt_stae_dims;
+int32_t regt_stae_sizes(const regt_stae_dims* dims, size_t* workspace_floats);
+int32_t regt_stae_forward(const regt_stae_dims* dims, const float* x, const float* const* params, float* out, float* workspace,
+                          regt_stream_t stream);
+int32_t regt_stae_attention(const float* q, const float* k, const float* v, int64_t ld, int32_t batch, int32_t in_steps,
+                            int32_t num_nodes, int32_t heads, int32_t axis, float* out, int64_t ldo, regt_stream_t stream);
+int32_t regt_stae_add_layernorm(const float* residual, const float* y, const float* gamma, const float* beta, float eps, int64_t rows,
+                                int32_t width, float* out, regt_stream_t stream);
+
 /* relu's gradient in place: d[i] = 0 where y[i] <= 0, y the relu's output (the head of StackedGRU between two regt_linear calls).
  * 1 <= n < 2^31. */
 int32_t regt_relu_backward(const float* y, float* d, int64_t n, regt_stream_t stream);

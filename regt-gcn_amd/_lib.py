@@ -62,6 +62,13 @@ class GruDims(C.Structure):
                [(n, C.c_int64) for n in ("x_stride_seq", "x_stride_row", "x_stride_t")]
 
 
+class StaeDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "in_steps", "num_nodes", "in_features", "input_dim", "input_embedding_dim",
+                                         "tod_embedding_dim", "dow_embedding_dim", "spatial_embedding_dim", "adaptive_embedding_dim",
+                                         "steps_per_day", "days_per_week", "num_heads", "feed_forward_dim", "num_layers", "out_steps",
+                                         "output_dim", "use_mixed_proj")] + [("ln_eps", C.c_float)]
+
+
 class Graph(C.Structure):
     _fields_ = [("rowptr", vp), ("col", vp), ("val", vp), ("node_region", vp), ("chunk_tab", vp),
                 ("chunk_region", vp), ("n_chunks", C.c_int32),
@@ -147,6 +154,10 @@ SIGNATURES = {
     "regt_gru_sizes": (C.c_int32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "regt_gru_forward": (C.c_int32, [vp] * 11),
     "regt_gru_backward": (C.c_int32, [vp] * 11),
+    "regt_stae_sizes": (C.c_int32, [vp, C.POINTER(C.c_size_t)]),
+    "regt_stae_forward": (C.c_int32, [vp, vp, vp, vp, vp, vp]),
+    "regt_stae_attention": (C.c_int32, [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp]),
+    "regt_stae_add_layernorm": (C.c_int32, [vp, vp, vp, vp, C.c_float, C.c_int64, C.c_int32, vp, vp]),
     "regt_relu_backward": (C.c_int32, [vp, vp, C.c_int64, vp]),
     "regt_mse_loss_grad": (C.c_int32, [vp, vp, vp, vp, C.c_int64, C.c_int64, vp]),
 }

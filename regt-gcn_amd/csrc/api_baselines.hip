@@ -1,4 +1,4 @@
-// Entry points of the four baselines with their argument checks: SpatialGCN, STNorm, STID, StackedGRU.
+// Entry points of the baselines with their argument checks: SpatialGCN, STNorm, STID, StackedGRU, STAEformer (inference).
 #include "api_internal.h"
 
 using namespace regt;
@@ -193,6 +193,146 @@ int32_t regt_gru_backward(const regt_gru_dims* d, const float* x, const float* c
     REGT_CHECK_ARG(dout || dh_last, "regt_gru_backward: dout and dh_last are both NULL");
     REGT_CHECK_ARG((((uintptr_t)ws | (uintptr_t)scratch) & 15) == 0, "regt_gru_backward: workspace and scratch must be 16-byte aligned");
     return regt::launch_gru_bwd(s, x, weights[1], dout, dh_last, grads, dh0, ws, scratch, (hipStream_t)st);
+}
+
+static int stae_check(const char* what, const regt_stae_dims* d, regt::StaeDims* s) {
+    REGT_CHECK_ARG(d != nullptr, "%s: dims is NULL", what);
+    REGT_CHECK_ARG(d->batch >= 1 && d->num_nodes >= 1, "%s: batch and num_nodes must be >= 1, got %d, %d", what, d->batch, d->num_nodes);
+    REGT_CHECK_ARG(d->in_steps >= 1 && d->in_steps <= 255, "%s: in_steps must be in [1, 255], got %d", what, d->in_steps);
+    REGT_CHECK_ARG(d->use_mixed_proj == 1, "%s: use_mixed_proj must be 1 (the temporal_proj tail is not built)", what);
+    REGT_CHECK_ARG(d->input_embedding_dim >= 1 && d->tod_embedding_dim >= 0 && d->dow_embedding_dim >= 0 && d->spatial_embedding_dim >= 0 &&
+                       d->adaptive_embedding_dim >= 0,
+                   "%s: embedding widths must be >= 0 (input_embedding_dim >= 1)", what);
+    const long D = (long)d->input_embedding_dim + d->tod_embedding_dim + d->dow_embedding_dim + d->spatial_embedding_dim + d->adaptive_embedding_dim;
+    REGT_CHECK_ARG(D % 32 == 0 && D <= regt::STAE_MAX_DIM, "%s: model_dim (the sum of the five embedding widths) must be a multiple of 32, at most %d, got %ld",
+                   what, regt::STAE_MAX_DIM, D);
+    REGT_CHECK_ARG(d->num_heads >= 1 && D == (long)d->num_heads * regt::STAE_HEAD_DIM, "%s: head width model_dim / num_heads must be %d, got model_dim %ld, num_heads %d",
+                   what, regt::STAE_HEAD_DIM, D, d->num_heads);
+    REGT_CHECK_ARG(d->feed_forward_dim >= 32 && d->feed_forward_dim % 32 == 0 && d->feed_forward_dim <= regt::STAE_MAX_FF,
+                   "%s: feed_forward_dim must be a multiple of 32 in [32, %d], got %d", what, regt::STAE_MAX_FF, d->feed_forward_dim);
+    REGT_CHECK_ARG(d->num_layers >= 1 && d->num_layers <= regt::STAE_MAX_LAYERS, "%s: num_layers must be in [1, %d], got %d", what,
+                   regt::STAE_MAX_LAYERS, d->num_layers);
+    REGT_CHECK_ARG(d->in_features >= 1 && d->in_features <= 256, "%s: in_features must be in [1, 256], got %d", what, d->in_features);
+    REGT_CHECK_ARG(d->input_dim >= 1 && d->input_dim <= d->in_features, "%s: input_dim must be in [1, in_features = %d], got %d", what,
+                   d->in_features, d->input_dim);
+    REGT_CHECK_ARG((d->tod_embedding_dim == 0 || d->in_features >= 2) && (d->dow_embedding_dim == 0 || d->in_features >= 3),
+                   "%s: in_features must cover the time-of-day (1) and day-of-week (2) feature columns, got %d", what, d->in_features);
+    REGT_CHECK_ARG(d->steps_per_day >= 1 && d->days_per_week >= 1, "%s: steps_per_day and days_per_week must be >= 1, got %d, %d", what,
+                   d->steps_per_day, d->days_per_week);
+    REGT_CHECK_ARG(d->out_steps >= 1 && d->output_dim >= 1 && (long)d->out_steps * d->output_dim <= regt::STAE_MAX_OUT,
+                   "%s: out_steps * output_dim must be in [1, %d], got %d * %d", what, regt::STAE_MAX_OUT, d->out_steps, d->output_dim);
+    REGT_CHECK_ARG(d->ln_eps > 0.f, "%s: ln_eps must be > 0, got %g", what, (double)d->ln_eps);
+    REGT_CHECK_ARG((long)d->batch * d->in_steps * d->num_nodes < (1L << 31) / 4, "%s: batch * in_steps * num_nodes is too large", what);
+    *s = regt::StaeDims{d->batch, d->in_steps, d->num_nodes, d->in_features, d->input_dim, d->input_embedding_dim, d->tod_embedding_dim,
+                        d->dow_embedding_dim, d->spatial_embedding_dim, d->adaptive_embedding_dim, d->steps_per_day, d->days_per_week,
+                        d->num_heads, d->feed_forward_dim, d->num_layers, d->out_steps, d->output_dim, d->ln_eps};
+    return REGT_OK;
+}
+
+static int stae_check_table(const char* what, const regt::StaeDims& s, const void* const* p) {
+    REGT_CHECK_ARG(p != nullptr, "%s: parameter table is NULL", what);
+    const bool need[regt::STAE_HEAD_PARAMS] = {s.e_sp > 0, s.e_adp > 0, true, true, s.e_tod > 0, s.e_dow > 0, true, true};
+    for (int k = 0; k < regt::STAE_HEAD_PARAMS; ++k) REGT_CHECK_ARG(!need[k] || p[k] != nullptr, "%s: head entry %d is NULL", what, k);
+    for (int k = regt::STAE_HEAD_PARAMS; k < regt::STAE_HEAD_PARAMS + 2 * s.num_layers * regt::STAE_LAYER_PARAMS; ++k)
+        REGT_CHECK_ARG(p[k] != nullptr, "%s: layer entry %d is NULL", what, k);
+    return REGT_OK;
+}
+
+// out[M x N] = act(A[M x K] W^T + bias), rows of A / out at lda / ldo
+static int stae_linear(const float* A, long lda, long M, int K, const float* W, int N, const float* bias, int act, float* out, long ldo,
+                       hipStream_t st) {
+    GemmSegs S{};
+    S.nseg = 1;
+    S.seg[0] = make_seg(A, lda, W, nullptr, K, INT_MAX, K, true);
+    S.row_div = 1;
+    EpiBiasAct e{out, ldo, bias, act, 0.f};
+    return launch_gemm_bias_act(S, M, N, e, st);
+}
+
+// The whole inference launch sequence.  Workspace (floats): X and Y (M x D each), Q|K|V (M x 3D), the attention output (M x D) and the
+// feed-forward hidden (M x FF).  Per layer: three projections into Q|K|V, attention along the layer's axis, out_proj -> Y,
+// X = LN1(X + Y), hidden = relu(X W1^T + b1), Y = hidden W2^T + b2, X = LN2(X + Y).
+static int stae_forward(const regt::StaeDims& s, const float* x, const float* const* P, float* out, float* ws, hipStream_t st) {
+    const int D = regt::stae_model_dim(s), FF = s.ff_dim;
+    const long M = (long)s.batch * s.in_steps * s.num_nodes;
+    float *X = ws, *Y = X + M * D, *QKV = Y + M * D, *AO = QKV + 3 * M * D, *Hf = AO + M * D;
+    {
+        PROF("stae_embed", st);
+        TRY(regt::launch_stae_embed(s, x, P, X, st));
+    }
+    for (int i = 0; i < 2 * s.num_layers; ++i) {
+        const float* const* p = P + regt::STAE_HEAD_PARAMS + i * regt::STAE_LAYER_PARAMS;
+        const int axis = i < s.num_layers ? 1 : 2;
+        {
+            PROF("stae_qkv", st);
+            for (int j = 0; j < 3; ++j) TRY(stae_linear(X, D, M, D, p[2 * j], D, p[2 * j + 1], ACT_NONE, QKV + j * D, 3 * D, st));
+        }
+        {
+            PROF(axis == 1 ? "stae_attention_t" : "stae_attention_s", st);
+            TRY(regt::launch_stae_attention(QKV, QKV + D, QKV + 2 * D, 3 * D, s.batch, s.in_steps, s.num_nodes, s.num_heads, axis, AO, D, st));
+        }
+        {
+            PROF("stae_out_proj", st);
+            TRY(stae_linear(AO, D, M, D, p[6], D, p[7], ACT_NONE, Y, D, st));
+        }
+        {
+            PROF("stae_add_layernorm", st);
+            TRY(regt::launch_stae_add_layernorm(X, Y, p[12], p[13], s.ln_eps, M, D, X, st));
+        }
+        {
+            PROF("stae_feed_forward", st);
+            TRY(stae_linear(X, D, M, D, p[8], FF, p[9], ACT_RELU, Hf, FF, st));
+            TRY(stae_linear(Hf, FF, M, FF, p[10], D, p[11], ACT_NONE, Y, D, st));
+        }
+        {
+            PROF("stae_add_layernorm", st);
+            TRY(regt::launch_stae_add_layernorm(X, Y, p[14], p[15], s.ln_eps, M, D, X, st));
+        }
+    }
+    PROF("stae_output_proj", st);
+    return regt::launch_stae_output_proj(s, X, P[6], P[7], out, st);
+}
+
+int32_t regt_stae_sizes(const regt_stae_dims* d, size_t* ws) {
+    regt::StaeDims s;
+    if (int rc = stae_check("regt_stae_sizes", d, &s)) return rc;
+    REGT_CHECK_ARG(ws != nullptr, "regt_stae_sizes: workspace_floats is NULL");
+    *ws = (size_t)s.batch * s.in_steps * s.num_nodes * (6 * (size_t)regt::stae_model_dim(s) + s.ff_dim);
+    return REGT_OK;
+}
+
+int32_t regt_stae_forward(const regt_stae_dims* d, const float* x, const float* const* params, float* out, float* ws, regt_stream_t st) {
+    regt::StaeDims s;
+    if (int rc = stae_check("regt_stae_forward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && out && ws, "regt_stae_forward: x, out or workspace is NULL");
+    REGT_CHECK_ARG(al16(ws), "regt_stae_forward: workspace must be 16-byte aligned");
+    if (int rc = stae_check_table("regt_stae_forward", s, reinterpret_cast<const void* const*>(params))) return rc;
+    return stae_forward(s, x, params, out, ws, (hipStream_t)st);
+}
+
+int32_t regt_stae_attention(const float* q, const float* k, const float* v, int64_t ld, int32_t B, int32_t T, int32_t N, int32_t heads,
+                            int32_t axis, float* out, int64_t ldo, regt_stream_t st) {
+    REGT_CHECK_ARG(q && k && v && out, "regt_stae_attention: NULL pointer");
+    REGT_CHECK_ARG(axis == 1 || axis == 2, "regt_stae_attention: axis must be 1 (temporal) or 2 (spatial), got %d", axis);
+    REGT_CHECK_ARG(B >= 1 && T >= 1 && N >= 1, "regt_stae_attention: batch, in_steps and num_nodes must be >= 1, got %d, %d, %d", B, T, N);
+    REGT_CHECK_ARG(heads >= 1 && heads * regt::STAE_HEAD_DIM <= regt::STAE_MAX_DIM, "regt_stae_attention: heads must be in [1, %d], got %d",
+                   regt::STAE_MAX_DIM / regt::STAE_HEAD_DIM, heads);
+    const long D = (long)heads * regt::STAE_HEAD_DIM;
+    REGT_CHECK_ARG(ld >= D && ldo >= D && ld % 4 == 0 && ldo % 4 == 0, "regt_stae_attention: ld and ldo must be multiples of 4, at least 32 * heads = %ld, got %ld, %ld",
+                   D, (long)ld, (long)ldo);
+    REGT_CHECK_ARG(al16(q) && al16(k) && al16(v) && al16(out), "regt_stae_attention: q, k, v and out must be 16-byte aligned");
+    REGT_CHECK_ARG((long)B * T * N < (1L << 31) / 4, "regt_stae_attention: batch * in_steps * num_nodes is too large");
+    return regt::launch_stae_attention(q, k, v, (long)ld, B, T, N, heads, axis, out, (long)ldo, (hipStream_t)st);
+}
+
+int32_t regt_stae_add_layernorm(const float* residual, const float* y, const float* gamma, const float* beta, float eps, int64_t M, int32_t D,
+                                float* out, regt_stream_t st) {
+    REGT_CHECK_ARG(residual && y && gamma && beta && out, "regt_stae_add_layernorm: NULL pointer");
+    REGT_CHECK_ARG(D >= 32 && D % 32 == 0 && D <= regt::STAE_MAX_DIM, "regt_stae_add_layernorm: D must be a multiple of 32 in [32, %d], got %d",
+                   regt::STAE_MAX_DIM, D);
+    REGT_CHECK_ARG(M >= 1 && M < (1L << 31), "regt_stae_add_layernorm: M must be in [1, 2^31), got %ld", (long)M);
+    REGT_CHECK_ARG(eps > 0.f, "regt_stae_add_layernorm: eps must be > 0, got %g", (double)eps);
+    return regt::launch_stae_add_layernorm(residual, y, gamma, beta, eps, (long)M, D, out, (hipStream_t)st);
 }
 
 }  // extern "C"

@@ -387,6 +387,25 @@ int launch_relu_mask(const float* y, float* d, long n, hipStream_t st);      // 
 int launch_gru_bwd(const GruDims& s, const float* x, const float* w_hh, const float* dout, const float* dh_last, float* const* grads,
                    float* dh0, const float* ws, float* scratch, hipStream_t st);
 
+// STAEformer inference (staeformer.hip): the kernels between the dense layers; the launch sequence is stae_forward (api_baselines.hip).
+// Parameter pointer table in state_dict order: node_emb, adaptive_embedding, input_proj w, b, tod_embedding, dow_embedding (NULL
+// where the width is 0), output_proj w, b, then STAE_LAYER_PARAMS per layer, temporal layers first (attn.FC_Q w, b, FC_K, FC_V,
+// out_proj, feed_forward.0 w, b, feed_forward.2 w, b, ln1 w, b, ln2 w, b).
+struct StaeDims {
+    int batch, in_steps, num_nodes, in_features, input_dim, e_in, e_tod, e_dow, e_sp, e_adp, steps_per_day, days_per_week, num_heads,
+        ff_dim, num_layers, out_steps, output_dim;
+    float ln_eps;
+};
+constexpr int STAE_HEAD_DIM = 32, STAE_MAX_DIM = 256, STAE_MAX_FF = 1024, STAE_MAX_LAYERS = 8, STAE_MAX_OUT = 64, STAE_HEAD_PARAMS = 8,
+              STAE_LAYER_PARAMS = 16;
+inline int stae_model_dim(const StaeDims& s) { return s.e_in + s.e_tod + s.e_dow + s.e_sp + s.e_adp; }
+int launch_stae_attention(const float* q, const float* k, const float* v, long ld, int B, int T, int N, int heads, int axis, float* out,
+                          long ldo, hipStream_t st);
+int launch_stae_add_layernorm(const float* residual, const float* y, const float* gamma, const float* beta, float eps, long M, int D,
+                              float* out, hipStream_t st);
+int launch_stae_embed(const StaeDims& s, const float* x, const float* const* P, float* out, hipStream_t st);
+int launch_stae_output_proj(const StaeDims& s, const float* x, const float* w, const float* bias, float* out, hipStream_t st);
+
 // ---- per-device launch state ------------------------------------------------------------------------------------
 // What a launcher needs to know about the device it is about to launch on is keyed by the device's ordinal, never by the process.
 // A launcher that needs both helpers asks for the ordinal once and passes it on.

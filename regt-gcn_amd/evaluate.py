@@ -116,6 +116,11 @@ def predict_metrics_stid(model, xs, ys, snap_batch: int = 1):
     return _predict_metrics_windows(model, xs, ys, snap_batch, lambda x: model(x))
 
 
+def predict_metrics_staeformer(model, xs, ys, snap_batch: int = 1):
+    """predict.py:173-180 for STAEformer: (MAE, RMSE, MAPE); out is (1, O, N, 1).  The model runs in inference only."""
+    return _predict_metrics_windows(model, xs, ys, snap_batch, lambda x: model(x))
+
+
 def predict_metrics_gru(model, xs, ys, snap_batch: int = 1):
     """predict.py:155-162 for StackedGRU: (MAE, RMSE, MAPE) of ``batch.y - out[:, -1, :]``.  ``snap_batch`` snapshots run as
     stacked batch rows (N, 8 b, T); snapshot k's prediction is its last feature row."""
@@ -133,7 +138,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fixture", help=".npz in the layout of tests/golden/tpims_fixture.npz")
     ap.add_argument("--pickle", help="the reference's processed tpims_data_small.pkl")
     ap.add_argument("--checkpoint", required=True)
-    ap.add_argument("--model", default="RegionalTemporalGCN", choices=["RegionalTemporalGCN", "TemporalGCN", "SpatialGCN", "STNorm", "STID", "StackedGRU"])   # predict.py:110-114
+    ap.add_argument("--model", default="RegionalTemporalGCN", choices=["RegionalTemporalGCN", "TemporalGCN", "SpatialGCN", "STNorm", "STID", "StackedGRU", "STAEformer"])   # predict.py:110-114
     ap.add_argument("--num_timesteps_in", default=6, type=int)
     ap.add_argument("--num_timesteps_out", default=1, type=int)
     ap.add_argument("--tr", "--train_ratio", default=0.2, type=float, dest="tr")
@@ -165,6 +170,12 @@ def main(argv=None):
                          if_day_in_week=False).to(dev)
         model.load_state_dict(torch.load(a.checkpoint, map_location=dev, weights_only=True))
         mae, rmse, mape = predict_metrics_stid(model, vx, vy, max(1, a.snap_batch))
+        print("MAE: {:.4f}, RMSE: {:.4f}, MAPE: {:.4f}".format(mae, rmse, mape))
+        return
+    if a.model == "STAEformer":                               # predict.py:130-131, 173-180
+        model = rnn.STAEformer(num_nodes=n, in_steps=a.num_timesteps_in, out_steps=a.num_timesteps_out, tod_embedding_dim=0).to(dev)
+        model.load_state_dict(torch.load(a.checkpoint, map_location=dev, weights_only=True))
+        mae, rmse, mape = predict_metrics_staeformer(model, vx, vy, max(1, a.snap_batch))
         print("MAE: {:.4f}, RMSE: {:.4f}, MAPE: {:.4f}".format(mae, rmse, mape))
         return
     if a.model == "StackedGRU":                               # predict.py:122-123, 155-162

@@ -12,6 +12,7 @@ unchanged:
 * :class:`STNorm`               <-> models/STNorm.py:6-185
 * :class:`STID`                 <-> models/STID.py:5-157
 * :class:`StackedGRU`           <-> models/StackedGRU.py:4-30
+* :class:`STAEformer`           <-> models/STAEformer.py:110-255 (inference only)
 
 The modules only *hold* parameters; all arithmetic runs in libregtgcn_hip.so through
 :class:`regt-gcn_amd.functional.RegTGCNFunction`.  There is no CPU implementation here: calling
@@ -889,3 +890,106 @@ class StackedGRU(nn.Module):
         y = MLPHeadFunction.apply(out.view(-1, ops.GRU_HIDDEN), self.linear1.weight, self.linear1.bias, self.linear2.weight,
                                   self.linear2.bias)
         return y.view(x.shape[0], x.shape[1], self.output_dim)
+
+
+# ---- STAEformer, inference only (models/STAEformer.py) ---------------------------------------------------------------------------------
+
+class _STAEAttentionParams(nn.Module):
+    """Parameters of one multi-head attention (models/STAEformer.py:20-33): the three projections and out_proj."""
+
+    def __init__(self, model_dim: int):
+        super().__init__()
+        self.FC_Q = nn.Linear(model_dim, model_dim)
+        self.FC_K = nn.Linear(model_dim, model_dim)
+        self.FC_V = nn.Linear(model_dim, model_dim)
+        self.out_proj = nn.Linear(model_dim, model_dim)
+
+
+class _STAELayerParams(nn.Module):
+    """Parameters of one self-attention layer (models/STAEformer.py:77-91), registered in the reference's order."""
+
+    def __init__(self, model_dim: int, feed_forward_dim: int):
+        super().__init__()
+        self.attn = _STAEAttentionParams(model_dim)
+        self.feed_forward = nn.Sequential(nn.Linear(model_dim, feed_forward_dim), nn.ReLU(inplace=True), nn.Linear(feed_forward_dim, model_dim))
+        self.ln1 = nn.LayerNorm(model_dim)
+        self.ln2 = nn.LayerNorm(model_dim)
+
+    def table(self):
+        a, f = self.attn, self.feed_forward
+        return [a.FC_Q.weight, a.FC_Q.bias, a.FC_K.weight, a.FC_K.bias, a.FC_V.weight, a.FC_V.bias, a.out_proj.weight, a.out_proj.bias,
+                f[0].weight, f[0].bias, f[2].weight, f[2].bias, self.ln1.weight, self.ln1.bias, self.ln2.weight, self.ln2.bias]
+
+
+class STAEformer(nn.Module):
+    """STAEformer (models/STAEformer.py:110-255) with the reference's constructor, ``forward(x (B, in_steps, N, F)) ->
+    (B, out_steps, N, output_dim)`` and state_dict, for INFERENCE: what run.py::test() and predict.py do with the model.  All
+    arithmetic runs in regt_stae_forward; the ``nn.Linear`` / ``nn.Embedding`` / ``nn.LayerNorm`` modules only hold weights and are
+    created in the reference's order, so a seeded construction draws the same initial values.
+
+    ``forward`` raises NotImplementedError ("inference only") where autograd would record the call (grad mode on and the input or a
+    parameter requires grad) and in training mode with ``dropout > 0``: wrap the call in ``torch.no_grad()`` and ``eval()``.
+    Constructions outside the kernels' limits (head width 32, ``use_mixed_proj=True``, ...; include/regtgcn.h) raise
+    NotImplementedError here: run.py:132 passes ``tod_embedding_dim=0``, which gives model_dim 128 = 4 heads of 32, while the class
+    default (model_dim 152, head width 38) is refused.  The day-of-week and time-of-day indices are clamped into their tables."""
+
+    def __init__(self, num_nodes, in_steps=12, out_steps=12, steps_per_day=288, days_per_week=7, input_dim=3, output_dim=1,
+                 input_embedding_dim=24, tod_embedding_dim=24, dow_embedding_dim=24, spatial_embedding_dim=0, adaptive_embedding_dim=80,
+                 feed_forward_dim=256, num_heads=4, num_layers=3, dropout=0.1, use_mixed_proj=True):
+        super().__init__()
+        self.num_nodes, self.in_steps, self.out_steps = num_nodes, in_steps, out_steps
+        self.steps_per_day, self.days_per_week, self.input_dim, self.output_dim = steps_per_day, days_per_week, input_dim, output_dim
+        self.input_embedding_dim, self.tod_embedding_dim, self.dow_embedding_dim = input_embedding_dim, tod_embedding_dim, dow_embedding_dim
+        self.spatial_embedding_dim, self.adaptive_embedding_dim = spatial_embedding_dim, adaptive_embedding_dim
+        self.model_dim = input_embedding_dim + tod_embedding_dim + dow_embedding_dim + spatial_embedding_dim + adaptive_embedding_dim
+        self.feed_forward_dim, self.num_heads, self.num_layers = feed_forward_dim, num_heads, num_layers
+        self.dropout, self.use_mixed_proj = float(dropout), use_mixed_proj
+        if num_nodes < 1 or input_embedding_dim < 1 or min(tod_embedding_dim, dow_embedding_dim, spatial_embedding_dim, adaptive_embedding_dim) < 0 \
+                or steps_per_day < 1 or days_per_week < 1:
+            raise ValueError("STAEformer needs num_nodes, input_embedding_dim, steps_per_day, days_per_week >= 1 and embedding widths >= 0")
+        ops.stae_limits(in_steps, out_steps, input_dim, output_dim, self.model_dim, num_heads, feed_forward_dim, num_layers, use_mixed_proj)
+        self.input_proj = nn.Linear(input_dim, input_embedding_dim)
+        if tod_embedding_dim > 0:
+            self.tod_embedding = nn.Embedding(steps_per_day, tod_embedding_dim)
+        if dow_embedding_dim > 0:
+            self.dow_embedding = nn.Embedding(days_per_week, dow_embedding_dim)
+        if spatial_embedding_dim > 0:
+            self.node_emb = nn.Parameter(torch.empty(num_nodes, spatial_embedding_dim))
+            nn.init.xavier_uniform_(self.node_emb)
+        if adaptive_embedding_dim > 0:
+            self.adaptive_embedding = nn.Parameter(torch.empty(in_steps, num_nodes, adaptive_embedding_dim))
+            nn.init.xavier_uniform_(self.adaptive_embedding)
+        self.output_proj = nn.Linear(in_steps * self.model_dim, out_steps * output_dim)
+        self.attn_layers_t = nn.ModuleList([_STAELayerParams(self.model_dim, feed_forward_dim) for _ in range(num_layers)])
+        self.attn_layers_s = nn.ModuleList([_STAELayerParams(self.model_dim, feed_forward_dim) for _ in range(num_layers)])
+
+    def param_table(self):
+        """The parameters in state_dict order, the table order of regt_stae_forward (None where an embedding's width is 0)."""
+        t = [self.node_emb if self.spatial_embedding_dim > 0 else None, self.adaptive_embedding if self.adaptive_embedding_dim > 0 else None,
+             self.input_proj.weight, self.input_proj.bias, self.tod_embedding.weight if self.tod_embedding_dim > 0 else None,
+             self.dow_embedding.weight if self.dow_embedding_dim > 0 else None, self.output_proj.weight, self.output_proj.bias]
+        for m in list(self.attn_layers_t) + list(self.attn_layers_s):
+            t += m.table()
+        return t
+
+    def dims(self, batch: int, in_features: int) -> _lib.StaeDims:
+        return _lib.StaeDims(batch, self.in_steps, self.num_nodes, in_features, self.input_dim, self.input_embedding_dim,
+                             self.tod_embedding_dim, self.dow_embedding_dim, self.spatial_embedding_dim, self.adaptive_embedding_dim,
+                             self.steps_per_day, self.days_per_week, self.num_heads, self.feed_forward_dim, self.num_layers, self.out_steps,
+                             self.output_dim, int(bool(self.use_mixed_proj)), float(self.attn_layers_t[0].ln1.eps))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        _need_cuda(x)
+        need = max(self.input_dim, 2 if self.tod_embedding_dim > 0 else 0, 3 if self.dow_embedding_dim > 0 else 0)
+        if x.dim() != 4 or x.shape[1] != self.in_steps or x.shape[2] != self.num_nodes or x.shape[3] < need:
+            raise ValueError(f"x must be (B, {self.in_steps}, {self.num_nodes}, F >= {need}), got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise _lib.RegtError(f"STAEformer input must be float32, got {x.dtype}")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("STAEformer is inference only here (no backward kernels): call it under torch.no_grad()")
+        if self.training and self.dropout > 0:
+            raise NotImplementedError(f"STAEformer is inference only here: training mode with dropout={self.dropout} would draw dropout "
+                                      "masks; call eval() first")
+        dims = self.dims(x.shape[0], x.shape[3])
+        params = [None if p is None else p.detach() for p in self.param_table()]
+        return ops.stae_forward(dims, x.contiguous(), params)

@@ -529,3 +529,124 @@ def relu_backward_(y: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
         raise ValueError("relu_backward_: d must be contiguous and of y's size")
     _lib.check(_lib.load().regt_relu_backward(_lib.ptr(y), _lib.ptr(d), d.numel(), _stream()), "regt_relu_backward")
     return d
+
+
+# ---- STAEformer inference (models/STAEformer.py) ---------------------------------------------------------------------------------------
+
+STAE_HEAD_DIM = 32           # head width the attention kernel is built for (include/regtgcn.h)
+STAE_MAX_DIM = 256           # model_dim
+STAE_MAX_FF = 1024           # feed_forward_dim
+STAE_MAX_LAYERS = 8
+STAE_MAX_OUT = 64            # out_steps * output_dim
+STAE_LN_EPS = 1e-5           # nn.LayerNorm's default, which the reference keeps
+
+
+def stae_limits(in_steps: int, out_steps: int, input_dim: int, output_dim: int, model_dim: int, num_heads: int, feed_forward_dim: int,
+                num_layers: int, use_mixed_proj: bool = True):
+    """NotImplementedError naming the limits unless the construction is inside what regt_stae_* accept (include/regtgcn.h)."""
+    limits = (f"STAEformer runs with head width model_dim / num_heads == {STAE_HEAD_DIM}, model_dim a multiple of 32 up to {STAE_MAX_DIM}, "
+              f"feed_forward_dim a multiple of 32 up to {STAE_MAX_FF}, 1 <= in_steps <= 255, 1 <= num_layers <= {STAE_MAX_LAYERS}, "
+              f"input_dim >= 1, out_steps * output_dim <= {STAE_MAX_OUT} and use_mixed_proj=True")
+    ok = (use_mixed_proj and num_heads >= 1 and model_dim == num_heads * STAE_HEAD_DIM and model_dim <= STAE_MAX_DIM
+          and feed_forward_dim >= 32 and feed_forward_dim % 32 == 0 and feed_forward_dim <= STAE_MAX_FF and 1 <= in_steps <= 255
+          and 1 <= num_layers <= STAE_MAX_LAYERS and 1 <= input_dim <= 256 and out_steps >= 1 and output_dim >= 1
+          and out_steps * output_dim <= STAE_MAX_OUT)
+    if not ok:
+        raise NotImplementedError(f"{limits}; got model_dim={model_dim}, num_heads={num_heads}, feed_forward_dim={feed_forward_dim}, "
+                                  f"in_steps={in_steps}, num_layers={num_layers}, input_dim={input_dim}, out_steps={out_steps}, "
+                                  f"output_dim={output_dim}, use_mixed_proj={use_mixed_proj}")
+
+
+def stae_model_dim(dims: _lib.StaeDims) -> int:
+    return (dims.input_embedding_dim + dims.tod_embedding_dim + dims.dow_embedding_dim + dims.spatial_embedding_dim
+            + dims.adaptive_embedding_dim)
+
+
+def stae_sizes(dims: _lib.StaeDims) -> int:
+    """Workspace floats of regt_stae_forward."""
+    ws = ctypes.c_size_t()
+    _lib.check(_lib.load().regt_stae_sizes(ctypes.byref(dims), ctypes.byref(ws)), "regt_stae_sizes")
+    return ws.value
+
+
+def stae_table_shapes(dims: _lib.StaeDims):
+    """Expected shapes of the parameter table in state_dict order (None: the entry must be None, that embedding is off)."""
+    d, ff, n, t = stae_model_dim(dims), dims.feed_forward_dim, dims.num_nodes, dims.in_steps
+    shapes = [(n, dims.spatial_embedding_dim) if dims.spatial_embedding_dim else None,
+              (t, n, dims.adaptive_embedding_dim) if dims.adaptive_embedding_dim else None,
+              (dims.input_embedding_dim, dims.input_dim), (dims.input_embedding_dim,),
+              (dims.steps_per_day, dims.tod_embedding_dim) if dims.tod_embedding_dim else None,
+              (dims.days_per_week, dims.dow_embedding_dim) if dims.dow_embedding_dim else None,
+              (dims.out_steps * dims.output_dim, t * d), (dims.out_steps * dims.output_dim,)]
+    for _ in range(2 * dims.num_layers):
+        shapes += [(d, d), (d,)] * 4 + [(ff, d), (ff,), (d, ff), (d,)] + [(d,)] * 4
+    return shapes
+
+
+def stae_check_tables(dims: _lib.StaeDims, device, params, what: str = "STAEformer"):
+    """RegtError unless every parameter is a contiguous float32 tensor of its reference shape on ``device``: the kernels read them
+    through raw device pointers."""
+    shapes = stae_table_shapes(dims)
+    if len(params) != len(shapes):
+        raise _lib.RegtError(f"{what}: expected {len(shapes)} parameter entries, got {len(params)}")
+    _check_table(what, "parameter", params, shapes, device, "embedding width 0")
+
+
+def stae_forward(dims: _lib.StaeDims, x: torch.Tensor, params) -> torch.Tensor:
+    """out (B, out_steps, N, output_dim) of STAEformer in inference for x (B, T, N, F); ``params`` in state_dict order (None where an
+    embedding is off).  The whole launch sequence is one C call; nothing is kept for a backward."""
+    x = _f32c(x, "x")
+    shape = (dims.batch, dims.in_steps, dims.num_nodes, dims.in_features)
+    if tuple(x.shape) != shape:
+        raise ValueError(f"x must be {shape}, got {tuple(x.shape)}")
+    stae_check_tables(dims, x.device, params, "regt_stae_forward")
+    ws = torch.empty(stae_sizes(dims), dtype=torch.float32, device=x.device)
+    out = torch.empty(dims.batch, dims.out_steps, dims.num_nodes, dims.output_dim, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().regt_stae_forward(ctypes.byref(dims), _lib.ptr(x), _ptr_table(params), _lib.ptr(out), _lib.ptr(ws), _stream()),
+               "regt_stae_forward")
+    return out
+
+
+def _stae_rows(t: torch.Tensor, name: str, rows: int, width: int) -> int:
+    """Row stride of a (rows, width) float32 CUDA view whose rows are dense (a column window of a wider buffer is fine)."""
+    if not t.is_cuda or t.dtype != torch.float32:
+        raise _lib.RegtError(f"{name} must be a float32 CUDA tensor (no CPU path)")
+    if t.dim() != 2 or tuple(t.shape) != (rows, width) or t.stride(1) != 1:
+        raise ValueError(f"{name} must be a ({rows}, {width}) view with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
+    return t.stride(0) if rows > 1 else max(t.stride(0), width)
+
+
+def stae_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, in_steps: int, num_nodes: int, heads: int, axis: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(Q K^T / sqrt(32)) V per head along ``axis`` (1: time, 2: nodes) of (B, T, N, 32 * heads) rows.  q, k, v: (M, 32 * heads)
+    views with one common row stride (for instance column windows of a Q|K|V buffer); ``out``: an (M, 32 * heads) view, allocated
+    when None."""
+    m, d = batch * in_steps * num_nodes, heads * STAE_HEAD_DIM
+    ld = _stae_rows(q, "q", m, d)
+    if _stae_rows(k, "k", m, d) != ld or _stae_rows(v, "v", m, d) != ld:
+        raise ValueError("q, k and v must share one row stride")
+    if out is None:
+        out = torch.empty(m, d, dtype=torch.float32, device=q.device)
+    ldo = _stae_rows(out, "out", m, d)
+    _lib.check(_lib.load().regt_stae_attention(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ld, batch, in_steps, num_nodes, heads, axis,
+                                               _lib.ptr(out), ldo, _stream()), "regt_stae_attention")
+    return out
+
+
+def stae_add_layernorm(residual: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = STAE_LN_EPS,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm(residual + y) * gamma + beta over the last axis of (M, D) rows; ``out`` may be ``residual`` itself (in place)."""
+    if out is not None and out is not residual and (not out.is_contiguous() or out.shape != residual.shape or out.dtype != torch.float32
+                                                    or out.device != residual.device):
+        raise ValueError("out must be a contiguous float32 tensor of residual's shape on its device")
+    if out is residual and not residual.is_contiguous():
+        raise ValueError("an in-place residual must be contiguous")
+    residual, y, gamma, beta = _f32c(residual, "residual"), _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta")
+    m, d = residual.shape
+    if tuple(y.shape) != (m, d) or tuple(gamma.shape) != (d,) or tuple(beta.shape) != (d,):
+        raise ValueError(f"y must be ({m}, {d}) and gamma, beta ({d},)")
+    if out is None:
+        out = torch.empty_like(residual)
+    _lib.check(_lib.load().regt_stae_add_layernorm(_lib.ptr(residual), _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), eps, m, d,
+                                                   _lib.ptr(out), _stream()), "regt_stae_add_layernorm")
+    return out

@@ -188,8 +188,8 @@ def split(xs, ys, ratio: float):
 # models of run.py:115-136: those built on the TGCN cell (the hot path and the SURVEY 8(f) baselines), SpatialGCN (two ChebConv
 # layers, run.py:117-118), STNorm (gated dilated convolutions with temporal / spatial normalisation, no graph, run.py:135-136) and
 # STID (a per-node MLP on the node's history and a learned node embedding, no graph, run.py:133-134) and StackedGRU (two GRU layers
-# whose sequence runs over the nodes, no graph, run.py:123-124); TemporalGConvLSTM (which run.py:122 cannot construct) and
-# STAEformer are out of scope
+# whose sequence runs over the nodes, no graph, run.py:123-124); TemporalGConvLSTM (which run.py:122 cannot construct) is out of scope.  STAEformer
+# (run.py:131-132) runs for inference only (nn.STAEformer, evaluate.py --model STAEformer): training it is not offered here
 MODELS = ("RegionalTemporalGCN", "RandomTemporalGCN", "TemporalGCN", "ConvStackedTemporalGCN", "GraphSAGETemporalGCN", "GAT", "GATTemporal",
           "SpatialGCN", "STNorm", "STID", "StackedGRU")
 
