@@ -35,13 +35,10 @@ int32_t regt_cell0_forward(const regt_dims* dims, const regt_cell0_args* args, f
     const long M = (long)d.N * d.T;
     TRY(launch_softmax_small(a.attention, L.probs, d.T, st));
     for (int k = 0; k < 2; ++k) {      // Z = sigmoid(a_z gz^T + cz), H~ = tanh(a_h gh^T + ch)
-        GemmSegs S{};
-        S.nseg = 1;
-        S.seg[0] = make_seg(k ? a.a_h : a.a_z, k ? a.kh : a.kz, k ? a.gh : a.gz, nullptr, k ? a.kh : a.kz, INT_MAX, k ? a.kh : a.kz, true);
-        S.row_div = 1;
+        const int kk = k ? a.kh : a.kz;
         EpiBiasAct e{k ? L.Ht : L.Z, d.C, k ? a.ch : a.cz, k ? ACT_TANH : ACT_SIGMOID, 0.f};
         PROF(k ? "cell0_candidate" : "cell0_gate", st);
-        TRY(launch_gemm_bias_act(S, M, d.C, e, st));
+        TRY(launch_gemm_bias_act(one_seg(make_seg(k ? a.a_h : a.a_z, kk, k ? a.gh : a.gz, nullptr, kk, INT_MAX, kk, true)), M, d.C, e, st));
     }
     {
         PROF("cell0_blend", st);
@@ -83,13 +80,9 @@ int32_t regt_cell0_backward(const regt_dims* dims, const regt_cell0_args* args, 
         float* da = k ? g.a_h : g.a_z;
         if (!da) continue;
         const int kk = k ? a.kh : a.kz;
-        GemmSegs S{};
-        S.nseg = 1;
-        S.seg[0] = make_seg(k ? L.dhp : L.dzp, C, k ? a.gh : a.gz, nullptr, kk, INT_MAX, C, false);
-        S.row_div = 1;
         EpiBiasAct e{da, kk, nullptr, ACT_NONE, 0.f};
         PROF("cell0_dinput", st);
-        TRY(launch_gemm_bias_act(S, M, kk, e, st));
+        TRY(launch_gemm_bias_act(one_seg(make_seg(k ? L.dhp : L.dzp, C, k ? a.gh : a.gz, nullptr, kk, INT_MAX, C, false)), M, kk, e, st));
     }
     return REGT_OK;
 }

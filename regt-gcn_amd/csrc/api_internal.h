@@ -134,6 +134,12 @@ inline GemmSeg make_seg(const float* A, long lda, const float* B0, const float* 
     s.flags = f;
     return s;
 }
+// the GEMM of a single segment
+inline GemmSegs one_seg(const GemmSeg& s, int row_div = 1) {
+    GemmSegs S{};
+    S.nseg = 1; S.seg[0] = s; S.row_div = row_div;
+    return S;
+}
 
 // out[Nout x Nin] (+ column sums) = P^T Q over uniform chunks, reduced deterministically.
 // Weight-gradient slabs and their reductions inside one backward pass: every wgrad gets its own slab region and its
@@ -179,6 +185,40 @@ struct ReduceQueue {
         return REGT_OK;
     }
 };
+// The ONE weight-gradient path.  wgrad_launch takes the launch's slab region from the queue, launches under PROF(name) and gives back
+// the region as a WgradSlab; every reduction of that slab is then `rq.push(w.block(...))`, which states only what differs: the block
+// inside a slab, where it goes, and optionally its column sums or its chunk groups.
+struct ReduceBlock : WgradReduceArgs {
+    // column sums (bias gradient): `n` sums at slab element `offset` -> out (NULL: this block delivers none)
+    ReduceBlock& colsum(float* out, long offset, int n) { colsum_out = out; colsum_offset = offset; ncolsum = n; return *this; }
+    // chunk c belongs to output group chunk_group[c]; groups base .. base + n - 1 go to out + (group - base) * stride
+    ReduceBlock& groups(const int* chunk_group_, int n, int base, long stride) {
+        chunk_group = chunk_group_; ngroups = n; group_base = base; group_stride = stride;
+        return *this;
+    }
+};
+struct WgradSlab {
+    float* slab; int nchunks; long stride; int row;      // `row`: output columns of the launch = length of a slab row
+    // the (Nout x Nin) block at slab element `elem_offset` -> out with leading dimension ldo; a block narrower than the slab's rows
+    // is strided by them (slab_ld), one that spans them is dense (slab_ld = 0)
+    ReduceBlock block(long elem_offset, int Nout, int Nin, float* out, long ldo) const {
+        ReduceBlock r{};
+        r.slab = slab; r.nchunks = nchunks; r.slab_stride = stride; r.slab_ld = Nin == row ? 0 : row; r.ngroups = 1;
+        r.elem_offset = elem_offset; r.Nout = Nout; r.Nin = Nin; r.out = out; r.ldo = ldo;
+        return r;
+    }
+};
+inline int wgrad_slab(ReduceQueue& q, int nchunks, long stride, int row, WgradSlab* w) {
+    *w = WgradSlab{nullptr, nchunks, stride, row};
+    return q.take((long)nchunks * stride, &w->slab);
+}
+inline int wgrad_launch(ReduceQueue& q, WgradArgs a, const char* name, hipStream_t st, WgradSlab* w) {
+    TRY(wgrad_slab(q, a.nchunks, wgrad_slab_stride(a), a.Nin, w));
+    a.slab = w->slab;
+    PROF(name, st);
+    return launch_wgrad(a, st);
+}
+// one gradient out[Nout x Nin] = P^T Q (+ column sums of P) over uniform chunks: launch and reduction
 int wgrad_full(ReduceQueue& q, const char* name, const float* P, long ldp, int Nout, const float* Q, long ldq, int Nin, int q_relu,
                long M, int kchunk, int nchunks, float* out, long ldo, float* colsum, hipStream_t st, int p_bf16 = 0, int q_bf16 = 0);
 int head_forward(const regt_dims& d, const regt_params& p, const float* hidden, float* y1, float* pred, hipStream_t st);

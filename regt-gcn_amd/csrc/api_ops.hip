@@ -57,12 +57,8 @@ int32_t regt_linear(const float* A, int64_t lda, int64_t M, int32_t K, const flo
                     const float* bias, int32_t act, float slope, float* out, int64_t ldo, regt_stream_t st) {
     REGT_CHECK_ARG(A && W && out && M > 0 && K > 0 && N > 0, "regt_linear: bad argument");
     REGT_CHECK_ARG(act >= 0 && act <= 4, "regt_linear: act must be 0 (none), 1 (leaky_relu), 2 (relu), 3 (sigmoid) or 4 (tanh)");
-    GemmSegs S{};
-    S.nseg = 1;
-    S.seg[0] = make_seg(A, lda, W, nullptr, ldw, INT_MAX, K, true);
-    S.row_div = 1;
     EpiBiasAct e{out, ldo, bias, act, slope};
-    return launch_gemm_bias_act(S, M, N, e, (hipStream_t)st);
+    return launch_gemm_bias_act(one_seg(make_seg(A, lda, W, nullptr, ldw, INT_MAX, K, true)), M, N, e, (hipStream_t)st);
 }
 
 static void wgrad_chunks(int64_t M, int* kchunk, int* nchunks) {

@@ -36,17 +36,18 @@ static inline const float* byte_off(const float* p, long bytes) { return reinter
 
 // bf16 mode with bf16-stored activations: the GEMM weights get per-step bf16 copies in MFMA fragment order (SEG_B_FRAG: every
 // wave loads its B fragments straight into registers) when every K is a multiple of the 32-k slab
+static bool frag_shape_ok(const regt_dims& d) {
+    return bf16_intermediates(d) && d.F % 32 == 0 && d.C % 128 == 0 && !gemm_desc_table_forced() && !fp32_core_wide();
+}
 static bool weights_frag(const regt_dims& d) {
     // ... and every GEMM of the step fits the 64-slab descriptor table of the bf16-operand core (SplitCore::plan_u): the
     // regional embedding repeats its K = F segment once per region a 128-row tile can meet, the gate data gradient has K = 2C
     const long reg_slabs = (long)(std::min<long>(d.R, 128 / d.T + 2) + 1) * (d.F / 32);
-    return bf16_intermediates(d) && d.F % 32 == 0 && d.C % 128 == 0 && !gemm_desc_table_forced() && !fp32_core_wide() &&
-           reg_slabs <= 64 && (2L * d.C + d.F) / 32 <= 64;
+    return frag_shape_ok(d) && reg_slabs <= 64 && (2L * d.C + d.F) / 32 <= 64;
 }
 static bool xbf_ok(const regt_dims& d, const regt_graph& g, bool h_ext, int x_rows, bool packed_fp32) {
-    // (fragment-order weights as in weights_frag(), without its bound on the regional GEMM's slab table: the fused kernel has none)
-    const bool frag = bf16_intermediates(d) && d.F % 32 == 0 && d.C % 128 == 0 && !gemm_desc_table_forced() && !fp32_core_wide();
-    return xbf_wanted() && frag && d.regional && d.R > 1 && !g.overlap && !h_ext && g.m_rowptr && g.m_col && g.m_val_a && g.m_val_l &&
+    // (fragment-order weights without weights_frag()'s bound on the regional GEMM's slab table: the fused kernel has none)
+    return xbf_wanted() && frag_shape_ok(d) && d.regional && d.R > 1 && !g.overlap && !h_ext && g.m_rowptr && g.m_col && g.m_val_a && g.m_val_l &&
            g.chunk_tab && g.chunk_region && g.n_chunks > 0 &&
            fused_forward_ok(d.C, d.F) && ((long)d.T * d.F) % 64 == 0 && (!packed_fp32 || x_rows <= 2 * d.N) &&
            (long)(x_rows > d.N ? x_rows : d.N) * d.T * d.F * 2 < (1L << 32) - 4096;
@@ -68,6 +69,35 @@ int forward_format(const regt_dims& d, const regt_graph& g, int x_rows, bool pac
     return fmt;
 }
 
+// The form of one step, derived in one place from (dims, fmt, whether the hidden input is the caller's); forward_impl and backward_impl
+// read the same one.
+// Two sources stay apart: `ibf` is THIS call's arithmetic -- the forward stores q in it --, `qbf` is what `fmt` says the forward stored;
+// the entry points check that they agree before a backward runs.
+struct StepForm {
+    int ibf;        // bf16_intermediates(d): q, dhp, dzp|drp are stored as bf16
+    int qbf;        // fmt: q was stored as bf16
+    int abf;        // ... and h, [Z|R], H~ (dh / ds in the backward) too: everything M x C, unless the hidden input is the caller's
+    int xbf;        // fmt: x, A_hat x, L~ x hold bf16 rows
+    bool tcol;      // fmt: TemporalGCN, the gates' linear use of h folded into x, L~ x (never with a caller's hidden input: it is not that h)
+    bool wfr;       // fragment-order bf16 copies of the GEMM weights (the forward also needs node-disjoint regions for them)
+    bool split;     // the three-workgroup GEMM cores: the data gradients read transposed copies of the gate weights
+    bool save;      // the forward stores what only the backward reads (not a forward-only call)
+};
+static StepForm step_form(const regt_dims& d, int fmt, bool h_ext) {
+    StepForm f;
+    f.ibf = bf16_intermediates(d) ? 1 : 0;
+    f.qbf = fmt & FMT_QBF;
+    f.abf = f.ibf && !h_ext ? 1 : 0;
+    f.xbf = (fmt & FMT_XBF) ? 1 : 0;
+    f.tcol = (fmt & FMT_TCOLLAPSE) != 0 && !h_ext;
+    f.wfr = f.abf && weights_frag(d) && d.regional;
+    // (gemm_split.h: fp32 planes, bf16x3 split, bf16 take weights as [N][K] only; REGT_FP32_CORE=wide keeps the fp32 path on the
+    // two-workgroup core, which reads the weights as they are)
+    f.split = gemm_mode() != 0 || !fp32_core_wide();
+    f.save = !(fmt & FMT_FWDONLY);
+    return f;
+}
+
 static inline bool fits32(long v) { return v >= INT_MIN && v <= INT_MAX; }
 static SgTerm term(const float* A, long sai, long sak, long sab, const float* B, long sbk, long sbj, long sbb, int k, int batch = 1,
             int sum_batch = 0) {
@@ -87,13 +117,14 @@ static void add_task(SgBatch& b, float* C, long sci, long scj, long scb, int m, 
     for (const SgTerm& q : terms) t.term[t.nterm++] = q;
 }
 
-// All weight compositions of one step in ONE launch (SURVEY/DESIGN section 3, item 2).
 // owned region block [lo, hi) of a graph (regt_graph.region_lo / region_hi; 0, 0 = all)
 static void region_range(const regt_dims& d, const regt_graph& g, int* lo, int* hi) {
     *lo = 0; *hi = d.R;
     if (g.region_hi > g.region_lo && g.region_lo >= 0 && g.region_hi <= d.R) { *lo = g.region_lo; *hi = g.region_hi; }
 }
 
+// All weight compositions of one step in ONE launch (SURVEY/DESIGN section 3, item 2); compose_backward is its mirror.
+// `tcol` adds the TemporalGCN compositions of the collapsed gate GEMM.
 static int compose_forward(const regt_dims& d, const regt_graph& g, const regt_params& p, const Layout& L, hipStream_t st, bool tcol = false) {
     const int C = d.C, F = d.F, R = d.R;
     const long RC = (long)R * C;
@@ -132,26 +163,66 @@ static int compose_forward(const regt_dims& d, const regt_graph& g, const regt_p
 // for the backward pass
 int head_forward(const regt_dims& d, const regt_params& p, const float* hidden, float* y1, float* pred, hipStream_t st) {
     const int N = d.N, C = d.C, O = d.O, H1 = d.H1;
-    GemmSegs S{};
-    S.nseg = 1;
-    S.seg[0] = make_seg(hidden, C, p.head1_w, nullptr, C, INT_MAX, C, true, SEG_RELU_A);
-    S.row_div = 1;
     EpiBiasAct e{y1, H1, p.head1_b, ACT_RELU, 0.f};
     PROF("head_fwd", st);
-    TRY(launch_gemm_bias_act(S, N, H1, e, st));
-    if (head2_skinny_ok(H1, O, y1, p.head2_w)) {
-        TRY(launch_head2_fwd(y1, p.head2_w, p.head2_b, pred, N, H1, O, st));
-    } else {
-        GemmSegs S2{};
-        S2.nseg = 1;
-        S2.seg[0] = make_seg(y1, H1, p.head2_w, nullptr, H1, INT_MAX, H1, true);
-        S2.row_div = 1;
-        EpiBiasAct e2{pred, O, p.head2_b, ACT_NONE, 0.f};
-        TRY(launch_gemm_bias_act(S2, N, O, e2, st));
-    }
-    return REGT_OK;
+    TRY(launch_gemm_bias_act(one_seg(make_seg(hidden, C, p.head1_w, nullptr, C, INT_MAX, C, true, SEG_RELU_A)), N, H1, e, st));
+    if (head2_skinny_ok(H1, O, y1, p.head2_w)) return launch_head2_fwd(y1, p.head2_w, p.head2_b, pred, N, H1, O, st);
+    EpiBiasAct e2{pred, O, p.head2_b, ACT_NONE, 0.f};
+    return launch_gemm_bias_act(one_seg(make_seg(y1, H1, p.head2_w, nullptr, H1, INT_MAX, H1, true)), N, O, e2, st);
 }
 
+// bf16 copies, in MFMA fragment order, of the weights the forward GEMMs read (bf16 arithmetic with fragment-order weights: regional
+// models only, so A0 / A_r are the composed ones).  C % 128 == 0: region r of A_r starts at block row r C / 32.
+static int weights_to_frag(const regt_dims& d, const regt_params& p, const Layout& L, const WbPtrs& wb, hipStream_t st) {
+    const int F = d.F, C = d.C;
+    CvtBatch cb{};
+    cb.n = 0;
+    for (int k = 0; k < 3; ++k) cb.t[cb.n++] = CvtTask{p.gate_w[k] + C, 2L * C, C, C, const_cast<float*>(wb.U[k])};
+    cb.t[cb.n++] = CvtTask{L.Gzr, F, 2 * C, F, const_cast<float*>(wb.Gzr)};
+    cb.t[cb.n++] = CvtTask{L.Gh, F, C, F, const_cast<float*>(wb.Gh)};
+    cb.t[cb.n++] = CvtTask{L.A0, F, C, F, const_cast<float*>(wb.A0)};
+    cb.t[cb.n++] = CvtTask{L.Aall, F, d.R * C, F, const_cast<float*>(wb.Aall)};
+    PROF("weights_bf16", st);
+    return launch_cvt_bf16_frag(cb, st);
+}
+
+// The forward on bf16 rows (FMT_XBF, chosen by xbf_ok): x, A_hat x, L~ x as bf16 rows and the whole cell as ONE kernel -- the row-owning
+// one (fused_rows.hip) where fused_rows_form() holds, else the 64-row one (fused.hip) --, then the head.
+static int forward_bf16_rows(const regt_dims& d, const regt_graph& g, const regt_params& p, const float* x, const float* xp_ext, int x_rows,
+                             float* pred, float* hidden, const Layout& L, hipStream_t st, bool skip_pack, int fmt, bool save) {
+    const int N = d.N, T = d.T, F = d.F, C = d.C;
+    const void* Xb = (fmt & FMT_XCALLER) ? static_cast<const void*>(xp_ext) : static_cast<const void*>(L.Xp);
+    if (!(fmt & FMT_XCALLER) && !skip_pack) {
+        PROF("pack_x", st);
+        if (xp_ext) TRY(launch_cvt_rows_bf16(xp_ext, L.Xp, (long)x_rows * T * F, st));
+        else TRY(launch_pack_x_bf16(x, L.Xp, N, F, T, st));
+    }
+    {
+        PROF("spmm", st);
+        TRY(launch_spmm_dual_bf16(g.m_rowptr, g.m_col, g.m_val_a, g.m_val_l, Xb, L.AX, L.LX, N, xp_ext ? x_rows : N, T * F, st));
+    }
+    const WbPtrs wb = wb_ptrs(L.Wb, C, F);
+    TRY(side_join(st));                      // composed weights ready
+    TRY(weights_to_frag(d, p, L, wb, st));
+    {
+        FusedFwdArgs a{};
+        a.X = Xb; a.LX = L.LX; a.AX = L.AX;
+        a.A0f = wb.A0; a.Aallf = wb.Aall; a.ar_stride = wb.ar_stride;
+        a.Uzf = wb.U[0]; a.Urf = wb.U[1]; a.Uhf = wb.U[2]; a.Gzrf = wb.Gzr; a.Ghf = wb.Gh;
+        a.bprime = L.bprime; a.czr = L.czr; a.ch = L.ch; a.probs = L.probs;
+        a.node_region = d.R > 1 ? g.node_region : nullptr;
+        a.h = L.h; a.ZR = L.ZR; a.q = L.q; a.Ht = L.Ht; a.OH = hidden;      // (forward-only layout: all four NULL, never touched)
+        a.M = (long)N * T; a.T = T; a.slope = d.lrelu_slope; a.act_lrelu = 1; a.tile_ctr = L.tile_ctr;
+        PROF("fused_forward", st);
+        TRY(launch_zero_f32(hidden, (long)N * C, st));
+        if (fused_rows_form(d, g)) TRY(launch_fused_forward_rows(a, C, F, option(OPT_FUSED_ROWS) == 2 ? 4 : 8, st, save));
+        else TRY(launch_fused_forward(a, C, F, st, save));
+    }
+    return head_forward(d, p, hidden, L.y1, pred, st);
+}
+
+// The forward: weight compositions on the side stream, then either the bf16-row form above (FMT_XBF) or five stages on the launch
+// stream: pack + aggregate, regional embedding, gates, candidate + blend + attention sum, head.
 // `h_ext` != NULL: the cell's hidden input (M x C, rows node*T + t) comes from the caller (regt_cell_forward); the
 // regional / Cheb embedding stage is skipped and only A_hat x is aggregated (graph = the N rows of A_hat).
 int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, const float* x, const float* xp_ext,
@@ -159,58 +230,18 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
     const int N = d.N, T = d.T, F = d.F, C = d.C, R = d.R;
     const long M = (long)N * T;
     const float* H = h_ext ? h_ext : L.h;
-    const int qbf = bf16_intermediates(d) ? 1 : 0;      // q (and dhp, dzp|drp in the backward) stored as bf16
-    const int abf = qbf && !h_ext ? 1 : 0;              // ... and h, [Z|R], H~ (dh in the backward) too: everything M x C
-    const bool save = !(fmt & FMT_FWDONLY);             // forward-only: the kernels that store nothing the backward alone reads
+    const StepForm f = step_form(d, fmt, h_ext != nullptr);
+    const int qbf = f.ibf, abf = f.abf;      // the forward is q's producer: it stores q in this call's arithmetic
+    const bool save = f.save;                // forward-only: the kernels that store nothing the backward alone reads
     // The weight compositions do not depend on the snapshot: they run on the side stream next to pack_x + aggregation and are
     // joined in front of their first consumer (0.03-0.10 ms per step off the critical path at every size).
     {
         hipStream_t sc = side_fork(st);
         PROF("compose_fwd", sc);
         TRY(launch_softmax_small(p.attention, L.probs, T, sc));
-        TRY(compose_forward(d, g, p, L, sc, (fmt & FMT_TCOLLAPSE) != 0));
+        TRY(compose_forward(d, g, p, L, sc, f.tcol));
     }
-    if (fmt & FMT_XBF) {
-        // bf16 rows of x, A_hat x, L~ x + the fused cell kernel (fused.hip)
-        const void* Xb = (fmt & FMT_XCALLER) ? static_cast<const void*>(xp_ext) : static_cast<const void*>(L.Xp);
-        if (!(fmt & FMT_XCALLER) && !skip_pack) {
-            PROF("pack_x", st);
-            if (xp_ext) TRY(launch_cvt_rows_bf16(xp_ext, L.Xp, (long)x_rows * T * F, st));
-            else TRY(launch_pack_x_bf16(x, L.Xp, N, F, T, st));
-        }
-        {
-            PROF("spmm", st);
-            TRY(launch_spmm_dual_bf16(g.m_rowptr, g.m_col, g.m_val_a, g.m_val_l, Xb, L.AX, L.LX, N, xp_ext ? x_rows : N, T * F, st));
-        }
-        const WbPtrs wbf = wb_ptrs(L.Wb, C, F);
-        TRY(side_join(st));                      // composed weights ready
-        {
-            CvtBatch cb{};
-            cb.n = 0;
-            for (int k = 0; k < 3; ++k) cb.t[cb.n++] = CvtTask{p.gate_w[k] + C, 2L * C, C, C, const_cast<float*>(wbf.U[k])};
-            cb.t[cb.n++] = CvtTask{L.Gzr, F, 2 * C, F, const_cast<float*>(wbf.Gzr)};
-            cb.t[cb.n++] = CvtTask{L.Gh, F, C, F, const_cast<float*>(wbf.Gh)};
-            cb.t[cb.n++] = CvtTask{L.A0, F, C, F, const_cast<float*>(wbf.A0)};
-            cb.t[cb.n++] = CvtTask{L.Aall, F, R * C, F, const_cast<float*>(wbf.Aall)};
-            PROF("weights_bf16", st);
-            TRY(launch_cvt_bf16_frag(cb, st));
-        }
-        {
-            FusedFwdArgs a{};
-            a.X = Xb; a.LX = L.LX; a.AX = L.AX;
-            a.A0f = wbf.A0; a.Aallf = wbf.Aall; a.ar_stride = wbf.ar_stride;
-            a.Uzf = wbf.U[0]; a.Urf = wbf.U[1]; a.Uhf = wbf.U[2]; a.Gzrf = wbf.Gzr; a.Ghf = wbf.Gh;
-            a.bprime = L.bprime; a.czr = L.czr; a.ch = L.ch; a.probs = L.probs;
-            a.node_region = R > 1 ? g.node_region : nullptr;
-            a.h = L.h; a.ZR = L.ZR; a.q = L.q; a.Ht = L.Ht; a.OH = hidden;      // (forward-only layout: all four NULL, never touched)
-            a.M = M; a.T = T; a.slope = d.lrelu_slope; a.act_lrelu = 1; a.tile_ctr = L.tile_ctr;
-            PROF("fused_forward", st);
-            TRY(launch_zero_f32(hidden, (long)N * C, st));
-            if (fused_rows_form(d, g)) TRY(launch_fused_forward_rows(a, C, F, option(OPT_FUSED_ROWS) == 2 ? 4 : 8, st, save));
-            else TRY(launch_fused_forward(a, C, F, st, save));
-        }
-        return head_forward(d, p, hidden, L.y1, pred, st);
-    }
+    if (f.xbf) return forward_bf16_rows(d, g, p, x, xp_ext, x_rows, pred, hidden, L, st, skip_pack, fmt, save);
     // 1. pack the snapshot and aggregate: [A_hat; L~] x  (one stacked SpMM over 2N rows, width T*F)
     const float* Xp = xp_ext ? xp_ext : L.Xp;
     if (!xp_ext && !skip_pack) {
@@ -232,19 +263,9 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
     const float* A0 = d.regional ? L.A0 : p.cheb_w0;
     const float* Aall = d.regional ? L.Aall : p.cheb_w1;
     const float* bpr = d.regional ? L.bprime : p.cheb_bias;
-    const bool wfr = abf && weights_frag(d) && d.regional && !g.overlap;
+    const bool wfr = f.wfr && !g.overlap;      // (the repeated segments of overlapping regions have no fragment-order form)
     const WbPtrs wb = wb_ptrs(L.Wb, C, F);
-    if (wfr) {
-        CvtBatch cb{};
-        cb.n = 0;
-        for (int k = 0; k < 3; ++k) cb.t[cb.n++] = CvtTask{p.gate_w[k] + C, 2L * C, C, C, const_cast<float*>(wb.U[k])};
-        cb.t[cb.n++] = CvtTask{L.Gzr, F, 2 * C, F, const_cast<float*>(wb.Gzr)};
-        cb.t[cb.n++] = CvtTask{L.Gh, F, C, F, const_cast<float*>(wb.Gh)};
-        cb.t[cb.n++] = CvtTask{A0, F, C, F, const_cast<float*>(wb.A0)};
-        cb.t[cb.n++] = CvtTask{Aall, F, R * C, F, const_cast<float*>(wb.Aall)};      // C % 128 == 0: region r starts at block row r C / 32
-        PROF("weights_bf16", st);
-        TRY(launch_cvt_bf16_frag(cb, st));
-    }
+    if (wfr) TRY(weights_to_frag(d, p, L, wb, st));
     // 2. regional embedding h = act(x A0^T + (L~ x) A_region^T + b')
     if (!h_ext) {
         GemmSegs S{};
@@ -282,7 +303,7 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
         if (wfr) {
             S.seg[0] = make_seg(H, C, wb.U[0], wb.U[1], C, C, C, true, SEG_A_BF16 | SEG_B_FRAG);
             S.seg[1] = make_seg(L.AX, F, wb.Gzr, nullptr, F, INT_MAX, F, true, SEG_B_FRAG);
-        } else if (fmt & FMT_TCOLLAPSE) {      // K = 3 F: the linear hidden input folded into x and L~ x
+        } else if (f.tcol) {      // K = 3 F: the linear hidden input folded into x and L~ x
             S.nseg = 3;
             S.seg[0] = make_seg(Xp, F, L.P0zr, nullptr, F, INT_MAX, F, true);
             S.seg[1] = make_seg(L.LX, F, L.P1zr, nullptr, F, INT_MAX, F, true);
@@ -292,7 +313,7 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
             S.seg[1] = make_seg(L.AX, F, L.Gzr, nullptr, F, INT_MAX, F, true);
         }
         S.row_div = T;
-        EpiGates e{L.ZR, H, L.q, (fmt & FMT_TCOLLAPSE) ? L.czr2 : L.czr, C};
+        EpiGates e{L.ZR, H, L.q, f.tcol ? L.czr2 : L.czr, C};
         e.q_bf16 = qbf; e.h_bf16 = abf; e.zr_bf16 = abf;
         PROF("gemm_gates", st);
         TRY(launch_gemm_gates(S, M, 2 * C, e, st, save));
@@ -324,29 +345,21 @@ int wgrad_full(ReduceQueue& q, const char* name, const float* P, long ldp, int N
                long M, int kchunk, int nchunks, float* out, long ldo, float* colsum, hipStream_t st, int p_bf16, int q_bf16) {
     WgradArgs a{P, ldp, Nout, Q, ldq, Nin, q_relu, M, kchunk, nullptr, nchunks, nullptr, colsum ? 1 : 0};
     a.p_bf16 = p_bf16; a.q_bf16 = q_bf16;
-    TRY(q.take((long)nchunks * wgrad_slab_stride(a), &a.slab));
-    {
-        PROF(name, st);
-        TRY(launch_wgrad(a, st));
-    }
-    WgradReduceArgs r{};
-    r.slab = a.slab; r.nchunks = nchunks; r.slab_stride = wgrad_slab_stride(a); r.elem_offset = 0;
-    r.Nout = Nout; r.Nin = Nin; r.chunk_group = nullptr; r.ngroups = 1; r.out = out; r.ldo = ldo; r.group_stride = 0;
-    r.colsum_out = colsum; r.colsum_offset = (long)Nout * Nin; r.ncolsum = Nout; r.accumulate = 0;
-    return q.push(r);
+    WgradSlab w;
+    TRY(wgrad_launch(q, a, name, st, &w));
+    return q.push(w.block(0, Nout, Nin, out, ldo).colsum(colsum, (long)Nout * Nin, Nout));
 }
 
 // backward of head_forward: weight / bias gradients of linear2 and linear1 (slabs queued on `rq`) and
-// dOH = (d1 A1) * (hidden > 0) + dhidden, the gradient of the attention-weighted hidden state
+// dOH = (d1 A1) * (hidden > 0) + dhidden, the gradient of the attention-weighted hidden state.
+// head2_skinny_ok (output_dim <= 4) selects the row-wise kernels of the last layer; its two weight gradients then run on the side stream.
 int head_backward(const regt_dims& d, const regt_params& p, const regt_grads& gr, const float* dpred, const float* dhidden,
                   const float* hidden, const float* y1, float* d1, float* dOH, ReduceQueue& rq, hipStream_t st) {
     const int N = d.N, C = d.C, O = d.O, H1 = d.H1;
     const HeadChunks hc = head_chunks(N, H1, C);
-    const int kchunk_head = hc.k1, nchunks_head = hc.n1;
-    const bool skinny = head2_skinny_ok(H1, O, y1, p.head2_w);
-    if (skinny) {
-        float* slab = nullptr;
-        TRY(rq.take((long)hc.n2 * ((long)O * H1 + O), &slab));
+    if (head2_skinny_ok(H1, O, y1, p.head2_w)) {
+        WgradSlab w2;
+        TRY(wgrad_slab(rq, hc.n2, (long)O * H1 + O, H1, &w2));
         {   // d1 first: the weight gradients leave the critical path behind it (side stream)
             PROF("head_bwd", st);
             TRY(launch_head2_bwd(dpred, p.head2_w, y1, d1, N, H1, O, st));
@@ -354,385 +367,363 @@ int head_backward(const regt_dims& d, const regt_params& p, const regt_grads& gr
         hipStream_t ss = side_fork(st);
         {
             PROF("wgrad_head2", ss);
-            TRY(launch_head2_wgrad(dpred, y1, slab, N, H1, O, hc.k2, hc.n2, 1, ss));
+            TRY(launch_head2_wgrad(dpred, y1, w2.slab, N, H1, O, hc.k2, hc.n2, 1, ss));
         }
-        WgradReduceArgs r{};
-        r.slab = slab; r.nchunks = hc.n2; r.slab_stride = (long)O * H1 + O; r.elem_offset = 0;
-        r.Nout = O; r.Nin = H1; r.chunk_group = nullptr; r.ngroups = 1; r.out = gr.head2_w; r.ldo = H1; r.group_stride = 0;
-        r.colsum_out = gr.head2_b; r.colsum_offset = (long)O * H1; r.ncolsum = O; r.accumulate = 0;
-        TRY(rq.push(r));
-        TRY(wgrad_full(rq, "wgrad_head1", d1, H1, H1, hidden, C, C, 1, N, kchunk_head, nchunks_head, gr.head1_w, C, gr.head1_b, ss));
+        TRY(rq.push(w2.block(0, O, H1, gr.head2_w, H1).colsum(gr.head2_b, (long)O * H1, O)));
+        TRY(wgrad_full(rq, "wgrad_head1", d1, H1, H1, hidden, C, C, 1, N, hc.k1, hc.n1, gr.head1_w, C, gr.head1_b, ss));
     } else {
-        TRY(wgrad_full(rq, "wgrad_head2", dpred, O, O, y1, H1, H1, 0, N, kchunk_head, nchunks_head, gr.head2_w, H1, gr.head2_b, st));
-        // d1 = (dpred A2) * (y1 > 0)
-        GemmSegs S{};
-        S.nseg = 1;
-        S.seg[0] = make_seg(dpred, O, p.head2_w, nullptr, H1, INT_MAX, O, false);
-        S.row_div = 1;
+        TRY(wgrad_full(rq, "wgrad_head2", dpred, O, O, y1, H1, H1, 0, N, hc.k1, hc.n1, gr.head2_w, H1, gr.head2_b, st));
+        // d1 = (dpred A2) * (y1 > 0)      (this head_bwd scope has always spanned wgrad_head1 as well: kept, the profile's figures stay comparable)
         EpiMaskAdd e{d1, H1, y1, H1, nullptr, 0};
         PROF("head_bwd", st);
-        TRY(launch_gemm_mask_add(S, N, H1, e, st));
-        TRY(wgrad_full(rq, "wgrad_head1", d1, H1, H1, hidden, C, C, 1, N, kchunk_head, nchunks_head, gr.head1_w, C, gr.head1_b, st));
+        TRY(launch_gemm_mask_add(one_seg(make_seg(dpred, O, p.head2_w, nullptr, H1, INT_MAX, O, false)), N, H1, e, st));
+        TRY(wgrad_full(rq, "wgrad_head1", d1, H1, H1, hidden, C, C, 1, N, hc.k1, hc.n1, gr.head1_w, C, gr.head1_b, st));
     }
-    {   // dOH = (d1 A1) * (hidden > 0) + dhidden
-        GemmSegs S{};
-        S.nseg = 1;
-        S.seg[0] = make_seg(d1, H1, p.head1_w, nullptr, C, INT_MAX, H1, false);
-        S.row_div = 1;
-        EpiMaskAdd e{dOH, C, hidden, C, dhidden, C};
-        PROF("head_bwd", st);
-        TRY(launch_gemm_mask_add(S, N, C, e, st));
-    }
-    return REGT_OK;
+    // dOH = (d1 A1) * (hidden > 0) + dhidden
+    EpiMaskAdd e{dOH, C, hidden, C, dhidden, C};
+    PROF("head_bwd", st);
+    return launch_gemm_mask_add(one_seg(make_seg(d1, H1, p.head1_w, nullptr, C, INT_MAX, H1, false)), N, C, e, st);
 }
 
-// `h_ext` / `dh_ext` != NULL (regt_cell_backward): the hidden input was supplied by the caller; its gradient is
-// written to dh_ext and the embedding-stage gradients (A0 / A_r / Cheb weights) are skipped.
-int backward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, const regt_grads& gr,
-                  const float* dpred, const float* dhidden, const float* hidden, const float* xp_ext, const Layout& L,
-                  hipStream_t st, int fmt, const float* h_ext, float* dh_ext) {
-    const int N = d.N, T = d.T, F = d.F, C = d.C, R = d.R;
+// What the stages of one backward pass share.
+struct Bwd {
+    const regt_dims& d; const regt_graph& g; const regt_params& p; const regt_grads& gr; const Layout& L;
+    StepForm f;
+    WbPtrs wb;
+    const float* Xp;        // the packed input the forward read
+    const float* H;         // the hidden input: L.h, or the caller's (`ext`)
+    float* DH;              // its gradient: L.dh, or the caller's
+    bool ext;               // regt_cell_backward: no embedding stage
+    hipStream_t st;
+};
+
+// Tail of the attention gradient: off the critical path (side stream), joined before the slab reduction.  `parts` partial dots per row
+// are summed first (1: fused backward, C / 128: generated-operand kernel); 0: cell_bwd left the per-block sums complete.
+static int attention_tail(const Bwd& b, int parts) {
+    const Layout& L = b.L;
+    if (!b.gr.attention) return REGT_OK;
+    hipStream_t sa = side_fork(b.st);
+    if (parts) TRY(launch_rowdot_reduce(L.rowdot, L.dp_partial, b.d.N, b.d.T, L.cb_npb, sa, parts));
+    return launch_att_bwd(L.dp_partial, L.cb_blocks, L.probs, b.gr.attention, b.d.T, sa);
+}
+
+// Data gradients of the cell: dhp, dzp | drp (the left operands of the weight gradients), dh and ds = d(hidden input), in one of
+// three forms, flat:
+//   fused    bf16 arithmetic with fragment-order weights: ONE kernel (fused.hip), every activation read and written once; the same
+//            results bit for bit except the summation order of the attention gradient.  REGT_FUSED_BWD=0 / REGT_DIMS_NO_FUSED_BWD: off.
+//   gen      fp32 / bf16x3 at sizes the 128 x 128 core covers: dhp is GENERATED inside the candidate data gradient's K loop, dzp and the
+//            attention dots come out of its epilogue -- cell_bwd's pass over Z, h, H~ (5 C floats per row) does not happen
+//            (gemm_split.h: run_u_gen).  REGT_DGRAD1_GEN=0: off.
+//   two      cell_bwd, then the candidate data gradient.
+// The gate data gradient (dgrad_gates) follows gen and two -- the fused kernel holds it -- unless the collapsed TemporalGCN form never
+// forms ds.
+static int data_gradients(const Bwd& b) {
+    const regt_dims& d = b.d; const regt_params& p = b.p; const Layout& L = b.L; const StepForm& f = b.f; const WbPtrs& wb = b.wb;
+    const int N = d.N, T = d.T, C = d.C;
     const long M = (long)N * T;
-    const int qbf = fmt & FMT_QBF, xbf = (fmt & FMT_XBF) ? 1 : 0;     // xbf: x, A_hat x, L~ x hold bf16 rows (the forward's format)
-    const bool tcol = (fmt & FMT_TCOLLAPSE) != 0 && !h_ext;            // TemporalGCN: the gates' linear use of h folded into x, L~ x
-    const float* Xp = (xp_ext && (!xbf || (fmt & FMT_XCALLER))) ? xp_ext : L.Xp;
-    const float* H = h_ext ? h_ext : L.h;
-    float* DH = dh_ext ? dh_ext : L.dh;
-    const int ibf = bf16_intermediates(d) ? 1 : 0;      // dhp, dzp|drp stored as bf16 (and q, by the forward: checked by the caller)
-    const int abf = ibf && !h_ext ? 1 : 0;              // h, [Z|R], H~ were stored as bf16 by the forward; dh / ds follow
-    // ---- head ----------------------------------------------------------------------------------
-    ReduceQueue rq(L.slab, L.slab_floats, st);
-    TRY(head_backward(d, p, gr, dpred, dhidden, hidden, L.y1, L.d1, L.dOH, rq, st));
-    // The three-workgroup cores (gemm_split.h: fp32 planes, bf16x3 split, bf16) take weights as [N][K] only: give the data
-    // gradients transposed copies of the three C x C blocks.  REGT_FP32_CORE=wide keeps the fp32 path on the two-workgroup
-    // core, which reads the weights as they are.
-    const bool split = gemm_mode() != 0 || !fp32_core_wide();
-    if (split) {
+    hipStream_t st = b.st;
+    if (f.split) {      // transposed copies of the three C x C blocks (h, z, r)
         PROF("transpose_gate_w", st);
         TRY(launch_transpose3(p.gate_w[2] + C, p.gate_w[0] + C, p.gate_w[1] + C, 3, L.UT, C, C, 2L * C, st));
     }
-    const bool wfr = abf && ibf && weights_frag(d) && d.regional;
-    const WbPtrs wb = wb_ptrs(L.Wb, C, F);
-    if (wfr) {
+    if (f.wfr) {
         CvtBatch cb{};
         cb.n = 3;
         for (int k = 0; k < 3; ++k) cb.t[k] = CvtTask{L.UT + (long)k * C * C, C, C, C, const_cast<float*>(wb.UT[k])};
         PROF("weights_bf16", st);
         TRY(launch_cvt_bf16_frag(cb, st));
     }
-    // bf16 arithmetic with fragment-order weights: the three data-gradient launches below as ONE kernel (fused.hip), every
-    // activation read and written once.  Same results bit for bit except the summation order of the attention gradient.
-    const bool fused = wfr && !h_ext && fused_backward_ok(C) && fused_bwd_wanted();
+    const bool fused = f.wfr && !b.ext && fused_backward_ok(C) && fused_bwd_wanted();
+    const bool gen = !fused && f.split && !f.ibf && !f.abf && gemm_dgrad1_gen_ok(M, C, N) && al16(L.Ht) && al16(L.dhp);
     if (fused) {
         FusedBwdArgs a{};
-        a.ZR = L.ZR; a.h = H; a.Ht = L.Ht; a.dOH = L.dOH; a.probs = L.probs;
+        a.ZR = L.ZR; a.h = b.H; a.Ht = L.Ht; a.dOH = L.dOH; a.probs = L.probs;
         a.UhTf = wb.UT[0]; a.UzTf = wb.UT[1]; a.UrTf = wb.UT[2];
-        a.dhp = L.dhp; a.dzr = L.dzr; a.dh = DH; a.rowdot = L.rowdot;
+        a.dhp = L.dhp; a.dzr = L.dzr; a.dh = b.DH; a.rowdot = L.rowdot;
         a.M = M; a.T = T; a.slope = d.lrelu_slope; a.act_lrelu = d.regional ? 1 : 0; a.tile_ctr = L.tile_ctr;
         {
             PROF("fused_backward", st);
             TRY(launch_fused_backward(a, C, st));
         }
-        if (gr.attention) {      // (one-workgroup tail of the attention gradient: off the critical path, joined before the slab reduction)
-            hipStream_t sa = side_fork(st);
-            TRY(launch_rowdot_reduce(L.rowdot, L.dp_partial, N, T, L.cb_npb, sa));
-            TRY(launch_att_bwd(L.dp_partial, L.cb_blocks, L.probs, gr.attention, T, sa));
-        }
-    } else {
-    // fp32 arithmetic at sizes the 128 x 128 core covers: dhp is GENERATED inside the candidate data gradient's K loop and dzp /
-    // the attention dots come out of its epilogue -- cell_bwd's pass over Z, h, H~ (5 C floats per row) does not happen
-    // (gemm_split.h: run_u_gen; REGT_DGRAD1_GEN=0 restores the two launches)
-    const bool gen = split && !ibf && !abf && gemm_dgrad1_gen_ok(M, C, N) && al16(L.Ht) && al16(L.dhp);
+        return attention_tail(b, 1);
+    }
     if (gen) {
-        GemmSegs S{};
-        S.nseg = 1;
-        S.seg[0] = make_seg(L.dhp, C, L.UT, nullptr, C, INT_MAX, C, true);      // (A is generated: the pointer is not read)
-        S.row_div = T;
-        EpiDgrad1 e{H, L.ZR, L.dOH, L.probs, L.dzr, DH, C, T};
+        EpiDgrad1 e{b.H, L.ZR, L.dOH, L.probs, L.dzr, b.DH, C, T};
         e.Ht = L.Ht; e.dhp = L.dhp; e.rowdot = L.rowdot; e.num_nodes = N;
         {
-            PROF("dgrad_candidate", st);
-            TRY(launch_gemm_dgrad1_gen(S, M, C, e, st));
+            PROF("dgrad_candidate", st);      // (A is generated: the segment's pointer is not read)
+            TRY(launch_gemm_dgrad1_gen(one_seg(make_seg(L.dhp, C, L.UT, nullptr, C, INT_MAX, C, true), T), M, C, e, st));
         }
-        if (gr.attention) {      // (tail of the attention gradient: off the critical path, joined before the slab reduction)
-            hipStream_t sa = side_fork(st);
-            TRY(launch_rowdot_reduce(L.rowdot, L.dp_partial, N, T, L.cb_npb, sa, C / 128));
-            TRY(launch_att_bwd(L.dp_partial, L.cb_blocks, L.probs, gr.attention, T, sa));
-        }
+        TRY(attention_tail(b, C / 128));
     } else {
-    // ---- cell: gate pre-activation gradients ------------------------------------------------------
-    {
-        CellBwdArgs a{L.dOH, L.probs, L.ZR, H, L.Ht, L.dhp, L.dzr, L.dp_partial, N, T, C, L.cb_npb};
-        a.out_bf16 = ibf; a.in_bf16 = abf;
+        CellBwdArgs a{L.dOH, L.probs, L.ZR, b.H, L.Ht, L.dhp, L.dzr, L.dp_partial, N, T, C, L.cb_npb};
+        a.out_bf16 = f.ibf; a.in_bf16 = f.abf;
         {
             PROF("cell_bwd", st);
             TRY(launch_cell_bwd(a, st));
         }
-        if (gr.attention) TRY(launch_att_bwd(L.dp_partial, L.cb_blocks, L.probs, gr.attention, T, side_fork(st)));
-    }
-    {   // dq = dhp Uh2 ; drp -> dzr[:, C:], dh = dq*R + p_t dOH Z
-        GemmSegs S{};
-        S.nseg = 1;
-        if (wfr) S.seg[0] = make_seg(L.dhp, C, wb.UT[0], nullptr, C, INT_MAX, C, true, SEG_A_BF16 | SEG_B_FRAG);
-        else if (split) S.seg[0] = make_seg(L.dhp, C, L.UT, nullptr, C, INT_MAX, C, true, ibf ? SEG_A_BF16 : 0);
-        else S.seg[0] = make_seg(L.dhp, C, p.gate_w[2] + C, nullptr, 2L * C, INT_MAX, C, false);
-        S.row_div = T;
-        EpiDgrad1 e{H, L.ZR, L.dOH, L.probs, L.dzr, DH, C, T};
-        e.dzr_bf16 = ibf; e.h_bf16 = abf; e.zr_bf16 = abf; e.dh_bf16 = abf;
+        TRY(attention_tail(b, 0));
+        // dq = dhp Uh2 ; drp -> dzr[:, C:], dh = dq*R + p_t dOH Z
+        const GemmSeg s = f.wfr   ? make_seg(L.dhp, C, wb.UT[0], nullptr, C, INT_MAX, C, true, SEG_A_BF16 | SEG_B_FRAG)
+                        : f.split ? make_seg(L.dhp, C, L.UT, nullptr, C, INT_MAX, C, true, f.ibf ? SEG_A_BF16 : 0)
+                                  : make_seg(L.dhp, C, p.gate_w[2] + C, nullptr, 2L * C, INT_MAX, C, false);
+        EpiDgrad1 e{b.H, L.ZR, L.dOH, L.probs, L.dzr, b.DH, C, T};
+        e.dzr_bf16 = f.ibf; e.h_bf16 = f.abf; e.zr_bf16 = f.abf; e.dh_bf16 = f.abf;
         PROF("dgrad_candidate", st);
-        TRY(launch_gemm_dgrad1(S, M, C, e, st));
+        TRY(launch_gemm_dgrad1(one_seg(s, T), M, C, e, st));
     }
+    if (f.tcol) return REGT_OK;      // ds is never formed: dh alone feeds dW0 / dW1 / db
+    // ds = (dh + dzp Uz2 + drp Ur2) * act'(h)
+    GemmSegs S{};
+    S.nseg = 2;
+    if (f.wfr) {      // (drp first: the accumulation order of the fused kernel, which multiplies drp while dzp is still on its way)
+        S.seg[0] = make_seg(byte_off(L.dzr, 2L * C), 2L * C, wb.UT[2], nullptr, C, INT_MAX, C, true, SEG_A_BF16 | SEG_B_FRAG);
+        S.seg[1] = make_seg(L.dzr, 2L * C, wb.UT[1], nullptr, C, INT_MAX, C, true, SEG_A_BF16 | SEG_B_FRAG);
+    } else if (f.split) {
+        const int fl = f.ibf ? SEG_A_BF16 : 0;
+        S.seg[0] = make_seg(byte_off(L.dzr, (f.ibf ? 2L : 4L) * C), 2L * C, L.UT + 2L * C * C, nullptr, C, INT_MAX, C, true, fl);
+        S.seg[1] = make_seg(L.dzr, 2L * C, L.UT + (long)C * C, nullptr, C, INT_MAX, C, true, fl);
+    } else {
+        S.seg[0] = make_seg(L.dzr, 2L * C, p.gate_w[0] + C, nullptr, 2L * C, INT_MAX, C, false);
+        S.seg[1] = make_seg(L.dzr + C, 2L * C, p.gate_w[1] + C, nullptr, 2L * C, INT_MAX, C, false);
     }
-    if (!tcol) {   // ds = (dh + dzp Uz2 + drp Ur2) * act'(h)      (FMT_TCOLLAPSE: never formed -- dh alone feeds dW0 / dW1 / db below)
-        GemmSegs S{};
-        S.nseg = 2;
-        if (wfr) {      // (drp first: the accumulation order of the fused kernel, which multiplies drp while dzp is still on its way)
-            S.seg[0] = make_seg(byte_off(L.dzr, 2L * C), 2L * C, wb.UT[2], nullptr, C, INT_MAX, C, true, SEG_A_BF16 | SEG_B_FRAG);
-            S.seg[1] = make_seg(L.dzr, 2L * C, wb.UT[1], nullptr, C, INT_MAX, C, true, SEG_A_BF16 | SEG_B_FRAG);
-        } else if (split) {
-            const int fl = ibf ? SEG_A_BF16 : 0;
-            S.seg[0] = make_seg(byte_off(L.dzr, (ibf ? 2L : 4L) * C), 2L * C, L.UT + 2L * C * C, nullptr, C, INT_MAX, C, true, fl);
-            S.seg[1] = make_seg(L.dzr, 2L * C, L.UT + (long)C * C, nullptr, C, INT_MAX, C, true, fl);
-        } else {
-            S.seg[0] = make_seg(L.dzr, 2L * C, p.gate_w[0] + C, nullptr, 2L * C, INT_MAX, C, false);
-            S.seg[1] = make_seg(L.dzr + C, 2L * C, p.gate_w[1] + C, nullptr, 2L * C, INT_MAX, C, false);
-        }
-        S.row_div = T;
-        EpiDgrad2 e{DH, H, C, d.regional ? ACT_LRELU : ACT_NONE, d.lrelu_slope};
-        e.h_bf16 = abf; e.dh_bf16 = abf;
-        PROF("dgrad_gates", st);
-        TRY(launch_gemm_dgrad2(S, M, C, e, st));
+    S.row_div = T;
+    EpiDgrad2 e{b.DH, b.H, C, d.regional ? ACT_LRELU : ACT_NONE, d.lrelu_slope};
+    e.h_bf16 = f.abf; e.dh_bf16 = f.abf;
+    PROF("dgrad_gates", st);
+    return launch_gemm_dgrad2(S, M, C, e, st);
+}
+
+// ---- weight gradients of the K = C contractions and of the composed (C, F) weights -----------------------------------------------------
+// The (C x F)-sized gradients (Gh, Gzr, A0 | A_r) are HBM-bound -- they stream dhp / dzp|drp / ds for a K = F..2F product -- while the
+// two big ones (Uh, Uzr) sit on the matrix pipe.  All run on the launch stream (issuing the former on the side stream so that the two
+// kinds overlap measured as noise).
+
+// dUh = dhp^T q, column sums -> dch
+static int wgrad_Uh(const Bwd& b, ReduceQueue& rq) {
+    const Layout& L = b.L; const StepForm& f = b.f;
+    const int C = b.d.C;
+    const long M = (long)b.d.N * b.d.T;
+    int kc = L.kchunk, nc = L.nchunks;
+    if (!f.ibf && !f.qbf) wgrad_wide_chunking(C, C, M, &kc, &nc);
+    return wgrad_full(rq, "wgrad_Uh", L.dhp, C, C, L.q, C, C, 0, M, kc, nc, b.gr.gate_w[2] + C, 2L * C, L.dch, b.st, f.ibf, f.qbf);
+}
+// dG = P^T (A_hat x) for P = dhp (Nout = C: dGh) or dzp|drp (Nout = 2C: dGzr)
+static int wgrad_G(const Bwd& b, ReduceQueue& rq, const char* name, const float* P, int Nout, float* out) {
+    const Layout& L = b.L; const StepForm& f = b.f;
+    const int F = b.d.F;
+    const long M = (long)b.d.N * b.d.T;
+    int kc = L.kchunk_s, nc = L.nchunks_s;
+    if (!f.ibf && !f.xbf && F <= 32) wgrad_skinny_chunking(Nout, M, &kc, &nc);
+    return wgrad_full(rq, name, P, Nout, Nout, L.AX, F, F, 0, M, kc, nc, out, F, nullptr, b.st, f.ibf, f.xbf);
+}
+// [dUz2; dUr2] = dzr^T h, column sums -> [dcz; dcr]
+static int wgrad_Uzr(const Bwd& b, ReduceQueue& rq) {
+    const Layout& L = b.L; const StepForm& f = b.f;
+    const int C = b.d.C;
+    const long M = (long)b.d.N * b.d.T;
+    int kc = L.kchunk, nc = L.nchunks;
+    if (!f.ibf && !f.abf) wgrad_wide_chunking(2 * C, C, M, &kc, &nc);
+    WgradArgs a{L.dzr, 2L * C, 2 * C, b.H, C, C, 0, M, kc, nullptr, nc, nullptr, 1};
+    a.p_bf16 = f.ibf; a.q_bf16 = f.abf;
+    WgradSlab w;
+    TRY(wgrad_launch(rq, a, "wgrad_Uzr", b.st, &w));
+    for (int k = 0; k < 2; ++k)
+        TRY(rq.push(w.block((long)k * C * C, C, C, b.gr.gate_w[k] + C, 2L * C).colsum(k == 0 ? L.dczr : nullptr, 2L * C * C, 2 * C)));
+    return REGT_OK;
+}
+// Collapsed TemporalGCN: [dP0 | dP1] = dzr^T [x | L~ x]  (2C x 2F), column sums -> [dcz; dcr]: what is left of dzr^T h (compose_backward
+// turns it into dUz2 / dUr2 / dW0 / dW1 / db).  One launch with a two-part right-hand side when F is a multiple of the 32-column
+// tile, else one launch per part.
+static int wgrad_P01(const Bwd& b, ReduceQueue& rq) {
+    const Layout& L = b.L; const StepForm& f = b.f;
+    const int F = b.d.F, C = b.d.C;
+    const long M = (long)b.d.N * b.d.T;
+    const bool two = F % 32 == 0;
+    const int Nin = two ? 2 * F : F;
+    for (int part = 0; part < (two ? 1 : 2); ++part) {
+        int kcs = L.kchunk_s, ncs = L.nchunks_s;
+        if (!f.ibf && !f.xbf && Nin <= 64) wgrad_skinny_chunking(2 * C, M, &kcs, &ncs);      // one wave of workgroups
+        WgradArgs a{L.dzr, 2L * C, 2 * C, part ? L.LX : b.Xp, F, Nin, 0, M, kcs, nullptr, ncs, nullptr, part == 0 ? 1 : 0};
+        if (two) { a.Q2 = L.LX; a.ldq2 = F; a.nin_split = F; }
+        WgradSlab w;
+        TRY(wgrad_launch(rq, a, "wgrad_P01", b.st, &w));
+        TRY(rq.push(w.block(0, 2 * C, Nin, L.dP01 + (two ? 0 : part * F), 2L * F).colsum(part == 0 ? L.dczr : nullptr, 2L * C * Nin, 2 * C)));
     }
-    }
-    // The (C x F)-sized gradients (Gh, Gzr, A0 | A_r) are HBM-bound -- they stream dhp / dzp|drp / ds for a K = F..2F product --
-    // while the two big ones (Uh, Uzr) sit on the matrix pipe.  (Issuing the former on the side stream so that the two kinds
-    // overlap: measured noise, round 3 -- see DESIGN.md section 6; they run on the launch stream.)
-    // ---- weight gradients of the K=C contractions and of the composed (C,F) weights -----------------
-    // bf16 rows (fused kernels' layout): dUh | dGh = dhp^T [q | A_hat x] and dUzr | dGzr = dzr^T [h | A_hat x] as ONE launch each -- the
-    // A_hat x part is a third column tile of the same row chunk on the same XCD, so dhp / dzp|drp cross HBM once instead of twice.
-    // (Round 3 measured this form slower, 1.86 vs 1.44 ms for the four: every tile issued the loads of BOTH right-hand operands.
-    // Since round 4 a column tile that lies entirely in one operand issues one load, wgrad_split_kernel q_tile.)
-    // With the ring kernel (round 4) the paired form wins (0.64 + 0.43 against 0.54 + 0.35 + 0.29 + 0.18 ms at the cfg-5 shard) and is
-    // the default whenever that kernel is on: regt_set_option("wgrad_pairs", 0 | 1 | 2 = follow the ring kernel).
-    const int pairs_opt = option(OPT_WGRAD_PAIRS);
-    const bool pairs = (pairs_opt == 2 ? wgrad_ring_active() : pairs_opt == 1) && ibf && qbf && abf && xbf && !h_ext && !tcol && C % 128 == 0 && F % 8 == 0;
-    if (pairs) {
+    return REGT_OK;
+}
+// Paired form (bf16 rows, the fused kernels' layout): dUh | dGh = dhp^T [q | A_hat x] and dUzr | dGzr = dzr^T [h | A_hat x] as ONE launch
+// each -- the A_hat x part is a third column tile of the same row chunk on the same XCD, so dhp / dzp|drp cross HBM once instead of
+// twice.  Measured: slower than the four launches (1.86 vs 1.44 ms at the cfg-5 shard) while every tile issued the loads of BOTH
+// right-hand operands; since a column tile that lies entirely in one operand issues one load (wgrad_split_kernel q_tile) and with the
+// ring kernel it wins (0.64 + 0.43 against 0.54 + 0.35 + 0.29 + 0.18 ms).  Hence the default: paired whenever the ring kernel is active --
+// regt_set_option("wgrad_pairs", 0 | 1 | 2 = follow the ring kernel).
+static int wgrad_paired(const Bwd& b, ReduceQueue& rq) {
+    const Layout& L = b.L;
+    const int F = b.d.F, C = b.d.C;
+    const long M = (long)b.d.N * b.d.T;
+    WgradSlab w;
+    {
         int kc = L.kchunk, nc = L.nchunks;
         wgrad_ring_chunking(C, C + F, M, &kc, &nc);          // one wave of workgroups (ring kernel), else the layout's chunks
         WgradArgs a{L.dhp, C, C, L.q, C, C + F, 0, M, kc, nullptr, nc, nullptr, 1};
         a.p_bf16 = 1; a.q_bf16 = 1; a.Q2 = L.AX; a.ldq2 = F; a.nin_split = C;
-        TRY(rq.take((long)nc * wgrad_slab_stride(a), &a.slab));
-        {
-            PROF("wgrad_UhGh", st);
-            TRY(launch_wgrad(a, st));
-        }
-        WgradReduceArgs r{};
-        r.slab = a.slab; r.nchunks = nc; r.slab_stride = wgrad_slab_stride(a); r.slab_ld = C + F; r.ngroups = 1;
-        r.elem_offset = 0; r.Nout = C; r.Nin = C; r.out = gr.gate_w[2] + C; r.ldo = 2L * C;
-        r.colsum_out = L.dch; r.colsum_offset = (long)C * (C + F); r.ncolsum = C;
-        TRY(rq.push(r));
-        WgradReduceArgs g{};
-        g.slab = a.slab; g.nchunks = nc; g.slab_stride = wgrad_slab_stride(a); g.slab_ld = C + F; g.ngroups = 1;
-        g.elem_offset = C; g.Nout = C; g.Nin = F; g.out = L.dGh; g.ldo = F;
-        TRY(rq.push(g));
-    } else {
-    {
-        int kc = L.kchunk, nc = L.nchunks;
-        if (!ibf && !qbf) wgrad_wide_chunking(C, C, M, &kc, &nc);
-        TRY(wgrad_full(rq, "wgrad_Uh", L.dhp, C, C, L.q, C, C, 0, M, kc, nc, gr.gate_w[2] + C, 2L * C, L.dch, st, ibf, qbf));
+        TRY(wgrad_launch(rq, a, "wgrad_UhGh", b.st, &w));
+        TRY(rq.push(w.block(0, C, C, b.gr.gate_w[2] + C, 2L * C).colsum(L.dch, (long)C * (C + F), C)));
+        TRY(rq.push(w.block(C, C, F, L.dGh, F)));
     }
-    {
-        int kc = L.kchunk_s, nc = L.nchunks_s;
-        if (!ibf && !xbf && F <= 32) wgrad_skinny_chunking(C, M, &kc, &nc);
-        TRY(wgrad_full(rq, "wgrad_Gh", L.dhp, C, C, L.AX, F, F, 0, M, kc, nc, L.dGh, F, nullptr, st, ibf, xbf));
-    }
-    }
-    if (pairs) {
-        int kc = L.kchunk, nc = L.nchunks;
-        wgrad_ring_chunking(2 * C, C + F, M, &kc, &nc);
-        WgradArgs a{L.dzr, 2L * C, 2 * C, H, C, C + F, 0, M, kc, nullptr, nc, nullptr, 1};
-        a.p_bf16 = 1; a.q_bf16 = 1; a.Q2 = L.AX; a.ldq2 = F; a.nin_split = C;
-        TRY(rq.take((long)nc * wgrad_slab_stride(a), &a.slab));
-        {
-            PROF("wgrad_UzrGzr", st);
-            TRY(launch_wgrad(a, st));
-        }
-        for (int k = 0; k < 2; ++k) {
-            WgradReduceArgs r{};
-            r.slab = a.slab; r.nchunks = nc; r.slab_stride = wgrad_slab_stride(a); r.slab_ld = C + F; r.ngroups = 1;
-            r.elem_offset = (long)k * C * (C + F); r.Nout = C; r.Nin = C; r.out = gr.gate_w[k] + C; r.ldo = 2L * C;
-            r.colsum_out = k == 0 ? L.dczr : nullptr; r.colsum_offset = 2L * C * (C + F); r.ncolsum = 2 * C;
-            TRY(rq.push(r));
-        }
-        WgradReduceArgs g{};
-        g.slab = a.slab; g.nchunks = nc; g.slab_stride = wgrad_slab_stride(a); g.slab_ld = C + F; g.ngroups = 1;
-        g.elem_offset = C; g.Nout = 2 * C; g.Nin = F; g.out = L.dGzr; g.ldo = F;
-        TRY(rq.push(g));
-    } else if (tcol) {
-        // [dP0 | dP1] = dzr^T [x | L~ x]  (2C x 2F), column sums -> [dcz; dcr]: what is left of dzr^T h (the composition backward
-        // below turns it into dUz2 / dUr2 / dW0 / dW1 / db).  One launch with a two-part right-hand side when F is a multiple of
-        // the 32-column tile, else one launch per part.
-        const bool two = F % 32 == 0;
-        for (int part = 0; part < (two ? 1 : 2); ++part) {
-            int kcs = L.kchunk_s, ncs = L.nchunks_s;
-            if (!ibf && !xbf && (two ? 2 * F : F) <= 64) wgrad_skinny_chunking(2 * C, M, &kcs, &ncs);      // one wave of workgroups
-            WgradArgs a{L.dzr, 2L * C, 2 * C, part ? L.LX : Xp, F, two ? 2 * F : F, 0, M, kcs, nullptr, ncs, nullptr, part == 0 ? 1 : 0};
-            if (two) { a.Q2 = L.LX; a.ldq2 = F; a.nin_split = F; }
-            TRY(rq.take((long)ncs * wgrad_slab_stride(a), &a.slab));
-            {
-                PROF("wgrad_P01", st);
-                TRY(launch_wgrad(a, st));
-            }
-            WgradReduceArgs r{};
-            r.slab = a.slab; r.nchunks = ncs; r.slab_stride = wgrad_slab_stride(a); r.elem_offset = 0;
-            r.Nout = 2 * C; r.Nin = two ? 2 * F : F; r.ngroups = 1;
-            r.out = L.dP01 + (two ? 0 : part * F); r.ldo = 2L * F;
-            r.colsum_out = part == 0 ? L.dczr : nullptr; r.colsum_offset = (long)2 * C * (two ? 2 * F : F); r.ncolsum = 2 * C;
-            TRY(rq.push(r));
-        }
-    } else {   // [dUz2; dUr2] = dzr^T h, column sums -> [dcz; dcr]
-        int kc = L.kchunk, nc = L.nchunks;
-        if (!ibf && !abf) wgrad_wide_chunking(2 * C, C, M, &kc, &nc);
-        WgradArgs a{L.dzr, 2L * C, 2 * C, H, C, C, 0, M, kc, nullptr, nc, nullptr, 1};
-        a.p_bf16 = ibf; a.q_bf16 = abf;
-        TRY(rq.take((long)nc * wgrad_slab_stride(a), &a.slab));
-        {
-            PROF("wgrad_Uzr", st);
-            TRY(launch_wgrad(a, st));
-        }
-        for (int k = 0; k < 2; ++k) {
-            WgradReduceArgs r{};
-            r.slab = a.slab; r.nchunks = nc; r.slab_stride = wgrad_slab_stride(a);
-            r.elem_offset = (long)k * C * C; r.Nout = C; r.Nin = C; r.ngroups = 1;
-            r.out = gr.gate_w[k] + C; r.ldo = 2L * C;
-            r.colsum_out = k == 0 ? L.dczr : nullptr; r.colsum_offset = 2L * C * C; r.ncolsum = 2 * C;
-            TRY(rq.push(r));
-        }
-    }
-    // (One launch per pair with a two-part right-hand side [q | A_hat x] / [h | A_hat x] -- so that dhp and dzp|drp are read
-    // once -- was measured and is slower: 1.86 vs 1.44 ms for the four at the cfg-5 shard; the third, half-empty column tile and
-    // the doubled load instructions of the two-descriptor staging cost more than the second pass over the left operand.)
-    if (!pairs) {
-        int kc = L.kchunk_s, nc = L.nchunks_s;
-        if (!ibf && !xbf && F <= 32) wgrad_skinny_chunking(2 * C, M, &kc, &nc);
-        TRY(wgrad_full(rq, "wgrad_Gzr", L.dzr, 2L * C, 2 * C, L.AX, F, F, 0, M, kc, nc, L.dGzr, F, nullptr, st, ibf, xbf));
-    }
-    float* dA0 = d.regional ? L.dA0 : gr.cheb_w0;
-    float* dAall = d.regional ? L.dAall : gr.cheb_w1;
-    float* dbpr = d.regional ? L.dbprime : gr.cheb_bias;
-    // node-disjoint regions (the headline case): dA0 = ds^T x and dA_r = ds^T (L~ x) share ds -- one launch over the
-    // region-pure row chunks with [x | L~ x] as a two-part right-hand side, so that ds is read from HBM once
-    const bool fuse_a = !h_ext && !g.overlap && R > 1 && F % 32 == 0;
-    if (fuse_a) {
+    int kc = L.kchunk, nc = L.nchunks;
+    wgrad_ring_chunking(2 * C, C + F, M, &kc, &nc);
+    WgradArgs a{L.dzr, 2L * C, 2 * C, b.H, C, C + F, 0, M, kc, nullptr, nc, nullptr, 1};
+    a.p_bf16 = 1; a.q_bf16 = 1; a.Q2 = L.AX; a.ldq2 = F; a.nin_split = C;
+    TRY(wgrad_launch(rq, a, "wgrad_UzrGzr", b.st, &w));
+    for (int k = 0; k < 2; ++k)
+        TRY(rq.push(w.block((long)k * C * (C + F), C, C, b.gr.gate_w[k] + C, 2L * C).colsum(k == 0 ? L.dczr : nullptr, 2L * C * (C + F), 2 * C)));
+    return rq.push(w.block(C, 2 * C, F, L.dGzr, F));
+}
+// Embedding gradients dA0 = ds^T x (column sums -> db') and dA_r = ds^T (L~ x), per region.  (TemporalGCN: the Cheb weights themselves.)
+static int wgrad_embedding(const Bwd& b, ReduceQueue& rq) {
+    if (b.ext) return REGT_OK;      // no embedding stage behind a caller-supplied hidden input
+    const regt_dims& d = b.d; const regt_graph& g = b.g; const Layout& L = b.L; const StepForm& f = b.f;
+    const int F = d.F, C = d.C, R = d.R;
+    const long M = (long)d.N * d.T;
+    float* dA0 = d.regional ? L.dA0 : b.gr.cheb_w0;
+    float* dAall = d.regional ? L.dAall : b.gr.cheb_w1;
+    float* dbpr = d.regional ? L.dbprime : b.gr.cheb_bias;
+    if (!g.overlap && R > 1 && F % 32 == 0) {
+        // node-disjoint regions (the headline case): dA0 and dA_r share ds -- one launch over the region-pure row chunks with
+        // [x | L~ x] as a two-part right-hand side, so that ds is read from HBM once
         REGT_CHECK_ARG(g.chunk_tab && g.chunk_region && g.n_chunks > 0, "backward: region chunk table missing");
-        WgradArgs a{L.dh, C, C, Xp, F, 2 * F, 0, M, 0, g.chunk_tab, g.n_chunks, nullptr, 1};
+        WgradArgs a{L.dh, C, C, b.Xp, F, 2 * F, 0, M, 0, g.chunk_tab, g.n_chunks, nullptr, 1};
         a.Q2 = L.LX; a.ldq2 = F; a.nin_split = F;
-        a.p_bf16 = abf; a.q_bf16 = xbf;
-        TRY(rq.take((long)g.n_chunks * wgrad_slab_stride(a), &a.slab));
-        {
-            PROF("wgrad_A0_Ar", st);
-            TRY(launch_wgrad(a, st));
-        }
-        WgradReduceArgs r0{};
-        r0.slab = a.slab; r0.nchunks = g.n_chunks; r0.slab_stride = wgrad_slab_stride(a); r0.elem_offset = 0; r0.slab_ld = 2 * F;
-        r0.Nout = C; r0.Nin = F; r0.chunk_group = nullptr; r0.ngroups = 1; r0.out = dA0; r0.ldo = F;
-        r0.colsum_out = dbpr; r0.colsum_offset = 2L * C * F; r0.ncolsum = C;
-        TRY(rq.push(r0));
-        WgradReduceArgs r1{};
-        r1.slab = a.slab; r1.nchunks = g.n_chunks; r1.slab_stride = wgrad_slab_stride(a); r1.elem_offset = F; r1.slab_ld = 2 * F;
+        a.p_bf16 = f.abf; a.q_bf16 = f.xbf;
+        WgradSlab w;
+        TRY(wgrad_launch(rq, a, "wgrad_A0_Ar", b.st, &w));
+        TRY(rq.push(w.block(0, C, F, dA0, F).colsum(dbpr, 2L * C * F, C)));
         int lo, hi;
         region_range(d, g, &lo, &hi);           // only the owned region blocks have rows here (and are read later)
-        r1.Nout = C; r1.Nin = F; r1.chunk_group = g.chunk_region; r1.ngroups = hi - lo; r1.group_base = lo;
-        r1.out = dAall + (long)lo * C * F; r1.ldo = F;
-        r1.group_stride = (long)C * F;
-        TRY(rq.push(r1));
+        return rq.push(w.block(F, C, F, dAall + (long)lo * C * F, F).groups(g.chunk_region, hi - lo, lo, (long)C * F));
     }
-    if (!h_ext && !fuse_a) TRY(wgrad_full(rq, "wgrad_A0", L.dh, C, C, Xp, F, F, 0, M, L.kchunk_s, L.nchunks_s, dA0, F, dbpr, st, abf, 0));
-    if (h_ext || fuse_a) {
-        // no embedding stage behind a caller-supplied hidden input / already done above
-    } else if (g.overlap) {   // one unmasked (C x F) gradient per region: dA_r = ds^T (L~_r x)
+    TRY(wgrad_full(rq, "wgrad_A0", L.dh, C, C, b.Xp, F, F, 0, M, L.kchunk_s, L.nchunks_s, dA0, F, dbpr, b.st, f.abf, 0));
+    if (g.overlap) {   // one unmasked (C x F) gradient per region: dA_r = ds^T (L~_r x)
         for (int r = 0; r < R; ++r)
             TRY(wgrad_full(rq, "wgrad_Ar", L.dh, C, C, L.LX + (long)r * M * F, F, F, 0, M, L.kchunk_s, L.nchunks_s,
-                           dAall + (long)r * C * F, F, nullptr, st, abf, 0));
-    } else if (R > 1) {   // per-region dA_r = sum over the region's rows of ds^T (L~ x)
-        REGT_CHECK_ARG(g.chunk_tab && g.chunk_region && g.n_chunks > 0, "backward: region chunk table missing");
-        WgradArgs a{L.dh, C, C, L.LX, F, F, 0, M, 0, g.chunk_tab, g.n_chunks, nullptr, 0};
-        a.p_bf16 = abf;
-        TRY(rq.take((long)g.n_chunks * wgrad_slab_stride(a), &a.slab));
-        {
-            PROF("wgrad_Ar", st);
-            TRY(launch_wgrad(a, st));
-        }
-        WgradReduceArgs r{};
-        r.slab = a.slab; r.nchunks = g.n_chunks; r.slab_stride = wgrad_slab_stride(a); r.elem_offset = 0;
-        r.Nout = C; r.Nin = F; r.chunk_group = g.chunk_region; r.ngroups = R; r.out = dAall; r.ldo = F;
-        r.group_stride = (long)C * F;
-        TRY(rq.push(r));
+                           dAall + (long)r * C * F, F, nullptr, b.st, f.abf, 0));
+        return REGT_OK;
+    }
+    if (R == 1) return wgrad_full(rq, "wgrad_Ar", L.dh, C, C, L.LX, F, F, 0, M, L.kchunk_s, L.nchunks_s, dAall, F, nullptr, b.st, f.abf, 0);
+    // per-region dA_r = sum over the region's rows of ds^T (L~ x), over the region-pure row chunks
+    REGT_CHECK_ARG(g.chunk_tab && g.chunk_region && g.n_chunks > 0, "backward: region chunk table missing");
+    WgradArgs a{L.dh, C, C, L.LX, F, F, 0, M, 0, g.chunk_tab, g.n_chunks, nullptr, 0};
+    a.p_bf16 = f.abf;
+    WgradSlab w;
+    TRY(wgrad_launch(rq, a, "wgrad_Ar", b.st, &w));
+    return rq.push(w.block(0, C, F, dAall, F).groups(g.chunk_region, R, 0, (long)C * F));
+}
+
+// One branch per form, each complete in itself: paired (bf16 rows with the ring kernel, see wgrad_paired), collapsed (TemporalGCN,
+// FMT_TCOLLAPSE: dzr^T h becomes dzr^T [x | L~ x]) or plain; then the embedding gradients.
+static int weight_gradients(const Bwd& b, ReduceQueue& rq) {
+    const Layout& L = b.L; const StepForm& f = b.f;
+    const int F = b.d.F, C = b.d.C;
+    const int pairs_opt = option(OPT_WGRAD_PAIRS);
+    const bool pairs = (pairs_opt == 2 ? wgrad_ring_active() : pairs_opt == 1) && f.ibf && f.qbf && f.abf && f.xbf && !b.ext && !f.tcol &&
+                       C % 128 == 0 && F % 8 == 0;
+    if (pairs) {
+        TRY(wgrad_paired(b, rq));
+    } else if (f.tcol) {
+        TRY(wgrad_Uh(b, rq));
+        TRY(wgrad_G(b, rq, "wgrad_Gh", L.dhp, C, L.dGh));
+        TRY(wgrad_P01(b, rq));
+        TRY(wgrad_G(b, rq, "wgrad_Gzr", L.dzr, 2 * C, L.dGzr));
     } else {
-        TRY(wgrad_full(rq, "wgrad_Ar", L.dh, C, C, L.LX, F, F, 0, M, L.kchunk_s, L.nchunks_s, dAall, F, nullptr, st, abf, 0));
+        TRY(wgrad_Uh(b, rq));
+        TRY(wgrad_G(b, rq, "wgrad_Gh", L.dhp, C, L.dGh));
+        TRY(wgrad_Uzr(b, rq));
+        TRY(wgrad_G(b, rq, "wgrad_Gzr", L.dzr, 2 * C, L.dGzr));
     }
+    return wgrad_embedding(b, rq);
+}
+
+// Back through the weight compositions of compose_forward (tiny; one launch of at most 19 tasks: nothing below reads what another
+// task writes -- G0 = dA0 W0^T + db' b_c^T, what EVERY block of d tgnn.linear.weight receives, is summed inside each block's task
+// instead of through a buffer).
+static int compose_backward(const Bwd& b) {
+    const regt_dims& d = b.d; const regt_graph& g = b.g; const regt_params& p = b.p; const regt_grads& gr = b.gr; const Layout& L = b.L;
+    const int F = d.F, C = d.C, R = d.R;
+    PROF("compose_bwd", b.st);
+    SgBatch sb{};
+    for (int k = 0; k < 3; ++k) {
+        const float* dG = k < 2 ? L.dGzr + (long)k * C * F : L.dGh;
+        const float* dc = k < 2 ? L.dczr + (long)k * C : L.dch;
+        // dU_k[:, :C] = dG_k V_k^T + dc_k beta_k^T
+        add_task(sb, gr.gate_w[k], 2L * C, 1, 0, C, C, 1, nullptr, 0,
+                 {term(dG, F, 1, 0, p.conv_lin_w[k], 1, F, 0, F), term(dc, 1, 0, 0, p.conv_bias[k], 0, 1, 0, 1)});
+        // dV_k = U_k[:, :C]^T dG_k ; dbeta_k = U_k[:, :C]^T dc_k
+        // (stated transposed -- output "rows" j, "columns" i -- so that consecutive lanes walk the CONTIGUOUS index i of the
+        // left factor U_k[k, i]; as (i, j) every k-step of a lane group touched lines 2C floats apart)
+        add_task(sb, gr.conv_lin_w[k], 1, F, 0, F, C, 1, nullptr, 0, {term(dG, 1, F, 0, p.gate_w[k], 2L * C, 1, 0, C)});
+        add_task(sb, gr.conv_bias[k], 1, 0, 0, C, 1, 1, nullptr, 0, {term(p.gate_w[k], 1, 2L * C, 0, dc, 1, 0, 0, C)});
+    }
+    for (int k = 0; k < 3; ++k)      // du_k = dc_k
+        add_task(sb, gr.gate_b[k], 1, 0, 0, C, 1, 1, k < 2 ? L.dczr + (long)k * C : L.dch, 1, {});
+    if (b.f.tcol) {
+        // back through P0_k = U_k2 W0, P1_k = U_k2 W1, c'_k = c_k + U_k2 b  (k = z, r):
+        //   dU_k2 = dP0_k W0^T + dP1_k W1^T + dc_k b^T ;  dW0 += sum_k U_k2^T dP0_k ;  dW1 += sum_k U_k2^T dP1_k ;  db += sum_k U_k2^T dc_k
+        // (dW0 / dW1 / db already hold the direct path dh^T x / dh^T L~ x / colsum dh from the slab reduction: added in place;
+        // the last three stated transposed -- output "rows" f, "columns" c -- so that lanes walk the contiguous index of U_k2)
+        const float* dP0[2] = {L.dP01, L.dP01 + (long)C * 2 * F};
+        const float* dP1[2] = {L.dP01 + F, L.dP01 + (long)C * 2 * F + F};
+        const float* dc[2] = {L.dczr, L.dczr + C};
+        for (int k = 0; k < 2; ++k)
+            add_task(sb, gr.gate_w[k] + C, 2L * C, 1, 0, C, C, 1, nullptr, 0,
+                     {term(dP0[k], 2L * F, 1, 0, p.cheb_w0, 1, F, 0, F), term(dP1[k], 2L * F, 1, 0, p.cheb_w1, 1, F, 0, F),
+                      term(dc[k], 1, 0, 0, p.cheb_bias, 0, 1, 0, 1)});
+        add_task(sb, gr.cheb_w0, 1, F, 0, F, C, 1, gr.cheb_w0, 1,
+                 {term(dP0[0], 1, 2L * F, 0, p.gate_w[0] + C, 2L * C, 1, 0, C), term(dP0[1], 1, 2L * F, 0, p.gate_w[1] + C, 2L * C, 1, 0, C)}, F);
+        add_task(sb, gr.cheb_w1, 1, F, 0, F, C, 1, gr.cheb_w1, 1,
+                 {term(dP1[0], 1, 2L * F, 0, p.gate_w[0] + C, 2L * C, 1, 0, C), term(dP1[1], 1, 2L * F, 0, p.gate_w[1] + C, 2L * C, 1, 0, C)}, F);
+        add_task(sb, gr.cheb_bias, 1, 0, 0, C, 1, 1, gr.cheb_bias, 1,
+                 {term(p.gate_w[0] + C, 1, 2L * C, 0, dc[0], 1, 0, 0, C), term(p.gate_w[1] + C, 1, 2L * C, 0, dc[1], 1, 0, 0, C)});
+    }
+    if (d.regional) {
+        const long RC = (long)R * C;
+        int lo, hi;
+        region_range(d, g, &lo, &hi);
+        // dWl_r = G0 + dA_r W1^T for the owned regions, G0 alone for the others (their rows live on other GPUs);
+        // G0 = dA0 W0^T + db' b_c^T (A0 and b' sum over all regions)
+        const SgTerm g0a = term(L.dA0, F, 1, 0, p.cheb_w0, 1, F, 0, F), g0b = term(L.dbprime, 1, 0, 0, p.cheb_bias, 0, 1, 0, 1);
+        add_task(sb, gr.region_w + (long)lo * C, RC, 1, C, C, C, hi - lo, nullptr, 0,
+                 {g0a, g0b, term(L.dAall + (long)lo * C * F, F, 1, (long)C * F, p.cheb_w1, 1, F, 0, F)});
+        if (lo > 0) add_task(sb, gr.region_w, RC, 1, C, C, C, lo, nullptr, 0, {g0a, g0b});
+        if (hi < R) add_task(sb, gr.region_w + (long)hi * C, RC, 1, C, C, C, R - hi, nullptr, 0, {g0a, g0b});
+        // dW0 = S^T dA0 ; dW1 = sum_{owned r} Wl_r^T dA_r ; db_c = S^T db' ; db_l = db'
+        // (both stated transposed, see dV_k above: tgnn.linear.weight rows are R*C floats apart)
+        add_task(sb, gr.cheb_w0, 1, F, 0, F, C, 1, nullptr, 0, {term(L.dA0, 1, F, 0, L.S, C, 1, 0, C)});
+        add_task(sb, gr.cheb_w1, 1, F, 0, F, C, 1, nullptr, 0,
+                 {term(L.dAall + (long)lo * C * F, 1, F, (long)C * F, p.region_w + (long)lo * C, RC, 1, C, C, hi - lo, 1)});
+        add_task(sb, gr.cheb_bias, 1, 0, 0, C, 1, 1, nullptr, 0, {term(L.S, 1, C, 0, L.dbprime, 1, 0, 0, C)});
+        add_task(sb, gr.region_b, 1, 0, 0, C, 1, 1, L.dbprime, 1, {});
+    }
+    return launch_small_gemm_multi(sb, b.st);
+}
+
+// The backward, four stages in this order: head, data gradients of the cell, weight gradients (their slab reductions deferred into ONE
+// launch, ReduceQueue), and back through the weight compositions.  No sparse op: A_hat x and L~ x are constants.
+// `h_ext` / `dh_ext` != NULL (regt_cell_backward): the hidden input was supplied by the caller; its gradient is
+// written to dh_ext and the embedding-stage gradients (A0 / A_r / Cheb weights) are skipped.
+int backward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, const regt_grads& gr,
+                  const float* dpred, const float* dhidden, const float* hidden, const float* xp_ext, const Layout& L,
+                  hipStream_t st, int fmt, const float* h_ext, float* dh_ext) {
+    const StepForm f = step_form(d, fmt, h_ext != nullptr);
+    const Bwd b{d, g, p, gr, L, f, wb_ptrs(L.Wb, d.C, d.F),
+                (xp_ext && (!f.xbf || (fmt & FMT_XCALLER))) ? xp_ext : L.Xp, h_ext ? h_ext : L.h, dh_ext ? dh_ext : L.dh, h_ext != nullptr, st};
+    ReduceQueue rq(L.slab, L.slab_floats, st);
+    TRY(head_backward(d, p, gr, dpred, dhidden, hidden, L.y1, L.d1, L.dOH, rq, st));
+    TRY(data_gradients(b));
+    TRY(weight_gradients(b, rq));
     TRY(rq.flush());      // every slab reduction of this backward pass, one launch
-    // ---- back through the weight compositions (tiny; one launch) ------------------------------------------
-    PROF("compose_bwd", st);
-    {
-        SgBatch b{};
-        for (int k = 0; k < 3; ++k) {
-            const float* dG = k < 2 ? L.dGzr + (long)k * C * F : L.dGh;
-            const float* dc = k < 2 ? L.dczr + (long)k * C : L.dch;
-            // dU_k[:, :C] = dG_k V_k^T + dc_k beta_k^T
-            add_task(b, gr.gate_w[k], 2L * C, 1, 0, C, C, 1, nullptr, 0,
-                     {term(dG, F, 1, 0, p.conv_lin_w[k], 1, F, 0, F), term(dc, 1, 0, 0, p.conv_bias[k], 0, 1, 0, 1)});
-            // dV_k = U_k[:, :C]^T dG_k ; dbeta_k = U_k[:, :C]^T dc_k
-            // (stated transposed -- output "rows" j, "columns" i -- so that consecutive lanes walk the CONTIGUOUS index i of the
-            // left factor U_k[k, i]; as (i, j) every k-step of a lane group touched lines 2C floats apart)
-            add_task(b, gr.conv_lin_w[k], 1, F, 0, F, C, 1, nullptr, 0, {term(dG, 1, F, 0, p.gate_w[k], 2L * C, 1, 0, C)});
-            add_task(b, gr.conv_bias[k], 1, 0, 0, C, 1, 1, nullptr, 0, {term(p.gate_w[k], 1, 2L * C, 0, dc, 1, 0, 0, C)});
-        }
-        // (one launch since round 4: nothing below reads what the tasks above write -- G0 = dA0 W0^T + db' b_c^T, what EVERY
-        // block of d tgnn.linear.weight receives, is summed inside each block's task instead of through a buffer)
-        for (int k = 0; k < 3; ++k)      // du_k = dc_k
-            add_task(b, gr.gate_b[k], 1, 0, 0, C, 1, 1, k < 2 ? L.dczr + (long)k * C : L.dch, 1, {});
-        if (tcol) {
-            // back through P0_k = U_k2 W0, P1_k = U_k2 W1, c'_k = c_k + U_k2 b  (k = z, r):
-            //   dU_k2 = dP0_k W0^T + dP1_k W1^T + dc_k b^T ;  dW0 += sum_k U_k2^T dP0_k ;  dW1 += sum_k U_k2^T dP1_k ;  db += sum_k U_k2^T dc_k
-            // (dW0 / dW1 / db already hold the direct path dh^T x / dh^T L~ x / colsum dh from the slab reduction above: added in place;
-            // the last three stated transposed -- output "rows" f, "columns" c -- so that lanes walk the contiguous index of U_k2)
-            const float* dP0[2] = {L.dP01, L.dP01 + (long)C * 2 * F};
-            const float* dP1[2] = {L.dP01 + F, L.dP01 + (long)C * 2 * F + F};
-            const float* dc[2] = {L.dczr, L.dczr + C};
-            for (int k = 0; k < 2; ++k)
-                add_task(b, gr.gate_w[k] + C, 2L * C, 1, 0, C, C, 1, nullptr, 0,
-                         {term(dP0[k], 2L * F, 1, 0, p.cheb_w0, 1, F, 0, F), term(dP1[k], 2L * F, 1, 0, p.cheb_w1, 1, F, 0, F),
-                          term(dc[k], 1, 0, 0, p.cheb_bias, 0, 1, 0, 1)});
-            add_task(b, gr.cheb_w0, 1, F, 0, F, C, 1, gr.cheb_w0, 1,
-                     {term(dP0[0], 1, 2L * F, 0, p.gate_w[0] + C, 2L * C, 1, 0, C), term(dP0[1], 1, 2L * F, 0, p.gate_w[1] + C, 2L * C, 1, 0, C)}, F);
-            add_task(b, gr.cheb_w1, 1, F, 0, F, C, 1, gr.cheb_w1, 1,
-                     {term(dP1[0], 1, 2L * F, 0, p.gate_w[0] + C, 2L * C, 1, 0, C), term(dP1[1], 1, 2L * F, 0, p.gate_w[1] + C, 2L * C, 1, 0, C)}, F);
-            add_task(b, gr.cheb_bias, 1, 0, 0, C, 1, 1, gr.cheb_bias, 1,
-                     {term(p.gate_w[0] + C, 1, 2L * C, 0, dc[0], 1, 0, 0, C), term(p.gate_w[1] + C, 1, 2L * C, 0, dc[1], 1, 0, 0, C)});
-        }
-        if (d.regional) {
-            const long RC = (long)R * C;
-            int lo, hi;
-            region_range(d, g, &lo, &hi);
-            // dWl_r = G0 + dA_r W1^T for the owned regions, G0 alone for the others (their rows live on other GPUs);
-            // G0 = dA0 W0^T + db' b_c^T (A0 and b' sum over all regions)
-            const SgTerm g0a = term(L.dA0, F, 1, 0, p.cheb_w0, 1, F, 0, F), g0b = term(L.dbprime, 1, 0, 0, p.cheb_bias, 0, 1, 0, 1);
-            add_task(b, gr.region_w + (long)lo * C, RC, 1, C, C, C, hi - lo, nullptr, 0,
-                     {g0a, g0b, term(L.dAall + (long)lo * C * F, F, 1, (long)C * F, p.cheb_w1, 1, F, 0, F)});
-            if (lo > 0) add_task(b, gr.region_w, RC, 1, C, C, C, lo, nullptr, 0, {g0a, g0b});
-            if (hi < R) add_task(b, gr.region_w + (long)hi * C, RC, 1, C, C, C, R - hi, nullptr, 0, {g0a, g0b});
-            // dW0 = S^T dA0 ; dW1 = sum_{owned r} Wl_r^T dA_r ; db_c = S^T db' ; db_l = db'
-            // (both stated transposed, see dV_k above: tgnn.linear.weight rows are R*C floats apart)
-            add_task(b, gr.cheb_w0, 1, F, 0, F, C, 1, nullptr, 0, {term(L.dA0, 1, F, 0, L.S, C, 1, 0, C)});
-            add_task(b, gr.cheb_w1, 1, F, 0, F, C, 1, nullptr, 0,
-                     {term(L.dAall + (long)lo * C * F, 1, F, (long)C * F, p.region_w + (long)lo * C, RC, 1, C, C, hi - lo, 1)});
-            add_task(b, gr.cheb_bias, 1, 0, 0, C, 1, 1, nullptr, 0, {term(L.S, 1, C, 0, L.dbprime, 1, 0, 0, C)});
-            add_task(b, gr.region_b, 1, 0, 0, C, 1, 1, L.dbprime, 1, {});
-        }
-        TRY(launch_small_gemm_multi(b, st));
-    }
-    return REGT_OK;
+    return compose_backward(b);
 }
 
 }  // namespace regt
