@@ -3,7 +3,10 @@
 Same op site (RegionalTemporalGCN.py:136-148 in the composed-weight form), same operands, another summation order over k (the
 16x16x4 fp32 MFMA instead of the 32x32x2 one): outputs and every gradient agree to fp32 rounding, and both agree with the
 oracle inside tests/test_gpu_model.py's bars.  Shapes: several regions per graph (tiles that straddle a region boundary run one
-pass per region), a row count that is no multiple of the 128-row tile, one region (no region lookup at all)."""
+pass per region), a row count that is no multiple of the 128-row tile, one region (no region lookup at all).
+
+This file compares whole models at bars relative to a tensor's maximum; the kernel's own output h is held per element against
+float64 (and bit for bit on exactly summable inputs, at ragged region layouts) in tests/test_gpu_embed_bars.py."""
 import pytest
 import torch
 

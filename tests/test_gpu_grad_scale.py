@@ -88,6 +88,38 @@ def _overlap(n, e, regions, f, t, o):
     return Case(p, y, (x, ei, ri, rw), M.regional_temporal_gcn, lambda R: R.RegionalTemporalGCN(f, n, t, o, num_regions=regions), num_regions=regions)
 
 
+def _ragged(n, f, t, o):
+    """Regions of 1, 2, 3, 5, 8, 11, 40, 300 nodes in turn (embed_probe.ragged_blocks) with random directed edges inside each region
+    and ordinary random parameters: a node without regional in-edges joins the region in front of it (graph.node_regions), so
+    graph.region_chunks holds chunks of a single node, 64-row tiles hold three and more regions and some region ids own no row
+    (tests/test_embed_probe_cpu.py checks that on the host, and that the fp32 oracle is within REL / 4 of float64 on every block)."""
+    from embed_probe import ragged_blocks
+    g = torch.Generator().manual_seed(n)
+    blocks = ragged_blocks(n)
+    ri, rw, start = [], [], 0
+    for size in blocks:
+        if size == 1:                                # no edge inside one node: a self loop (dropped by ChebConv) keeps the list non-empty
+            ei = torch.tensor([[start], [start]])
+        elif size <= 3:                              # every edge into the block's last node: it alone owns rows of this region
+            ei = torch.stack([start + torch.arange(size - 1), torch.full((size - 1,), start + size - 1)])
+        else:
+            e = size
+            src = start + torch.randint(0, size, (e,), generator=g)
+            dst = start + (src - start + 1 + torch.randint(0, size - 1, (e,), generator=g)) % size
+            ei = torch.stack([src, dst])
+        ri.append(ei.contiguous())
+        rw.append(torch.rand(ei.shape[1], generator=g) * 2925 + 75)
+        start += size
+    cross = torch.randint(0, n, (2, n // 2), generator=g)
+    ei = torch.cat(ri + [cross[:, cross[0] != cross[1]]], dim=1).contiguous()
+    x = torch.rand(n, f, t, generator=g)
+    y = torch.rand(n, o, generator=g)
+    regions = len(blocks)
+    p = M.init_params("RegionalTemporalGCN", f, t, o, num_nodes=n, num_regions=regions, seed=6)
+    return Case(p, y, (x, ei, ri, rw), M.regional_temporal_gcn,
+                lambda R: R.RegionalTemporalGCN(node_features=f, num_nodes=n, periods=t, output_dim=o, num_regions=regions), num_regions=regions)
+
+
 def _tgcn(n, e, f, t, o):
     from test_gpu_model import _synthetic
     ei, _ri, rw, x = _synthetic(n, e, 1, f, t, seed=n)               # one region: rw[0] weighs every edge of ei
@@ -145,9 +177,12 @@ CASES = {
     # RegionalTemporalGCN, small-tile regime; F = 7 is no multiple of 4: generic weight-gradient kernels
     "regt-777-4000-3-8-6-3": (lambda: _regt(777, 4000, 3, 8, 6, 3), [()]),
     "regt-600-4000-3-7-5-2": (lambda: _regt(600, 4000, 3, 7, 5, 2), [()]),
-    # big-tile regime: the smallest shape of the suite that reaches gemm_dgrad1_gen_kernel, embed_fp32_kernel (embed_fp32_ok), the
-    # 64-column weight-gradient tile and the region chunk table with grouped reduction
+    # big-tile regime (18 000 rows): the smallest shape of the suite that reaches gemm_dgrad1_gen_kernel, the 64-column weight-gradient
+    # tile and the region chunk table with grouped reduction.  (Not embed_fp32_kernel: embed_fp32_ok needs 65 536 rows --
+    # tests/test_gpu_embed_bars.py holds that kernel.)
     "regt-1500-15000-8-32-12-1": (lambda: _regt(1500, 15000, 8, 32, 12, 1), [((b"dgrad1_gen", 1),), ((b"dgrad1_gen", 0),)]),
+    # ragged regions of 1 .. 300 nodes: region chunks of a single node, tiles with three and more regions, region ids without rows
+    "ragged-700-8-6-1": (lambda: _ragged(700, 8, 6, 1), [()]),
     # many regions: lins.1's gradient is tiny
     "regt-2000-16000-64-8-6-1": (lambda: _regt(2000, 16000, 64, 8, 6, 1), [()]),
     "tgcn-1409-9000-1-8-6-2": (lambda: _tgcn(1409, 9000, 8, 6, 2), [((b"tgcn_collapse", 1),), ((b"tgcn_collapse", 0),)]),
