@@ -1,6 +1,6 @@
 // Element-wise / reduction kernels around the GRU cell (models/utils.py:163-203) and the attention
 // over periods (models/RegionalTemporalGCN.py:134,146).  The gate non-linearities of the *forward*
-// live in the GEMM epilogues (gemm.hip); this file holds the head of the backward pass -- one fused
+// live in the GEMM epilogues (gemm_fwd.hip, gemm_cell.hip); this file holds the head of the backward pass -- one fused
 // kernel that turns dL/dH_accum into the three gate pre-activation gradients -- plus the softmax of
 // the T attention logits, its backward, and the MSE loss gradient of run.py:180.
 #include "kernels.h"

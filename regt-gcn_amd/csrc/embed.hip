@@ -169,7 +169,7 @@ __global__ __launch_bounds__(512, 2) void embed_fp32_kernel(EmbedArgs a) {
                     for (int i = 0; i < 4; ++i) v[i] = v[i] > 0.f ? v[i] : v[i] * a.ns;
                     // (the column block's offset goes into the vector offset -- an immediate for the instruction -- not into soffset: a
                     // 16-byte buffer store with an SGPR soffset whose data registers the next instruction overwrites picks up the NEW
-                    // value now and then on gfx950, and hipcc pads that hazard only when soffset is an immediate (gemm.hip, top).  With
+                    // value now and then on gfx950, and hipcc pads that hazard only when soffset is an immediate (gemm_epilogue.h, top).  With
                     // the row-block loop unrolled the next MFMA's destination WAS the store's data: wrong rows in half of the runs)
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), so, voff + 64 * cb, 0, 0);
                 }

@@ -19,7 +19,7 @@ __device__ __forceinline__ float4 f_widen4(unsigned lo, unsigned hi) {
 struct V8 { float v[8]; };
 // Packed (two-lane) fp32 arithmetic for the epilogues: a VALU instruction of this kernel costs matrix-pipe time of its SIMD partner
 // (DESIGN 5c.1), and v_pk_add / v_pk_mul / v_pk_fma do two elements per instruction with the same IEEE results as the scalar forms.
-// The operation SEQUENCES are those of fast_sigmoid / fast_tanh (gemm.hip): mul by -log2(e), exp2, add 1, rcp -- bit for bit.
+// The operation SEQUENCES are those of fast_sigmoid / fast_tanh (gemm_epilogue.h): mul by -log2(e), exp2, add 1, rcp -- bit for bit.
 typedef float f2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ V8 f_sigmoid8(const V8& v, const V8& b) {
     V8 o;

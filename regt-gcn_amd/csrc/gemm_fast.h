@@ -348,7 +348,7 @@ struct FastCore {
     // row, 8 for two to four), and the first round is requested BEFORE the accumulators are staged through LDS, so that
     // its latency overlaps the 64 LDS writes and the barrier.
     // Full tile + a functor variant: the straight-line body (no row / column guards, no functor branches; see the note on
-    // the functors in gemm.hip).  Rounds of RR rows; when two rounds of auxiliary operands fit the registers the
+    // the functors in gemm_fwd.hip / gemm_cell.hip).  Rounds of RR rows; when two rounds of auxiliary operands fit the registers the
     // accumulators free up once they are staged, round g + 1 is requested BEFORE round g is applied, so that its loads
     // are ahead of round g's stores in the (in-order) vmcnt queue and never wait for a store to complete.
     __device__ __forceinline__ EpiRowEnt* rowtab() const { return reinterpret_cast<EpiRowEnt*>(table + G_MAX_ITERS); }

@@ -188,7 +188,7 @@ struct SplitCore : FastCore<true, REGION> {
     // walk over (segment, repeat, k0) and the descriptors stay in scalar registers, computed by the scalar unit from
     // the kernel arguments: the base pointer of the tile's rows, num_records = the bytes of the VALID rows (rows past the
     // end return 0 through the range check: no per-load guard), the slab's k offset as the instruction's scalar offset;
-    // what is left per slab are four v_mad for the per-thread row offsets.  Requirements (host: uniform_ok in gemm.hip):
+    // what is left per slab are four v_mad for the per-thread row offsets.  Requirements (host: uniform_ok in gemm_dispatch.hip):
     // no region-masked segment, every K a multiple of 32, rows of a tile consecutive (rm.mul == 1).
     // Region-masked segments (REGION kernels): the segment repeats once per DISTINCT region among the tile's rows (sorted
     // list from tile_regions, copied to the unused iteration-table area by uniform_regions()); a row takes part in the
@@ -329,7 +329,7 @@ struct SplitCore : FastCore<true, REGION> {
     // cell_bwd_kernel read Z, h, H~ and wrote dhp, dzp (5 C floats per row) only to hand dhp to this GEMM, which read it back.
     // Here the A slots of a thread are FORMED from Z, H~ and dOH while they are staged -- same rows, same k-quads, same LDS image
     // as run_u -- and the column-tile-0 workgroup of a row tile stores them to dhp on the way (the weight gradients dUh / dGh
-    // still need it); the epilogue (EpiDgrad1GenF, gemm.hip) adds dzp and the per-row attention dot, so cell_bwd disappears:
+    // still need it); the epilogue (EpiDgrad1GenF, gemm_cell.hip) adds dzp and the per-row attention dot, so cell_bwd disappears:
     // 8 C floats per row instead of 11 cross HBM.  Three loads per slot instead of one: 48 instead of 16 operand VGPRs -- this
     // kernel runs two workgroups per CU.
     struct AGen {
@@ -1009,7 +1009,7 @@ struct SplitCore : FastCore<true, REGION> {
         __syncthreads();
     }
 
-    // 8-column-per-thread form of the half-tile epilogue (functors of gemm.hip's "8F" family): thread = (row tid >> 4 (+16 i),
+    // 8-column-per-thread form of the half-tile epilogue (functors of the "8F" family in gemm_fwd.hip / gemm_cell.hip): thread = (row tid >> 4 (+16 i),
     // columns 8 (tid & 15) .. +7) -- 16 bytes per access of a bf16 array, two float4 of an fp32 one.
     // straight-line body of the 8-column form (full tile + functor variant): row slots i = 0 .. 7, row (tid >> 4) + 16 i
     template <class F, int V>

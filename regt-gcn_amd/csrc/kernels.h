@@ -21,7 +21,7 @@ extern __device__ long g_wg_marks[8 * WG_TRACE_MAX];
 #define WG_MARK(i) do { } while (0)
 #endif
 
-// ---- buffer-descriptor addressing for the straight-line epilogues (gemm.hip functors) ----------------------------------
+// ---- buffer-descriptor addressing for the straight-line epilogues (functors of gemm_fwd.hip / gemm_cell.hip) ----------------------------------
 // One descriptor per array and tile (its base is the tile's origin, wave-uniform), a per-thread byte offset and a
 // wave-uniform scalar offset per row slot: no vector instruction is spent on addresses inside the row loops.
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -50,7 +50,7 @@ __device__ __forceinline__ void buf_st4_bf16(__amdgpu_buffer_rsrc_t r, int voff,
     __builtin_amdgcn_raw_buffer_store_b64(w, r, voff, soff, 0);
 }
 // GRU blend H' = Z h + (1 - Z) H~ (models/utils.py:186-188) with ONE fixed instruction sequence -- fma(Z, h, fl((1 - Z) H~)) --
-// wherever it is computed (candidate epilogues in gemm.hip, fused forward in fused.hip): left to -ffp-contract the two
+// wherever it is computed (candidate epilogues in gemm_cell.hip, fused forward in fused.hip): left to -ffp-contract the two
 // kernels could round differently, and tests/test_gpu_fused.py compares them bit for bit.
 __device__ __forceinline__ float gru_blend(float Z, float h, float ht) { return fmaf(Z, h, __fmul_rn(1.0f - Z, ht)); }
 // The element-wise steps of the cell's backward pass, likewise with one fixed instruction sequence each (cell_bwd8_kernel and the

@@ -1,6 +1,6 @@
 // STAEformer (models/STAEformer.py) inference: the kernels between the dense layers.  Activations are fp32 rows of D = model_dim
 // floats in the reference's own order, (B, T, N, D) contiguous: row (b T + t) N + n, M = B T N rows.  Nothing is transposed in
-// memory; the dense layers (FC_Q / FC_K / FC_V, out_proj, the two feed-forward linears) run on the GEMMs of gemm.hip and the
+// memory; the dense layers (FC_Q / FC_K / FC_V, out_proj, the two feed-forward linears) run on the GEMMs of gemm_fwd.hip and the
 // launch sequence is stae_forward in api_baselines.hip.
 //
 // stae_attention_kernel: softmax(Q K^T / sqrt(32)) V per (sequence, head), Q / K / V read where the projection GEMMs wrote them

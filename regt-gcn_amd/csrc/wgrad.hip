@@ -1,7 +1,7 @@
 // Weight gradients out[Nout x Nin] = P^T Q of the RegT-GCN cell (the transposes of models/utils.py:168-188 and of the regional embedding,
 // models/RegionalTemporalGCN.py:136-148) and the reduction of their row-chunk slabs: the fp32-MFMA kernels, the bf16-split kernels
 // and the register-ring kernel for operands stored as bf16 rows, with the row chunking every launch uses.
-// (Split out of gemm.hip in round 5; the forward / data-gradient GEMMs, the candidate kernels and the small GEMMs stay there.)
+// (The forward / data-gradient GEMMs, the candidate kernels and the small GEMMs: gemm_fwd.hip, gemm_cell.hip, gemm_small.hip.)
 #include "kernels.h"
 #include "gemm_fast.h"
 #include "gemm_split.h"

@@ -39,7 +39,7 @@ inputs of ``split_sensitive_inputs`` / ``wgrad_sensitive_inputs``, where any los
 
 The HIP kernels' own r per case is in profiles/op_bars.txt (tools/op_bars.py writes it).
 
-``expected_kernel`` restates the host-side dispatch of csrc/gemm.hip, wgrad.hip, spmm.hip and api_ops.hip; the GPU cases are labelled
+``expected_kernel`` restates the host-side dispatch of csrc/gemm_dispatch.hip, gemm_flat.h, wgrad.hip, spmm.hip and api_ops.hip; the GPU cases are labelled
 with its result and tests/test_op_bars_cpu.py asserts that the tables reach every kernel name of KERNELS.
 """
 from __future__ import annotations
@@ -462,19 +462,19 @@ def expected_kernel(op: str, mode: int, shape, options: Optional[Dict] = None) -
     o.update(options or {})
     if op == "linear":
         m, k, n = shape
-        # gemm.hip launch_gemm_bias_act: contiguous fp32 tensors, ldo = N; api_internal.h make_seg: SEG_VEC_A / _B need lda = ldb = K % 4 == 0
+        # gemm_fwd.hip launch_gemm_bias_act: contiguous fp32 tensors, ldo = N; api_internal.h make_seg: SEG_VEC_A / _B need lda = ldb = K % 4 == 0
         vec = n % 4 == 0
-        # gemm.hip fast_class: one BT segment, no region, no relu on A
+        # gemm_dispatch.hip fast_class: one BT segment, no region, no relu on A
         fast = vec and k % 4 == 0 and _cdiv(k, GBK) <= G_MAX_ITERS and k < (1 << 22)
         if not fast:
-            return f"gemm_flat_kernel<vec={int(vec)}>"              # gemm.hip launch_flat: fp32 in every arithmetic
+            return f"gemm_flat_kernel<vec={int(vec)}>"              # gemm_flat.h launch_flat: fp32 in every arithmetic
         tiles = _cdiv(m, GBM) * _cdiv(n, GBN)
-        # gemm.hip launch_fast
+        # gemm_flat.h launch_fast
         if mode == 0 and tiles < SMALL_TILE_LIMIT:
             return "gemm_flat_small_kernel"
         if mode == 0 and o["fp32_core_wide"]:
             return "gemm_flat_fast_kernel<FastCore>"
-        # gemm.hip uniform_ok: scalar slab descriptors need K % 32 == 0 (bf16 operands: at most 64 slabs)
+        # gemm_dispatch.hip uniform_ok: scalar slab descriptors need K % 32 == 0 (bf16 operands: at most 64 slabs)
         uniform = not o["desc_table"] and k % GBK == 0 and k * 4 * (GBM + 1) < (1 << 31) and not (mode == 2 and k // GBK > 64)
         return f"gemm_flat_split_kernel<{(0, 3, 1)[mode]}>/{'scalar' if uniform else 'table'}"
     if op == "wgrad":

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VGPR / SGPR / scratch of every kernel of one HIP source (compiles it to gfx950 assembly): tools/kernel_regs.py gemm.hip [filter]"""
+"""VGPR / SGPR / scratch of every kernel of one HIP source (compiles it to gfx950 assembly): tools/kernel_regs.py gemm_cell.hip [filter]"""
 import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "regt-gcn_amd", "csrc", sys.argv[1])

@@ -4,7 +4,7 @@
     REGT_LIB_DIR=$PWD/regt-gcn_amd/lib_trace REGT_HIPCC_FLAGS="-DREGT_WG_TRACE -DREGT_WG_TRACE_N=512" python regt-gcn_amd/build.py
     REGT_LIB_DIR=$PWD/regt-gcn_amd/lib_trace python tools/wg_trace.py [gemm mode 0|1|2] [N of the traced GEMM, default 512]
 
-The trace build makes every flat GEMM workgroup whose N matches record the 100 MHz wall clock at the start of its K loop,
+The trace build makes every flat GEMM workgroup of gemm_fwd.hip (bias/act, gates) whose N matches record the 100 MHz wall clock at the start of its K loop,
 at the end of it and after its epilogue, plus HW_ID/XCC_ID.  This script runs a few cfg-3 steps, reads the table of the LAST
 traced launch and prints, over all 256 CUs, the fraction of CU-time with 0 / 1 / >= 2 workgroups inside their K loop (the
 matrix pipe is only fed from there), the mean loop / epilogue / turn-around durations and one CU's timeline.
