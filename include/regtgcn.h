@@ -469,6 +469,21 @@ int32_t regt_gru_backward(const regt_gru_dims* dims, const float* x, const float
  *   >= 32 * heads; q, k, v, out 16-byte aligned.  Only the M x 32 * heads window of out is written.
  * regt_stae_add_layernorm: out = LayerNorm(residual + y) * gamma + beta over rows of D floats (biased variance, eps inside the
  *   root, as nn.LayerNorm); dense rows; out may alias residual.  D % 32 == 0, 32 <= D <= 256; 1 <= M < 2^31.
+ *
+ * Training of one self-attention layer (regtgcn_amd.nn.SelfAttentionLayer composes these with regt_linear / regt_wgrad /
+ * regt_relu_backward; the whole model still runs for inference only).  Additive entries, fp32, no float atomics, bit-reproducible.
+ * regt_stae_attention_train: regt_stae_attention that also stores lse (M x heads floats, row-major, 16-byte aligned): per (row,
+ *   head) the log-sum-exp of the scaled scores.  out is the same, bit for bit, as regt_stae_attention's.
+ * regt_stae_attention_backward: given out and dout (rows ldo apart) and lse of the training forward, writes dq, dk, dv, whose rows
+ *   lie one common ldg floats apart (three pointers, possibly the column windows of one M x 3 * 32 * heads buffer); only their
+ *   M x 32 * heads windows are written.  scratch: regt_stae_attention_backward_scratch_floats floats (0: arguments out of
+ *   range), 16-byte aligned.  Same limits as regt_stae_attention; ld, ldo, ldg multiples of 4, >= 32 * heads; every pointer 16-byte
+ *   aligned; batch * in_steps * num_nodes < 2^31 / 4.  No score matrix is formed in memory.
+ * regt_stae_add_layernorm_backward: for out = LayerNorm(residual + y) * gamma + beta (regt_stae_add_layernorm with out different
+ *   from residual) and dout = dL/dout: dz (M x D) = dL/dresidual = dL/dy, dgamma (D), dbeta (D).  The row statistics are recomputed
+ *   from residual and y; gamma may hold zeros.  dz must not alias an input.  scratch:
+ *   regt_stae_add_layernorm_backward_scratch_floats floats (0: arguments out of range).  D % 32 == 0, 32 <= D <= 256;
+ *   1 <= M < 2^31 / 4; eps > 0; every pointer 16-byte aligned.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t batch, in_steps, num_nodes, in_features, input_dim;
@@ -483,6 +498,17 @@ int32_t regt_stae_attention(const float* q, const float* k, const float* v, int6
                             int32_t num_nodes, int32_t heads, int32_t axis, float* out, int64_t ldo, regt_stream_t stream);
 int32_t regt_stae_add_layernorm(const float* residual, const float* y, const float* gamma, const float* beta, float eps, int64_t rows,
                                 int32_t width, float* out, regt_stream_t stream);
+int32_t regt_stae_attention_train(const float* q, const float* k, const float* v, int64_t ld, int32_t batch, int32_t in_steps,
+                                  int32_t num_nodes, int32_t heads, int32_t axis, float* out, int64_t ldo, float* lse,
+                                  regt_stream_t stream);
+size_t regt_stae_attention_backward_scratch_floats(int32_t batch, int32_t in_steps, int32_t num_nodes, int32_t heads);
+int32_t regt_stae_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* dout,
+                                     int64_t ldo, const float* lse, int32_t batch, int32_t in_steps, int32_t num_nodes, int32_t heads,
+                                     int32_t axis, float* dq, float* dk, float* dv, int64_t ldg, float* scratch, regt_stream_t stream);
+size_t regt_stae_add_layernorm_backward_scratch_floats(int64_t rows, int32_t width);
+int32_t regt_stae_add_layernorm_backward(const float* residual, const float* y, const float* gamma, const float* dout, float eps,
+                                         int64_t rows, int32_t width, float* dz, float* dgamma, float* dbeta, float* scratch,
+                                         regt_stream_t stream);
 
 /* relu's gradient in place: d[i] = 0 where y[i] <= 0, y the relu's output (the head of StackedGRU between two regt_linear calls).
  * 1 <= n < 2^31. */

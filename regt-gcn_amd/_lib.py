@@ -158,6 +158,13 @@ SIGNATURES = {
     "regt_stae_forward": (C.c_int32, [vp, vp, vp, vp, vp, vp]),
     "regt_stae_attention": (C.c_int32, [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp]),
     "regt_stae_add_layernorm": (C.c_int32, [vp, vp, vp, vp, C.c_float, C.c_int64, C.c_int32, vp, vp]),
+    "regt_stae_attention_train": (C.c_int32, [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64,
+                                              vp, vp]),
+    "regt_stae_attention_backward_scratch_floats": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "regt_stae_attention_backward": (C.c_int32, [vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int32, vp, vp, vp, C.c_int64, vp, vp]),
+    "regt_stae_add_layernorm_backward_scratch_floats": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "regt_stae_add_layernorm_backward": (C.c_int32, [vp, vp, vp, vp, C.c_float, C.c_int64, C.c_int32, vp, vp, vp, vp, vp]),
     "regt_relu_backward": (C.c_int32, [vp, vp, C.c_int64, vp]),
     "regt_mse_loss_grad": (C.c_int32, [vp, vp, vp, vp, C.c_int64, C.c_int64, vp]),
 }

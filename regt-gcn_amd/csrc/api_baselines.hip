@@ -1,4 +1,5 @@
-// Entry points of the baselines with their argument checks: SpatialGCN, STNorm, STID, StackedGRU, STAEformer (inference).
+// Entry points of the baselines with their argument checks: SpatialGCN, STNorm, STID, StackedGRU, STAEformer (inference, and the
+// op-site forward / backward entries of its trainable self-attention layer).
 #include "api_internal.h"
 
 using namespace regt;
@@ -310,6 +311,16 @@ int32_t regt_stae_forward(const regt_stae_dims* d, const float* x, const float* 
     return stae_forward(s, x, params, out, ws, (hipStream_t)st);
 }
 
+// the shape arguments every attention entry shares
+static int stae_attention_check(const char* what, int32_t B, int32_t T, int32_t N, int32_t heads, int32_t axis) {
+    REGT_CHECK_ARG(axis == 1 || axis == 2, "%s: axis must be 1 (temporal) or 2 (spatial), got %d", what, axis);
+    REGT_CHECK_ARG(B >= 1 && T >= 1 && N >= 1, "%s: batch, in_steps and num_nodes must be >= 1, got %d, %d, %d", what, B, T, N);
+    REGT_CHECK_ARG(heads >= 1 && heads * regt::STAE_HEAD_DIM <= regt::STAE_MAX_DIM, "%s: heads must be in [1, %d], got %d", what,
+                   regt::STAE_MAX_DIM / regt::STAE_HEAD_DIM, heads);
+    REGT_CHECK_ARG((long)B * T * N < (1L << 31) / 4, "%s: batch * in_steps * num_nodes is too large", what);
+    return REGT_OK;
+}
+
 int32_t regt_stae_attention(const float* q, const float* k, const float* v, int64_t ld, int32_t B, int32_t T, int32_t N, int32_t heads,
                             int32_t axis, float* out, int64_t ldo, regt_stream_t st) {
     REGT_CHECK_ARG(q && k && v && out, "regt_stae_attention: NULL pointer");
@@ -325,6 +336,37 @@ int32_t regt_stae_attention(const float* q, const float* k, const float* v, int6
     return regt::launch_stae_attention(q, k, v, (long)ld, B, T, N, heads, axis, out, (long)ldo, (hipStream_t)st);
 }
 
+int32_t regt_stae_attention_train(const float* q, const float* k, const float* v, int64_t ld, int32_t B, int32_t T, int32_t N, int32_t heads,
+                                  int32_t axis, float* out, int64_t ldo, float* lse, regt_stream_t st) {
+    REGT_CHECK_ARG(q && k && v && out && lse, "regt_stae_attention_train: NULL pointer");
+    if (int rc = stae_attention_check("regt_stae_attention_train", B, T, N, heads, axis)) return rc;
+    const long D = (long)heads * regt::STAE_HEAD_DIM;
+    REGT_CHECK_ARG(ld >= D && ldo >= D && ld % 4 == 0 && ldo % 4 == 0,
+                   "regt_stae_attention_train: ld and ldo must be multiples of 4, at least 32 * heads = %ld, got %ld, %ld", D, (long)ld, (long)ldo);
+    REGT_CHECK_ARG(al16(q) && al16(k) && al16(v) && al16(out) && al16(lse), "regt_stae_attention_train: q, k, v, out and lse must be 16-byte aligned");
+    return regt::launch_stae_attention(q, k, v, (long)ld, B, T, N, heads, axis, out, (long)ldo, (hipStream_t)st, lse);
+}
+
+size_t regt_stae_attention_backward_scratch_floats(int32_t B, int32_t T, int32_t N, int32_t heads) {
+    if (stae_attention_check("regt_stae_attention_backward_scratch_floats", B, T, N, heads, 1)) return 0;
+    return regt::stae_attention_bwd_scratch_floats((long)B * T * N, heads);
+}
+
+int32_t regt_stae_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* dout,
+                                     int64_t ldo, const float* lse, int32_t B, int32_t T, int32_t N, int32_t heads, int32_t axis, float* dq,
+                                     float* dk, float* dv, int64_t ldg, float* scratch, regt_stream_t st) {
+    REGT_CHECK_ARG(q && k && v && out && dout && lse && dq && dk && dv && scratch, "regt_stae_attention_backward: NULL pointer");
+    if (int rc = stae_attention_check("regt_stae_attention_backward", B, T, N, heads, axis)) return rc;
+    const long D = (long)heads * regt::STAE_HEAD_DIM;
+    REGT_CHECK_ARG(ld >= D && ldo >= D && ldg >= D && ld % 4 == 0 && ldo % 4 == 0 && ldg % 4 == 0,
+                   "regt_stae_attention_backward: ld, ldo and ldg must be multiples of 4, at least 32 * heads = %ld, got %ld, %ld, %ld", D, (long)ld,
+                   (long)ldo, (long)ldg);
+    REGT_CHECK_ARG(al16(q) && al16(k) && al16(v) && al16(out) && al16(dout) && al16(lse) && al16(dq) && al16(dk) && al16(dv) && al16(scratch),
+                   "regt_stae_attention_backward: every pointer must be 16-byte aligned");
+    return regt::launch_stae_attention_bwd(q, k, v, (long)ld, out, dout, (long)ldo, lse, B, T, N, heads, axis, dq, dk, dv, (long)ldg, scratch,
+                                           (hipStream_t)st);
+}
+
 int32_t regt_stae_add_layernorm(const float* residual, const float* y, const float* gamma, const float* beta, float eps, int64_t M, int32_t D,
                                 float* out, regt_stream_t st) {
     REGT_CHECK_ARG(residual && y && gamma && beta && out, "regt_stae_add_layernorm: NULL pointer");
@@ -333,6 +375,29 @@ int32_t regt_stae_add_layernorm(const float* residual, const float* y, const flo
     REGT_CHECK_ARG(M >= 1 && M < (1L << 31), "regt_stae_add_layernorm: M must be in [1, 2^31), got %ld", (long)M);
     REGT_CHECK_ARG(eps > 0.f, "regt_stae_add_layernorm: eps must be > 0, got %g", (double)eps);
     return regt::launch_stae_add_layernorm(residual, y, gamma, beta, eps, (long)M, D, out, (hipStream_t)st);
+}
+
+static int stae_ln_backward_check(const char* what, int64_t M, int32_t D) {
+    REGT_CHECK_ARG(D >= 32 && D % 32 == 0 && D <= regt::STAE_MAX_DIM, "%s: D must be a multiple of 32 in [32, %d], got %d", what,
+                   regt::STAE_MAX_DIM, D);
+    REGT_CHECK_ARG(M >= 1 && M < (1L << 31) / 4, "%s: M must be in [1, 2^31 / 4), got %ld", what, (long)M);
+    return REGT_OK;
+}
+
+size_t regt_stae_add_layernorm_backward_scratch_floats(int64_t M, int32_t D) {
+    if (stae_ln_backward_check("regt_stae_add_layernorm_backward_scratch_floats", M, D)) return 0;
+    return regt::stae_add_layernorm_bwd_scratch_floats((long)M, D);
+}
+
+int32_t regt_stae_add_layernorm_backward(const float* residual, const float* y, const float* gamma, const float* dout, float eps, int64_t M,
+                                         int32_t D, float* dz, float* dgamma, float* dbeta, float* scratch, regt_stream_t st) {
+    REGT_CHECK_ARG(residual && y && gamma && dout && dz && dgamma && dbeta && scratch, "regt_stae_add_layernorm_backward: NULL pointer");
+    if (int rc = stae_ln_backward_check("regt_stae_add_layernorm_backward", M, D)) return rc;
+    REGT_CHECK_ARG(eps > 0.f, "regt_stae_add_layernorm_backward: eps must be > 0, got %g", (double)eps);
+    REGT_CHECK_ARG(al16(residual) && al16(y) && al16(gamma) && al16(dout) && al16(dz) && al16(dgamma) && al16(dbeta) && al16(scratch),
+                   "regt_stae_add_layernorm_backward: every pointer must be 16-byte aligned");
+    REGT_CHECK_ARG(dz != residual && dz != y && dz != dout, "regt_stae_add_layernorm_backward: dz must not alias residual, y or dout");
+    return regt::launch_stae_add_layernorm_bwd(residual, y, gamma, dout, eps, (long)M, D, dz, dgamma, dbeta, scratch, (hipStream_t)st);
 }
 
 }  // extern "C"

@@ -387,7 +387,8 @@ int launch_relu_mask(const float* y, float* d, long n, hipStream_t st);      // 
 int launch_gru_bwd(const GruDims& s, const float* x, const float* w_hh, const float* dout, const float* dh_last, float* const* grads,
                    float* dh0, const float* ws, float* scratch, hipStream_t st);
 
-// STAEformer inference (staeformer.hip): the kernels between the dense layers; the launch sequence is stae_forward (api_baselines.hip).
+// STAEformer (staeformer.hip): the forward kernels between the dense layers; the inference launch sequence is stae_forward
+// (api_baselines.hip), the trainable layer (nn.SelfAttentionLayer) composes the op-site entry points in functional.py.
 // Parameter pointer table in state_dict order: node_emb, adaptive_embedding, input_proj w, b, tod_embedding, dow_embedding (NULL
 // where the width is 0), output_proj w, b, then STAE_LAYER_PARAMS per layer, temporal layers first (attn.FC_Q w, b, FC_K, FC_V,
 // out_proj, feed_forward.0 w, b, feed_forward.2 w, b, ln1 w, b, ln2 w, b).
@@ -399,11 +400,23 @@ struct StaeDims {
 constexpr int STAE_HEAD_DIM = 32, STAE_MAX_DIM = 256, STAE_MAX_FF = 1024, STAE_MAX_LAYERS = 8, STAE_MAX_OUT = 64, STAE_HEAD_PARAMS = 8,
               STAE_LAYER_PARAMS = 16;
 inline int stae_model_dim(const StaeDims& s) { return s.e_in + s.e_tod + s.e_dow + s.e_sp + s.e_adp; }
+// lse (M, heads), optional: the training forward also stores each (row, head)'s log-sum-exp of the scaled scores; out is the same bits
 int launch_stae_attention(const float* q, const float* k, const float* v, long ld, int B, int T, int N, int heads, int axis, float* out,
-                          long ldo, hipStream_t st);
+                          long ldo, hipStream_t st, float* lse = nullptr);
 int launch_stae_add_layernorm(const float* residual, const float* y, const float* gamma, const float* beta, float eps, long M, int D,
                               float* out, hipStream_t st);
 int launch_stae_embed(const StaeDims& s, const float* x, const float* const* P, float* out, hipStream_t st);
+// STAEformer training (staeformer_bwd.hip): the backward kernels between the dense layers, two launches each.
+// Attention: out / dout rows at ldo, dq / dk / dv rows at one common ldg (three windows of one buffer are fine), lse from the
+// training forward; scratch: stae_attention_bwd_scratch_floats floats (delta per (row, head), written by the query pass).
+size_t stae_attention_bwd_scratch_floats(long M, int heads);
+int launch_stae_attention_bwd(const float* q, const float* k, const float* v, long ld, const float* out, const float* dout, long ldo,
+                              const float* lse, int B, int T, int N, int heads, int axis, float* dq, float* dk, float* dv, long ldg,
+                              float* scratch, hipStream_t st);
+// Add+LayerNorm: dz (the gradient of residual and of y; no alias with an input), dgamma, dbeta; scratch: per-wave partial sums.
+size_t stae_add_layernorm_bwd_scratch_floats(long M, int D);
+int launch_stae_add_layernorm_bwd(const float* residual, const float* y, const float* gamma, const float* dout, float eps, long M, int D,
+                                  float* dz, float* dgamma, float* dbeta, float* scratch, hipStream_t st);
 int launch_stae_output_proj(const StaeDims& s, const float* x, const float* w, const float* bias, float* out, hipStream_t st);
 
 // ---- per-device launch state ------------------------------------------------------------------------------------

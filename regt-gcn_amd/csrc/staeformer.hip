@@ -14,10 +14,12 @@
 //   O^T = V^T P^T -- the key order of that contraction is the accumulator's own, V is read to match, nothing passes through LDS.
 //   Padding keys of a ragged last tile get the score -inf and their V is taken as 0 (never loaded); padding queries are computed
 //   on zeros and never stored.  Every tile holds at least one real key, so the running maximum is finite from the first tile on.
-//   Sums run in a fixed order: two runs give the same bits.
+//   Sums run in a fixed order: two runs give the same bits.  The SAVE_LSE instance is the training forward: the same out, plus
+//   each (row, head)'s m + log(l), from which staeformer_bwd.hip rebuilds the probabilities.
 //
 // stae_add_layernorm_kernel: out = LayerNorm(residual + y) gamma + beta over D (biased variance, as nn.LayerNorm), one wave per
-// row, the row held in registers (mean first, then the centred squares); out may alias residual.
+// row, the row held in registers (mean first, then the centred squares; ln_centre_row of stae_rows.h, which the backward kernel
+// calls too); out may alias residual.
 //
 // stae_embed_kernel: layer 0's input, columns in the reference's concatenation order (models/STAEformer.py:203-229):
 // input_proj(x[..., :input_dim]) | tod_embedding[(x[..., 1] steps_per_day).long()] | dow_embedding[x[..., 2].long()] | node_emb |
@@ -28,35 +30,24 @@
 // + bias; one wave per (b, n) reads the node's T pieces at stride N D.
 //
 // Limits (checked by regt_stae_* before any launch): head width 32; D % 32 == 0, D <= 256.
-#include "kernels.h"
+#include "stae_rows.h"
 
 namespace regt {
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int QT = 32;                    // queries per wave, keys per tile
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-// row of accumulator register i within the 32 x 32 result (the column is lane & 31)
-__device__ __forceinline__ int crow(int i, int lh) { return (i & 3) + 8 * (i >> 2) + 4 * lh; }
+using namespace stae;
 
 struct AttnArgs {
     const float *q, *k, *v;
-    float* out;
+    float *out, *lse;                     // lse: (M, H) row statistics m + log(l), written by the SAVE_LSE instance only
     long ld, ldo, nwork;
     int T, N, H, axis, L, qtiles;
 };
 
-// 16 consecutive floats at p (16-byte aligned) or zeros
-__device__ __forceinline__ void load16(float (&r)[16], const float* p, bool live) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float4 v = live ? reinterpret_cast<const float4*>(p)[j] : make_float4(0.f, 0.f, 0.f, 0.f);
-        r[4 * j] = v.x, r[4 * j + 1] = v.y, r[4 * j + 2] = v.z, r[4 * j + 3] = v.w;
-    }
-}
-
+// SAVE_LSE: the training forward.  Same arithmetic and the same out, bit for bit; each query's log-sum-exp of its scaled scores
+// is stored besides, which is all the backward needs to rebuild the probabilities.
+template <bool SAVE_LSE>
 __global__ __launch_bounds__(THREADS) void stae_attention_kernel(const AttnArgs a) {
     const int lane = threadIdx.x & 63, lr = lane & 31, lh = lane >> 5;
     const long w = (long)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
@@ -128,13 +119,9 @@ __global__ __launch_bounds__(THREADS) void stae_attention_kernel(const AttnArgs 
 #pragma unroll
         for (int g = 0; g < 4; ++g)
             *reinterpret_cast<float4*>(op + 8 * g) = make_float4(o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv);
+        if constexpr (SAVE_LSE)
+            if (lh == 0) a.lse[(row0 + (long)ql * rstep) * a.H + h] = m + logf(l);
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {          // every lane gets the same sum, in one fixed order
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 // residual and out may be the same array: a lane reads its own elements before it writes them
@@ -144,24 +131,8 @@ __global__ __launch_bounds__(THREADS) void stae_add_layernorm_kernel(const float
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
     if (row >= M) return;
-    const float *r = residual + row * D, *yr = y + row * D;
     float v[4];
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int d = lane + 64 * j;
-        v[j] = d < D ? r[d] + yr[d] : 0.f;
-        sum += v[j];
-    }
-    const float mean = wave_sum(sum) / (float)D;
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float c = lane + 64 * j < D ? v[j] - mean : 0.f;
-        v[j] = c;
-        sq += c * c;
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)D + eps);
+    const float rstd = ln_centre_row(residual + row * D, y + row * D, lane, D, eps, v);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int d = lane + 64 * j;
@@ -228,15 +199,19 @@ __global__ __launch_bounds__(THREADS) void stae_output_proj_kernel(const float* 
 
 }  // namespace
 
+// lse == nullptr: the inference instance
 int launch_stae_attention(const float* q, const float* k, const float* v, long ld, int B, int T, int N, int heads, int axis, float* out,
-                          long ldo, hipStream_t st) {
+                          long ldo, hipStream_t st, float* lse) {
     AttnArgs a{};
-    a.q = q, a.k = k, a.v = v, a.out = out, a.ld = ld, a.ldo = ldo;
+    a.q = q, a.k = k, a.v = v, a.out = out, a.lse = lse, a.ld = ld, a.ldo = ldo;
     a.T = T, a.N = N, a.H = heads, a.axis = axis, a.L = axis == 1 ? T : N, a.qtiles = cdiv(a.L, QT);
     a.nwork = (long)B * (axis == 1 ? N : T) * heads * a.qtiles;
     const long blocks = (a.nwork + THREADS / 64 - 1) / (THREADS / 64);
     REGT_CHECK_ARG(blocks < (1L << 31), "stae attention: %ld workgroups exceed the grid", blocks);
-    hipLaunchKernelGGL(stae_attention_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, a);
+    if (lse)
+        hipLaunchKernelGGL(stae_attention_kernel<true>, dim3((unsigned)blocks), dim3(THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL(stae_attention_kernel<false>, dim3((unsigned)blocks), dim3(THREADS), 0, st, a);
     REGT_CHECK_LAUNCH();
     return REGT_OK;
 }

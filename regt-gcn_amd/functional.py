@@ -798,6 +798,84 @@ class MLPHeadFunction(torch.autograd.Function):
         return (da,) + _deliver_grads((w1, b1, w2, b2), (dw1, db1, dw2, db2))
 
 
+class STAEAttentionFunction(torch.autograd.Function):
+    """(q, k, v (M, 32 heads) views with one row stride, batch, in_steps, num_nodes, heads, axis) -> softmax(Q K^T / sqrt(32)) V per
+    head along ``axis`` (regt_stae_attention_train / regt_stae_attention_backward).  When a gradient is wanted the forward keeps its
+    output and each (row, head)'s log-sum-exp; otherwise it is the inference kernel and nothing is saved.  dq, dk, dv come back as
+    the three column windows of one (M, 3 * 32 heads) buffer."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, batch, in_steps, num_nodes, heads, axis):
+        from . import ops
+        ctx.shape = (batch, in_steps, num_nodes, heads, axis)
+        if not any(ctx.needs_input_grad[:3]):
+            return ops.stae_attention(q, k, v, batch, in_steps, num_nodes, heads, axis)
+        out, lse = ops.stae_attention_train(q, k, v, batch, in_steps, num_nodes, heads, axis)
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import ops
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = ops.stae_attention_backward(q, k, v, out, dout.contiguous(), lse, *ctx.shape)
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None, None, None)
+
+
+class STAEPackedAttentionFunction(torch.autograd.Function):
+    """:class:`STAEAttentionFunction` on one (M, 3 * 32 heads) buffer Q|K|V, as a fused projection writes it: the gradient is the
+    backward's own (M, 3 * 32 heads) buffer, handed on whole (three separate window gradients would be re-assembled by autograd
+    with three zero-filled copies of it)."""
+
+    @staticmethod
+    def forward(ctx, qkv, batch, in_steps, num_nodes, heads, axis):
+        from . import ops
+        d = heads * ops.STAE_HEAD_DIM
+        q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
+        ctx.shape = (batch, in_steps, num_nodes, heads, axis)
+        if not ctx.needs_input_grad[0]:
+            return ops.stae_attention(q, k, v, batch, in_steps, num_nodes, heads, axis)
+        out, lse = ops.stae_attention_train(q, k, v, batch, in_steps, num_nodes, heads, axis)
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import ops
+        qkv, out, lse = ctx.saved_tensors
+        d = out.shape[1]
+        grads = torch.empty_like(qkv)
+        ops.stae_attention_backward(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], out, dout.contiguous(), lse, *ctx.shape, grads=grads)
+        return grads, None, None, None, None, None
+
+
+class STAEAddLayerNormFunction(torch.autograd.Function):
+    """(residual (M, D), y (M, D), gamma, beta, eps) -> LayerNorm(residual + y) gamma + beta (regt_stae_add_layernorm /
+    regt_stae_add_layernorm_backward).  The backward recomputes the row statistics from residual and y, which is all the forward
+    keeps; residual and y receive the same gradient.  Honours :func:`set_grad_accumulation_in_backward`."""
+
+    @staticmethod
+    def forward(ctx, residual, y, gamma, beta, eps):
+        from . import ops
+        out = ops.stae_add_layernorm(residual, y, gamma.detach(), beta.detach(), eps)
+        if any(ctx.needs_input_grad[:4]):
+            ctx.save_for_backward(residual, y)
+            ctx.leaf_params = (gamma, beta)
+            ctx.eps = eps
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import ops
+        residual, y = ctx.saved_tensors
+        gamma, beta = ctx.leaf_params
+        dz, dgamma, dbeta = ops.stae_add_layernorm_backward(residual, y, gamma.detach(), dout, ctx.eps)
+        need = ctx.needs_input_grad
+        return (dz if need[0] else None, dz if need[1] else None) + \
+            _deliver_grads((gamma if need[2] else None, beta if need[3] else None), (dgamma, dbeta)) + (None,)
+
+
 class ZeroGradAnchor(torch.autograd.Function):
     """Identity on ``(pred, hidden)`` that gives ``dead`` parameters an all-zero gradient: in the reference's GraphSAGE / GAT models
     the reset gate is computed and multiplied by the zero hidden state, so autograd hands its parameters zeros, not None --

@@ -13,6 +13,7 @@ unchanged:
 * :class:`STID`                 <-> models/STID.py:5-157
 * :class:`StackedGRU`           <-> models/StackedGRU.py:4-30
 * :class:`STAEformer`           <-> models/STAEformer.py:110-255 (inference only)
+* :class:`SelfAttentionLayer`   <-> models/STAEformer.py:76-107 (trainable)
 
 The modules only *hold* parameters; all arithmetic runs in libregtgcn_hip.so through
 :class:`regt-gcn_amd.functional.RegTGCNFunction`.  There is no CPU implementation here: calling
@@ -29,7 +30,8 @@ import torch.nn as nn
 from . import _lib
 from . import ops
 from .functional import (HEAD_HIDDEN, PARAM_NAMES_CELL, AggregateFunction, Cell0Function, CellFunction, GatAggregateFunction,
-                         GRUFunction, LinearFunction, MLPHeadFunction, RegTGCNFunction, SpatialEmbedFunction, STIDFunction, STNormFunction, ZeroGradAnchor, cell_run, param_names, regt_run)
+                         GRUFunction, LinearFunction, MLPHeadFunction, RegTGCNFunction, SpatialEmbedFunction, STAEAddLayerNormFunction,
+                         STAEPackedAttentionFunction, STIDFunction, STNormFunction, ZeroGradAnchor, cell_run, param_names, regt_run)
 from .graph import (AttentionPattern, GcnOperator, MeanOperator, PreparedGraph, fingerprint, prepare_attention_pattern,
                     prepare_cheb_operator, prepare_gcn_operator, prepare_graph, prepare_mean_operator)
 
@@ -993,3 +995,52 @@ class STAEformer(nn.Module):
         dims = self.dims(x.shape[0], x.shape[3])
         params = [None if p is None else p.detach() for p in self.param_table()]
         return ops.stae_forward(dims, x.contiguous(), params)
+
+
+class SelfAttentionLayer(_STAELayerParams):
+    """One self-attention layer of STAEformer (models/STAEformer.py:76-107), TRAINABLE, with the reference's constructor,
+    ``forward(x, dim=-2)`` and 16-entry state_dict (attn.FC_Q.weight ... attn.out_proj.bias, feed_forward.0.*, feed_forward.2.*,
+    ln1.*, ln2.*).  ``x`` is (B, T, N, model_dim) with attention along ``dim`` 1 / -3 (time) or 2 / -2 (nodes), or (B, L, model_dim)
+    with ``dim`` 1 / -2, taken as (B, 1, L, model_dim); nothing is transposed in memory, the kernels read a sequence through its row
+    stride.  ``x`` receives its gradient, so layers stack.
+
+    Launches: Q, K, V come from ONE projection GEMM over the concatenated weights (x is read once; its backward is one data-gradient
+    GEMM and one weight-gradient call for the three), then attention, out_proj, add+LayerNorm, the two feed-forward GEMMs and the
+    second add+LayerNorm.  All arithmetic runs in the HIP library; the ``nn.Linear`` / ``nn.LayerNorm`` modules only hold weights.
+
+    NotImplementedError: head width other than 32, model_dim > 256, a feed_forward_dim outside the dense entry points' use here,
+    ``mask=True`` (STAEformer never masks) and training mode with ``dropout > 0`` (keep-bit dropout comes with whole-model training)."""
+
+    def __init__(self, model_dim, feed_forward_dim=2048, num_heads=8, dropout=0, mask=False):
+        ops.stae_layer_limits(model_dim, num_heads, feed_forward_dim)
+        if mask:
+            raise NotImplementedError("SelfAttentionLayer runs without the causal mask only (mask=False): STAEformer never masks")
+        super().__init__(model_dim, feed_forward_dim)
+        self.model_dim, self.feed_forward_dim, self.num_heads, self.dropout, self.mask = model_dim, feed_forward_dim, num_heads, float(dropout), False
+
+    def forward(self, x: torch.Tensor, dim: int = -2) -> torch.Tensor:
+        if self.training and self.dropout > 0:                       # a property of the module: refused whatever the input is
+            raise NotImplementedError(f"SelfAttentionLayer in training mode runs with dropout=0 only, got dropout={self.dropout}: call "
+                                      "eval() or construct it with dropout=0")
+        _need_cuda(x)
+        if x.dtype != torch.float32:
+            raise _lib.RegtError(f"SelfAttentionLayer input must be float32, got {x.dtype}")
+        d = self.model_dim
+        if x.dim() == 4 and x.shape[-1] == d and dim in (1, 2, -3, -2):
+            b, t, n = x.shape[:3]
+            axis = 1 if dim in (1, -3) else 2
+        elif x.dim() == 3 and x.shape[-1] == d and dim in (1, -2):
+            b, t, n, axis = x.shape[0], 1, x.shape[1], 2
+        else:
+            raise ValueError(f"x must be (B, T, N, {d}) with dim in (1, 2, -3, -2) or (B, L, {d}) with dim in (1, -2), got "
+                             f"{tuple(x.shape)}, dim={dim}")
+        if b < 1 or t < 1 or n < 1:
+            raise ValueError(f"x must have no empty axis, got {tuple(x.shape)}")
+        p = self.table()
+        rows = x.contiguous().view(b * t * n, d)
+        qkv = LinearFunction.apply(rows, torch.cat([p[0], p[2], p[4]]), torch.cat([p[1], p[3], p[5]]))
+        a = STAEPackedAttentionFunction.apply(qkv, b, t, n, self.num_heads, axis)
+        y = LinearFunction.apply(a, p[6], p[7])
+        h = STAEAddLayerNormFunction.apply(rows, y, p[12], p[13], float(self.ln1.eps))
+        f = MLPHeadFunction.apply(h, p[8], p[9], p[10], p[11])
+        return STAEAddLayerNormFunction.apply(h, f, p[14], p[15], float(self.ln2.eps)).view(x.shape)

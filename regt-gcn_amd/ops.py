@@ -650,3 +650,87 @@ def stae_add_layernorm(residual: torch.Tensor, y: torch.Tensor, gamma: torch.Ten
     _lib.check(_lib.load().regt_stae_add_layernorm(_lib.ptr(residual), _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), eps, m, d,
                                                    _lib.ptr(out), _stream()), "regt_stae_add_layernorm")
     return out
+
+
+# ---- STAEformer training: the self-attention layer's backward (csrc/staeformer_bwd.hip) ------------------------------------------------
+
+def stae_layer_limits(model_dim: int, num_heads: int, feed_forward_dim: int):
+    """NotImplementedError naming the limit unless one self-attention layer is inside what the kernels and the dense entry points take."""
+    if num_heads < 1 or model_dim != num_heads * STAE_HEAD_DIM:
+        raise NotImplementedError(f"SelfAttentionLayer runs with head width model_dim / num_heads == {STAE_HEAD_DIM} only, got "
+                                  f"model_dim={model_dim}, num_heads={num_heads}")
+    if model_dim > STAE_MAX_DIM:
+        raise NotImplementedError(f"SelfAttentionLayer runs with model_dim <= {STAE_MAX_DIM}, got model_dim={model_dim}")
+    if feed_forward_dim < 32 or feed_forward_dim % 32 or feed_forward_dim > STAE_MAX_FF:
+        raise NotImplementedError(f"SelfAttentionLayer runs with feed_forward_dim a multiple of 32 in [32, {STAE_MAX_FF}] (what the dense "
+                                  f"entry points regt_linear / regt_wgrad are used with here), got feed_forward_dim={feed_forward_dim}")
+
+
+def stae_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, in_steps: int, num_nodes: int, heads: int, axis: int,
+                         out: Optional[torch.Tensor] = None):
+    """:func:`stae_attention` for training: (out, lse), lse (M, heads) the log-sum-exp of each (row, head)'s scaled scores.  ``out`` is
+    the same, bit for bit, as :func:`stae_attention`'s."""
+    m, d = batch * in_steps * num_nodes, heads * STAE_HEAD_DIM
+    ld = _stae_rows(q, "q", m, d)
+    if _stae_rows(k, "k", m, d) != ld or _stae_rows(v, "v", m, d) != ld:
+        raise ValueError("q, k and v must share one row stride")
+    if out is None:
+        out = torch.empty(m, d, dtype=torch.float32, device=q.device)
+    ldo = _stae_rows(out, "out", m, d)
+    lse = torch.empty(m, heads, dtype=torch.float32, device=q.device)
+    _lib.check(_lib.load().regt_stae_attention_train(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ld, batch, in_steps, num_nodes, heads, axis,
+                                                     _lib.ptr(out), ldo, _lib.ptr(lse), _stream()), "regt_stae_attention_train")
+    return out, lse
+
+
+def stae_attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor,
+                            batch: int, in_steps: int, num_nodes: int, heads: int, axis: int, grads: Optional[torch.Tensor] = None):
+    """(dq, dk, dv) of :func:`stae_attention_train` given dL/dout: the three (M, 32 * heads) column windows of one (M, 3 * 32 * heads)
+    buffer (``grads``: any 2-D float32 view with unit column stride at least that large, whose first 3 * 32 * heads columns are used;
+    allocated when None).  q, k, v share a row stride, out and dout share one."""
+    m, d = batch * in_steps * num_nodes, heads * STAE_HEAD_DIM
+    ld = _stae_rows(q, "q", m, d)
+    if _stae_rows(k, "k", m, d) != ld or _stae_rows(v, "v", m, d) != ld:
+        raise ValueError("q, k and v must share one row stride")
+    ldo = _stae_rows(out, "out", m, d)
+    if _stae_rows(dout, "dout", m, d) != ldo:
+        raise ValueError("out and dout must share one row stride")
+    if not lse.is_cuda or lse.dtype != torch.float32 or tuple(lse.shape) != (m, heads) or not lse.is_contiguous():
+        raise _lib.RegtError(f"lse must be a contiguous float32 CUDA ({m}, {heads}) tensor (no CPU path)")
+    if grads is None:
+        grads = torch.empty(m, 3 * d, dtype=torch.float32, device=q.device)
+    dq, dk, dv = grads[:, :d], grads[:, d:2 * d], grads[:, 2 * d:3 * d]
+    ldg = _stae_rows(dq, "dq", m, d)
+    if _stae_rows(dk, "dk", m, d) != ldg or _stae_rows(dv, "dv", m, d) != ldg:
+        raise ValueError("grads must hold three (M, 32 * heads) column windows")
+    lib = _lib.load()
+    n = lib.regt_stae_attention_backward_scratch_floats(batch, in_steps, num_nodes, heads)
+    if n == 0:
+        raise _lib.RegtError("regt_stae_attention_backward_scratch_floats: " + lib.regt_last_error().decode("utf-8", "replace"))
+    scratch = torch.empty(n, dtype=torch.float32, device=q.device)
+    _lib.check(lib.regt_stae_attention_backward(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), ld, _lib.ptr(out), _lib.ptr(dout), ldo, _lib.ptr(lse),
+                                                batch, in_steps, num_nodes, heads, axis, _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), ldg,
+                                                _lib.ptr(scratch), _stream()), "regt_stae_attention_backward")
+    return dq, dk, dv
+
+
+def stae_add_layernorm_backward(residual: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, dout: torch.Tensor, eps: float = STAE_LN_EPS):
+    """(dz, dgamma, dbeta) of ``LayerNorm(residual + y) * gamma + beta`` given dL/dout; dz (M, D) is the gradient of both residual and y.
+    The row statistics are recomputed from residual and y exactly as :func:`stae_add_layernorm` computes them."""
+    residual, y, gamma, dout = _f32c(residual, "residual"), _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(dout, "dout")
+    if residual.dim() != 2:
+        raise ValueError(f"residual must be (M, D), got {tuple(residual.shape)}")
+    m, d = residual.shape
+    if tuple(y.shape) != (m, d) or tuple(dout.shape) != (m, d) or tuple(gamma.shape) != (d,):
+        raise ValueError(f"y and dout must be ({m}, {d}) and gamma ({d},)")
+    lib = _lib.load()
+    n = lib.regt_stae_add_layernorm_backward_scratch_floats(m, d)
+    if n == 0:
+        raise _lib.RegtError("regt_stae_add_layernorm_backward_scratch_floats: " + lib.regt_last_error().decode("utf-8", "replace"))
+    scratch = torch.empty(n, dtype=torch.float32, device=residual.device)
+    dz = torch.empty_like(residual)
+    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+    _lib.check(lib.regt_stae_add_layernorm_backward(_lib.ptr(residual), _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(dout), eps, m, d, _lib.ptr(dz),
+                                                    _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(scratch), _stream()),
+               "regt_stae_add_layernorm_backward")
+    return dz, dgamma, dbeta
