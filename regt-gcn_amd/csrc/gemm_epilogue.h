@@ -100,12 +100,13 @@ __device__ __forceinline__ void buf_st8_bf16(__amdgpu_buffer_rsrc_t r, int voff,
     __builtin_amdgcn_raw_buffer_store_b128(pack_bf16x8(v), r, voff, 0, 0);
 }
 
-// the accumulators of a 128 x 128 tile, before the K loop
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
+// the accumulators of a tile (128 x 128: [2][2]; the weight gradients have other shapes, wgrad_common.h), before the K loop
+template <int MI, int NJ>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[MI][NJ]) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 }

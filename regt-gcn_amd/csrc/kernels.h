@@ -155,6 +155,20 @@ struct WgradArgs {
 };
 int launch_wgrad(const WgradArgs& a, hipStream_t st);
 long wgrad_slab_stride(const WgradArgs& a);
+// Which of the 17 GEMM kernels a weight gradient runs on, with what grid and dynamic LDS: decided by wgrad_pick (wgrad_dispatch.hip,
+// launches nothing, makes every refusal), launched by the unit that holds the kernel.
+enum WgradKernel : int {
+    WG_SKINNY32, WG_SKINNY32_PBF, WG_MID64, WG_WIDE128, WG_WIDE3, WG_GENERIC32, WG_GENERIC128,      // wgrad_fp32.hip
+    WG_SPLIT3, WG_SPLIT1, WG_SPLIT1_QBF, WG_SPLIT1_PBF, WG_SPLIT1_PBF_QBF,                          // wgrad_bf16.hip (WG_SPLIT1 + 2 p_bf16 + q_bf16)
+    WG_RING_4_2, WG_RING_6_2, WG_RING_8_2, WG_RING_2_4, WG_RING_4_4
+};
+static_assert(WG_SPLIT3 == WG_GENERIC128 + 1, "launch_wgrad: the kernels of wgrad_fp32.hip come first, then those of wgrad_bf16.hip");
+static_assert(WG_SPLIT1_QBF == WG_SPLIT1 + 1 && WG_SPLIT1_PBF == WG_SPLIT1 + 2 && WG_SPLIT1_PBF_QBF == WG_SPLIT1 + 3,
+              "wgrad_pick: WG_SPLIT1 + 2 p_bf16 + q_bf16");
+struct WgradPick { WgradKernel kernel; long blocks; size_t lds; bool raise_lds; };      // raise_lds: the kernel's dynamic-LDS limit is asked for
+int wgrad_pick(const WgradArgs& a, WgradPick* p);
+int launch_wgrad_fp32(const WgradPick& p, const WgradArgs& a, hipStream_t st);
+int launch_wgrad_bf16(const WgradPick& p, const WgradArgs& a, hipStream_t st);
 
 struct WgradReduceArgs {
     const float* slab; int nchunks; long slab_stride;

@@ -39,7 +39,7 @@ inputs of ``split_sensitive_inputs`` / ``wgrad_sensitive_inputs``, where any los
 
 The HIP kernels' own r per case is in profiles/op_bars.txt (tools/op_bars.py writes it).
 
-``expected_kernel`` restates the host-side dispatch of csrc/gemm_dispatch.hip, gemm_flat.h, wgrad.hip, spmm.hip and api_ops.hip; the GPU cases are labelled
+``expected_kernel`` restates the host-side dispatch of csrc/gemm_dispatch.hip, gemm_flat.h, wgrad_dispatch.hip, spmm.hip and api_ops.hip; the GPU cases are labelled
 with its result and tests/test_op_bars_cpu.py asserts that the tables reach every kernel name of KERNELS.
 """
 from __future__ import annotations
@@ -240,7 +240,7 @@ def wgrad_chunks(m: int) -> Tuple[int, int]:
 
 
 def reduce_slabs(slabs) -> torch.Tensor:
-    """wgrad.hip wgrad_reduce_body: eight partial sums over every eighth chunk, then ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7))."""
+    """wgrad_reduce.hip wgrad_reduce_body: eight partial sums over every eighth chunk, then ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7))."""
     part = []
     for s in range(8):
         acc = torch.zeros_like(slabs[0])
@@ -481,7 +481,7 @@ def expected_kernel(op: str, mode: int, shape, options: Optional[Dict] = None) -
         m, nout, nin = shape
         # api_ops.hip wgrad_chunks + api_step.hip wgrad_full: one right-hand side, fp32 rows, ldp = Nout, ldq = Nin
         kc, nc = wgrad_chunks(m)
-        # wgrad.hip launch_wgrad_impl
+        # wgrad_dispatch.hip wgrad_pick
         wide = nin > 32
         fast = nout % 4 == 0 and nin % 4 == 0 and kc <= 65536
         if wide and fast:
@@ -493,7 +493,7 @@ def expected_kernel(op: str, mode: int, shape, options: Optional[Dict] = None) -
             name = "wgrad_kernel<32>"
         else:
             name = "wgrad_kernel_generic<32>"
-        # wgrad.hip wgrad_reduce_vec_ok: slab stride = Nout * Nin (+ Nout with a bias gradient), ldo = Nin
+        # wgrad_reduce.hip wgrad_reduce_vec_ok: slab stride = Nout * Nin (+ Nout with a bias gradient), ldo = Nin
         stride = nout * nin + (nout if o["with_bias"] else 0)
         v4 = nin % 4 == 0 and stride % 4 == 0
         return f"{name} + wgrad_reduce_kernel/{'v4' if v4 else 'scalar'} x{nc}"

@@ -1,5 +1,5 @@
 """The native library's launch state is keyed by device (kernels.h want_dynamic_lds / device_cus, the per-device graph stream of
-api_runtime.hip).  Without a GPU: the workspace sizes, which go through the one chunk calculator of wgrad.hip, are pinned to
+api_runtime.hip).  Without a GPU: the workspace sizes, which go through the one chunk calculator of wgrad_dispatch.hip, are pinned to
 recorded numbers.  With two GPUs: one process drives both and gets the same bits from each."""
 import ctypes as C
 import os

@@ -18,7 +18,7 @@ typedef unsigned int u32;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
-__device__ __forceinline__ int swz(int m) { return ((m & 3) << 2) | ((m >> 2) & 3); }      // ws_off's chunk permutation (wgrad.hip)
+__device__ __forceinline__ int swz(int m) { return ((m & 3) << 2) | ((m >> 2) & 3); }      // ws_off's chunk permutation (wgrad_bf16.hip)
 
 template <int S>
 __global__ __launch_bounds__(256) void stream_kernel(const uint4* __restrict__ x, unsigned long long* __restrict__ sums, long rows, int chunk_rows,
