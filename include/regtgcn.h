@@ -118,6 +118,14 @@ int32_t regt_linear(const float* A, int64_t lda, int64_t M, int32_t K, const flo
 size_t regt_wgrad_slab_floats(int64_t M, int32_t N, int32_t K, int32_t with_bias);
 int32_t regt_wgrad(const float* dOut, int64_t ldd, const float* A, int64_t lda, int64_t M, int32_t N, int32_t K,
                    float* dW, int64_t ldw, float* dbias, float* slab, regt_stream_t stream);
+/* Diagnostic entry (kernel tests and A/B timings; no model path calls it): the row-chunk slabs of a weight gradient before their
+ * reduction.  For each of the `nchunks` chunks of `kchunk` rows (the last may be shorter) slab[c] = P[chunk c]^T Q, (Nout x Nin)
+ * floats, followed by the Nout column sums of P[chunk c] when colsum != 0.  The kernel is the one the library chooses for these
+ * arguments under the current arithmetic and switches; any_rows != 0 lifts only the row-count gate of the wave-owned fp32 kernel
+ * (Nin == 256, Nout % 256 == 0), so that it can be run on chunks of a few slabs.  *kernel (may be NULL) receives the name of the
+ * kernel that ran (a static string). */
+int32_t regt_wgrad_slabs(const float* P, int64_t ldp, int32_t Nout, const float* Q, int64_t ldq, int32_t Nin, int64_t M, int32_t kchunk,
+                         int32_t nchunks, int32_t colsum, float* slab, int32_t any_rows, const char** kernel, regt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Whole-model forward / backward.
@@ -544,7 +552,9 @@ int32_t regt_set_gemm_mode(int32_t mode);
  *   "wgrad_pairs" (0 | 1 | 2, anything else = 2; default 2 = on with the ring kernel): the two gradients of each left operand as one
  *     launch.
  *   "wgrad_wave" (0 | 1, default 1): row chunks of those launches sized so that all their workgroups are resident at once (another
- *     summation order over chunk boundaries than 0, the fixed ~128 chunks).
+ *     summation order over chunk boundaries than 0, the fixed ~128 chunks).  Under the fp32 arithmetic it also selects the
+ *     wave-owned kernel (one workgroup per CU, one row chunk per CU) for the 256-column weight gradients of large problems; 0 keeps
+ *     the three-workgroup kernel and its chunks.
  *   "wgrad_bnw64" (0 | 1, default 1): fp32 rows, a 33..64-wide right-hand side ([x | L~ x] at F = 32) as one 64-column tile instead
  *     of two of 32 (bit-identical).
  * The first two also exist per call: regt_dims.flags.  Environment only, read at first use: REGT_GEMM_MODE (above), REGT_FP32_CORE=wide,

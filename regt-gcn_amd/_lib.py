@@ -124,6 +124,8 @@ SIGNATURES = {
                                 C.c_float, vp, C.c_int64, vp]),
     "regt_wgrad_slab_floats": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "regt_wgrad": (C.c_int32, [vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, vp, vp, vp]),
+    "regt_wgrad_slabs": (C.c_int32, [vp, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32,
+                                     C.POINTER(C.c_char_p), vp]),
     "regt_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.c_int32, C.c_int32]),
     "regt_forward_only_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.POINTER(Graph)]),
     "regt_forward_only_packed_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.POINTER(Graph), C.c_int32, C.c_int32]),

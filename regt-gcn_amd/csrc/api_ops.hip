@@ -85,6 +85,17 @@ int32_t regt_wgrad(const float* dOut, int64_t ldd, const float* A, int64_t lda, 
     return rq.flush();
 }
 
+int32_t regt_wgrad_slabs(const float* P, int64_t ldp, int32_t Nout, const float* Q, int64_t ldq, int32_t Nin, int64_t M, int32_t kchunk,
+                         int32_t nchunks, int32_t colsum, float* slab, int32_t any_rows, const char** kernel, regt_stream_t st) {
+    REGT_CHECK_ARG(P && Q && slab && M > 0 && Nout > 0 && Nin > 0 && kchunk > 0 && nchunks > 0, "regt_wgrad_slabs: bad argument");
+    REGT_CHECK_ARG((long)kchunk * nchunks >= M && (long)kchunk * (nchunks - 1) < M, "regt_wgrad_slabs: the chunks must tile the M rows");
+    WgradArgs a{P, ldp, Nout, Q, ldq, Nin, 0, M, kchunk, nullptr, nchunks, slab, colsum ? 1 : 0};
+    WgradKernel ran = WG_GENERIC32;
+    TRY(launch_wgrad_slabs(a, (hipStream_t)st, any_rows != 0, &ran));
+    if (kernel) *kernel = wgrad_kernel_name(ran);
+    return REGT_OK;
+}
+
 int32_t regt_pack_x_bf16(const float* x, void* xp, int32_t N, int32_t F, int32_t T, regt_stream_t st) {
     REGT_CHECK_ARG(x && xp && N > 0 && F > 0 && T > 0, "regt_pack_x_bf16: bad argument");
     return launch_pack_x_bf16(x, xp, N, F, T, (hipStream_t)st);

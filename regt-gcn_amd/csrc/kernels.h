@@ -112,6 +112,11 @@ bool gemm_dgrad1_gen_ok(long M, int C, int num_nodes);
 bool wgrad_ring_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks);
 bool wgrad_skinny_chunking(int Nout, long M, int* kchunk, int* nchunks);            // skinny (Nin <= 32) fp32-MFMA kernel
 bool wgrad_wide_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks);   // wide fp32 / bf16x3 kernels (experiment)
+// wave-owned fp32 kernel (wgrad_wave_kernel): whether a gradient has its shape under the current switches, its chunks (one per CU;
+// wgrad_wide_chunking returns them where they apply), and the smallest M it is chosen for
+bool wgrad_wave_shape(int Nout, int Nin);
+bool wgrad_wave_chunking(int Nout, long M, int* kchunk, int* nchunks);
+long wgrad_wave_min_rows();
 long wgrad_chunk_bound(int Nout, int Nin, long M);   // upper bound of what the three can return (slab sizing, api_layout.hip make_layout)
 bool wgrad_ring_active();             // the ring kernel takes the bf16-stored weight gradients (pairs pay off with it)
 int launch_gemm_dgrad1_gen(const GemmSegs& S, long M, int N, const EpiDgrad1& e, hipStream_t st);
@@ -155,18 +160,20 @@ struct WgradArgs {
 };
 int launch_wgrad(const WgradArgs& a, hipStream_t st);
 long wgrad_slab_stride(const WgradArgs& a);
-// Which of the 17 GEMM kernels a weight gradient runs on, with what grid and dynamic LDS: decided by wgrad_pick (wgrad_dispatch.hip,
+// Which of the 18 GEMM kernels a weight gradient runs on, with what grid and dynamic LDS: decided by wgrad_pick (wgrad_dispatch.hip,
 // launches nothing, makes every refusal), launched by the unit that holds the kernel.
 enum WgradKernel : int {
-    WG_SKINNY32, WG_SKINNY32_PBF, WG_MID64, WG_WIDE128, WG_WIDE3, WG_GENERIC32, WG_GENERIC128,      // wgrad_fp32.hip
+    WG_SKINNY32, WG_SKINNY32_PBF, WG_MID64, WG_WIDE128, WG_WIDE3, WG_GENERIC32, WG_GENERIC128, WG_WAVE,      // wgrad_fp32.hip
     WG_SPLIT3, WG_SPLIT1, WG_SPLIT1_QBF, WG_SPLIT1_PBF, WG_SPLIT1_PBF_QBF,                          // wgrad_bf16.hip (WG_SPLIT1 + 2 p_bf16 + q_bf16)
     WG_RING_4_2, WG_RING_6_2, WG_RING_8_2, WG_RING_2_4, WG_RING_4_4
 };
-static_assert(WG_SPLIT3 == WG_GENERIC128 + 1, "launch_wgrad: the kernels of wgrad_fp32.hip come first, then those of wgrad_bf16.hip");
+static_assert(WG_SPLIT3 == WG_WAVE + 1, "launch_wgrad: the kernels of wgrad_fp32.hip come first, then those of wgrad_bf16.hip");
 static_assert(WG_SPLIT1_QBF == WG_SPLIT1 + 1 && WG_SPLIT1_PBF == WG_SPLIT1 + 2 && WG_SPLIT1_PBF_QBF == WG_SPLIT1 + 3,
               "wgrad_pick: WG_SPLIT1 + 2 p_bf16 + q_bf16");
 struct WgradPick { WgradKernel kernel; long blocks; size_t lds; bool raise_lds; };      // raise_lds: the kernel's dynamic-LDS limit is asked for
 int wgrad_pick(const WgradArgs& a, WgradPick* p);
+int launch_wgrad_slabs(const WgradArgs& a, hipStream_t st, bool any_rows, WgradKernel* ran);     // launch_wgrad, optionally below WG_WAVE's row gate; *ran = the kernel
+const char* wgrad_kernel_name(WgradKernel k);
 int launch_wgrad_fp32(const WgradPick& p, const WgradArgs& a, hipStream_t st);
 int launch_wgrad_bf16(const WgradPick& p, const WgradArgs& a, hipStream_t st);
 

@@ -31,15 +31,36 @@ static bool wave_chunks(long nch, long M, long min_rows, int* kchunk, int* nchun
 // together they do, started as slots free up (1.5 waves of workgroups at 128 chunks x 6 tiles) they do not, and the half-filled
 // last wave costs as much as a full one.  Fewer, longer chunks also mean fewer slabs to write and reduce.
 // regt_set_option("wgrad_wave", 0): the layout's ~128 chunks.  false: not applicable, keep the caller's chunking.
+// (The same switch, under the fp32 arithmetic, turns the wave-owned kernel and its one-chunk-per-CU sizing off -- wgrad_wave_shape
+// below: in both arithmetics it means "chunks sized to one wave of resident workgroups", and no launch is reached by both meanings.)
 // The same for the wide fp32 / bf16x3 kernels (wgrad3_kernel: three workgroups per CU; wgrad_split_kernel<3>: two): chunks x
 // (128 x 128 tiles) = one full wave of workgroups instead of ~128 chunks (768 instead of 1024 / 512 workgroups for dUzr / dUh at
 // C = 256).  These kernels are MFMA-bound, so it buys little: -0.05 ms of 4.0 at cfg-3, -0.01 ms at the W = 8 shard shape
 // (profiles/r04_wgrad_wave32_ab.txt; two waves mean more slabs to reduce: slower).
 bool wgrad_wide_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks) {
     if (gemm_mode() == 2 || fp32_core_wide() || Nin <= 32) return false;
+    if (wgrad_wave_shape(Nout, Nin) && wgrad_wave_chunking(Nout, M, kchunk, nchunks)) return true;
     const int per_cu = gemm_mode() == 1 ? 2 : 3;
     const long tpc = (long)cdiv(Nout, 128) * cdiv(Nin, 128);
     return wave_chunks((long)device_cus() * per_cu / tpc, M, 512, kchunk, nchunks);
+}
+// The wave-owned kernel (wgrad_wave_kernel: ONE workgroup per CU, each computing a whole 256 x 256 output tile of its row chunk): one
+// row chunk per CU, so Nout = 256 is one full wave of workgroups and Nout = 512 two (the two tiles of a chunk run side by side on one
+// XCD and share Q through its L2).  Chunks shorter than WG_WAVE_MIN_ROWS are refused: the kernel's prologue (two slabs in flight
+// before the first MFMA), its 256 KB slab store per workgroup and the reduction of one slab per CU are paid per chunk whatever its
+// length, while wgrad3_kernel's chunking writes and reduces 192 / 96 slabs instead of 256.  The gate is 128 slabs per chunk: the whole
+// step is measured at cfg-3's 147 slabs; the kernel alone also wins at 128 and at 64 slabs (138 / 142 and 135 / 141 against 124 / 127
+// and 120 / 130 TFLOP/s, profiles/wgrad_wave_ab.txt), but there the added slabs' reduction is not in the figure -- smaller problems
+// keep wgrad3_kernel.
+// regt_set_option("wgrad_wave", 0): wgrad3_kernel and its chunking.
+constexpr long WG_WAVE_MIN_ROWS = 128 * W_BK;
+bool wgrad_wave_shape(int Nout, int Nin) { return gemm_mode() == 0 && !fp32_core_wide() && option(OPT_WGRAD_WAVE) && Nin == 256 && Nout > 0 && Nout % 256 == 0; }
+// The smallest row count the wave-owned kernel is chosen for: every CU gets a chunk of WG_WAVE_MIN_ROWS rows.  (From there on the
+// chunker's rounding of a chunk to whole slabs leaves at most one CU in 64 without a chunk.)
+long wgrad_wave_min_rows() { return (long)device_cus() * WG_WAVE_MIN_ROWS; }
+bool wgrad_wave_chunking(int Nout, long M, int* kchunk, int* nchunks) {
+    (void)Nout;                                    // (every 256-row tile of a chunk is a workgroup of its own: the count does not depend on it)
+    return M >= wgrad_wave_min_rows() && wave_chunks(device_cus(), M, WG_WAVE_MIN_ROWS, kchunk, nchunks);
 }
 // Skinny gradients (Nin <= 32: wgrad_kernel<32>, HBM-bound on their left operand): chunks x row tiles = two
 // workgroups per CU, all resident at once -- at cfg-3 the layout's 507 chunks are 1.3 (dGh) / 2.6 (dGzr) waves of workgroups.
@@ -60,6 +81,10 @@ bool wgrad_ring_chunking(int Nout, int Nin, long M, int* kchunk, int* nchunks) {
 // budgets, with no chunk refused (32 rows is what the rounding gives any M > 0).
 long wgrad_chunk_bound(int Nout, int Nin, long M) {
     const long cus = device_cus();
+    // (The wave-owned fp32 kernel's one chunk per CU has no candidate here: the workspace stays what it was.  make_layout asks with
+    // Nin = C + F, and the regions it sizes for dUh and dUzr together hold the 256 slabs of either launch -- the largest, dUzr's,
+    // is 512 x (C C + C) floats against 512 x (C (C + F) + C) reserved, tests/test_wgrad_choice_wave.py.  The slab regions are one
+    // pool: when both launches' slabs do not fit beside the rest, ReduceQueue reduces what is queued first.)
     const long cand[3] = {cus * 3 / ((long)cdiv(Nout, 128) * cdiv(Nin, 128)),      // wide fp32 / bf16x3, ring (128-row tiles)
                           cus * 2 / cdiv(Nout, 128),                               // skinny
                           cus * 3 / ((long)cdiv(Nout, 256) * cdiv(Nin, 128))};     // ring (256-row tiles)
@@ -76,17 +101,34 @@ long wgrad_slab_stride(const WgradArgs& a) { return (long)a.Nout * a.Nin + (a.co
 // the tiles of a chunk share P (and Q between row tiles) through their XCD's L2 and only find each other's lines there while they walk
 // the chunk in step -- with less work the other tiles run ahead and every tile reads its operands from HBM (measured on the bf16
 // ring kernel: 0.90 / 0.51 ms against 0.71 / 0.45 ms for the two paired gradients of the cfg-5 shard).
-int launch_wgrad(const WgradArgs& a, hipStream_t st) {
+static int pick_kernel(const WgradArgs& a, WgradPick* p, bool any_rows);
+static int launch_picked(const WgradArgs& a, hipStream_t st, bool any_rows, WgradKernel* ran) {
     WgradArgs am = a;
     am.all_csum = a.colsum && a.p_bf16 && a.q_bf16;     // (fp32 kernels: measured no gain, +0.02 ms on the MFMA-bound wgrad3_kernel)
     WgradPick p;
-    if (int rc = wgrad_pick(am, &p)) return rc;
+    if (int rc = pick_kernel(am, &p, any_rows)) return rc;
+    if (ran) *ran = p.kernel;
     if (int rc = p.kernel < WG_SPLIT3 ? launch_wgrad_fp32(p, am, st) : launch_wgrad_bf16(p, am, st)) return rc;
     REGT_CHECK_LAUNCH();
     return REGT_OK;
 }
+int launch_wgrad(const WgradArgs& a, hipStream_t st) { return launch_picked(a, st, false, nullptr); }
+// The same launch for regt_wgrad_slabs: any_rows lifts the row gate of the wave-owned kernel (the kernel on chunks of a few slabs);
+// *ran: the choice
+int launch_wgrad_slabs(const WgradArgs& a, hipStream_t st, bool any_rows, WgradKernel* ran) { return launch_picked(a, st, any_rows, ran); }
+const char* wgrad_kernel_name(WgradKernel k) {
+    static const char* const names[] = {"wgrad_kernel<32>", "wgrad_kernel<32, bf16 P>", "wgrad_kernel<64>", "wgrad_kernel<128>", "wgrad3_kernel",
+                                        "wgrad_kernel_generic<32>", "wgrad_kernel_generic<128>", "wgrad_wave_kernel", "wgrad_split_kernel<3>",
+                                        "wgrad_split_kernel<1>", "wgrad_split_kernel<1, bf16 Q>", "wgrad_split_kernel<1, bf16 P>",
+                                        "wgrad_split_kernel<1, bf16 P, bf16 Q>", "wgrad_bf16_ring_kernel<4, 2>", "wgrad_bf16_ring_kernel<6, 2>",
+                                        "wgrad_bf16_ring_kernel<8, 2>", "wgrad_bf16_ring_kernel<2, 4>", "wgrad_bf16_ring_kernel<4, 4>"};
+    static_assert(sizeof(names) / sizeof(names[0]) == WG_RING_4_4 + 1, "one name per WgradKernel, in its order");
+    return names[k];
+}
 // The kernel of a weight gradient, its grid and its dynamic LDS; launches nothing and makes every refusal.
-int wgrad_pick(const WgradArgs& a, WgradPick* p) {
+int wgrad_pick(const WgradArgs& a, WgradPick* p) { return pick_kernel(a, p, false); }
+// any_rows: the wave-owned kernel is not held to its row gate (every CU a chunk of WG_WAVE_MIN_ROWS rows); every other condition stays
+static int pick_kernel(const WgradArgs& a, WgradPick* p, bool any_rows) {
     const auto pick = [p](WgradKernel k, long nblocks, size_t bytes, bool raise_lds) { *p = WgradPick{k, nblocks, bytes, raise_lds}; return REGT_OK; };
     // a ring-kernel instantiation: `bytes` of dynamic LDS, raised past the 48 KB any kernel may ask for
     const auto ring_pick = [&](WgradKernel k, long nblocks, size_t bytes) { return pick(k, nblocks, bytes, bytes > 48 * 1024); };
@@ -135,6 +177,15 @@ int wgrad_pick(const WgradArgs& a, WgradPick* p) {
         }
         if (fast && !fp32_core_wide()) {
             REGT_CHECK_ARG(!(a.p_bf16 || a.q_bf16), "wgrad: bf16-stored operands with the fp32 kernel");
+            // one wave per SIMD owning a 128 x 128 block: 256-column right-hand sides, whole 256-row output tiles, and enough rows that
+            // every CU has a chunk of WG_WAVE_MIN_ROWS, in chunks as wgrad_wave_chunking sizes them (workgroups for 7 of 8 CUs at
+            // least, no chunk count that leaves the chunks short).  Its scalar row offsets run up to 28 rows into the second slab past
+            // a chunk's last, ragged one: (chunk rows + 96) x row bytes must stay below 2^31.
+            const long rows_max = a.chunk_tab ? a.M : (long)a.kchunk;
+            const bool wave_rows = a.M >= wgrad_wave_min_rows() && 8L * a.nchunks * (a.Nout / 256) >= 7L * device_cus() &&
+                                   2 * a.M >= (long)a.nchunks * WG_WAVE_MIN_ROWS;
+            if (wgrad_wave_shape(a.Nout, a.Nin) && !a.q_relu && (any_rows || wave_rows) && 4 * (rows_max + 96) * std::max(a.ldp, a.ldq) < (1L << 31))
+                return pick(WG_WAVE, (long)(a.Nout / 256) * a.nchunks, 2 * 2 * W_BK * (256 + 4) * 4, true);
             return pick(WG_WIDE3, blocks, 4 * 16 * 132 * 4, false);
         }
         if (fast) {

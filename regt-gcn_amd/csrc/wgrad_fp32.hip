@@ -390,6 +390,142 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(WgradArgs a) {
     if (store_colsum && i0 + tid < a.Nout) out[(long)a.Nout * a.Nin + i0 + tid] = csum2[0] + csum2[1];
 }
 
+// fp32 weight gradients on ONE workgroup per CU, each wave owning a 128 x 128 block (Nin == 256, Nout % 256 == 0: wgrad_pick).
+// A loop of v_mfma_f32_32x32x2_f32 holds 154 TFLOP/s with one wave per SIMD and ~100 with two (DESIGN_HISTORY section D): here a
+// SIMD's one wave holds 4 x 4 MFMA tiles (256 accumulator registers), so a k step of 2 is 16 MFMAs against 4 + 4 fragment values --
+// a quarter of the LDS and global traffic per MFMA of the 2 x 2 kernels above -- and no other wave competes for the matrix pipe.
+// Two LDS stages of a 32-row slab of both operands (32 x 260 floats each, k-major as in HBM: 133,120 B); while slab t is multiplied
+// the registers holding slab t + 1 go to the other stage and slab t + 2 is requested, one 16-byte store and one 16-byte load per
+// operand slot between the MFMAs of a k step; one barrier per slab (16 k steps = 256 MFMAs per wave).
+// Same chunking, arithmetic order inside a chunk (k ascending, the same pairing of k to MFMA lanes), column sums and slab layout as
+// wgrad3_kernel / wgrad_kernel<128, false>: on the same row chunks the slabs agree bit for bit.
+template <bool CSUM>      // CSUM: also the column sums of P (a template argument: a branch per k step would cut the schedule of the K loop)
+__global__ __launch_bounds__(256, 1) void wgrad_wave_kernel(WgradArgs a) {
+    constexpr int LDT = 256 + 4, OP_T = W_BK * LDT, STAGE = 2 * OP_T;      // floats (4 LDT = 16 mod 64 banks, as W_LDP)
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int lr = lane & 31, lh = lane >> 5;
+    const int wr = wid >> 1, wc = wid & 1;
+    const int tpc = a.Nout / 256;                                          // 256-row output tiles; one 256-column tile
+    const WgradBlock blk = wgrad_block(a.nchunks, tpc);
+    const int i0 = blk.tile * 256, chunk = blk.chunk;
+    const WgradRows rows = wgrad_chunk_rows(a, chunk);
+    const long r0 = rows.r0, r1 = rows.r1;
+    const int nrows = (int)(r1 - r0);
+    const int ldp = (int)a.ldp, ldq = (int)a.ldq;
+    const long pbytes = (long)nrows * ldp * 4, qbytes = (long)nrows * ldq * 4;
+    const __amdgpu_buffer_rsrc_t sp = wgrad_chunk_desc(a.P + r0 * a.ldp + i0, pbytes);
+    const __amdgpu_buffer_rsrc_t sq = wgrad_chunk_desc(a.Q + r0 * a.ldq, qbytes);
+    // a slab = 32 rows x 256 columns per operand = 2048 float4: slot tid + 256 s -> row (tid >> 6) + 4 s, column 4 (tid & 63).
+    // One vector offset per operand; the slab's first row and the slot's 4 s rows go into the scalar offset.
+    const int srow = tid >> 6, scol = 4 * (tid & 63);
+    const int vp = 4 * (srow * ldp + scol), vq = 4 * (srow * ldq + scol);
+    const int sp_row = ldp * 4, sq_row = ldq * 4;                          // bytes per row
+    float* const st_base = lds + srow * LDT + scol;                        // + stage * STAGE (+ OP_T for Q) + 4 s LDT
+    const float* const fa_base = lds + (4 * lh) * LDT + wr * 128 + lr;     // + stage * STAGE + k LDT + 32 mi
+    const float* const fb_base = lds + OP_T + (4 * lh) * LDT + wc * 128 + lr;
+    const float* const cs_base = lds + tid;                                // column tid of P
+
+    f32x16 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x2 csum2 = {0.f, 0.f};
+
+    float4 rp[8], rq[8];
+    auto load_slot = [&](int t, int s) {         // slot s of slab t (rows past the chunk's end: zeros)
+        rp[s] = buf_ld4(sp, vp, (32 * t + 4 * s) * sp_row);
+        rq[s] = buf_ld4(sq, vq, (32 * t + 4 * s) * sq_row);
+    };
+    auto store_slot = [&](int stage, int s) {
+        float* d = st_base + stage * STAGE + 4 * s * LDT;
+        *reinterpret_cast<float4*>(d) = rp[s];
+        *reinterpret_cast<float4*>(d + OP_T) = rq[s];
+    };
+    struct Frag { float a[4], b[4]; };
+    // k step s of a slab (0..15): lane half lh holds k = 8 (s >> 2) + 4 lh + (s & 3)
+    auto read_frag = [&](int stage, int s) {
+        const int off = stage * STAGE + (8 * (s >> 2) + (s & 3)) * LDT;
+        Frag f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            f.a[t] = fa_base[off + 32 * t];
+            f.b[t] = fb_base[off + 32 * t];
+        }
+        return f;
+    };
+    auto mfma = [&](const Frag& f) {
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[mi], f.b[ni], acc[mi][ni], 0, 0, 0);
+    };
+    // rows 2 s, 2 s + 1 of column tid of P: two partial sums (even / odd rows), one packed add per two rows
+    auto read_csum = [&](int stage, int s) {
+        f32x2 v = {0.f, 0.f};
+        if (CSUM) {
+            const float* c = cs_base + stage * STAGE + 2 * s * LDT;
+            v[0] = c[0];
+            v[1] = c[LDT];
+        }
+        return v;
+    };
+
+    const int nslab = (nrows + W_BK - 1) / W_BK;
+    if (nslab > 0) {
+#pragma unroll
+        for (int s = 0; s < 8; ++s) load_slot(0, s);
+#pragma unroll
+        for (int s = 0; s < 8; ++s) store_slot(0, s);
+#pragma unroll
+        for (int s = 0; s < 8; ++s) load_slot(1, s);
+        for (int t = 0; t < nslab; ++t) {
+            const int stage = t & 1;
+            __syncthreads();
+            Frag cur = read_frag(stage, 0);
+            f32x2 cv = read_csum(stage, 0);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                Frag nxt;
+                f32x2 cvn;
+                if (s < 15) { nxt = read_frag(stage, s + 1); cvn = read_csum(stage, s + 1); }
+                if (s < 8) {                       // slab t + 1 -> the other stage, slab t + 2 requested into the freed registers
+                    store_slot(stage ^ 1, s);
+                    load_slot(t + 2, s);
+                }
+                if (CSUM) csum2 += cv;             // (read one k step ahead, as the fragments: no wait in front of the add)
+                mfma(cur);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                       // MFMA
+                    if (r < (CSUM ? 6 : 4)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read (4 fragment pairs, 2 column-sum rows)
+                    else if (r >= 8 && r < 10) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);    // DS write
+                    else if (r >= 10 && r < 12) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
+                    __builtin_amdgcn_sched_group_barrier(0x006, 2, 0);                       // VALU | SALU
+                }
+                if (s < 15) { cur = nxt; cv = cvn; }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    const long stride = (long)a.Nout * a.Nin + (CSUM ? a.Nout : 0);
+    float* out = a.slab + (long)chunk * stride;
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int i = i0 + wr * 128 + mi * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) out[(long)i * a.Nin + wc * 128 + ni * 32 + lr] = acc[mi][ni][reg];
+        }
+    if (CSUM) out[(long)a.Nout * a.Nin + i0 + tid] = csum2[0] + csum2[1];
+}
+
 // Generic fallback (scalar-guarded loads) for operands that are not 16-byte tileable, e.g. the (N, O) head gradient.
 template <int BNW>   // 128: waves 2x2, each 2x2 MFMA tiles;  32: waves 4x1, each one MFMA tile
 __global__ __launch_bounds__(256, 2) void wgrad_kernel_generic(WgradArgs a) {
@@ -517,6 +653,8 @@ int launch_wgrad_fp32(const WgradPick& p, const WgradArgs& a, hipStream_t st) {
         case WG_WIDE3: return wgrad_launch<&wgrad3_kernel>(p, a, st);
         case WG_GENERIC32: return wgrad_launch<&wgrad_kernel_generic<32>>(p, a, st);
         case WG_GENERIC128: return wgrad_launch<&wgrad_kernel_generic<128>>(p, a, st);
+        case WG_WAVE:                                                                       // 133 120 B of dynamic LDS
+            return a.colsum ? wgrad_launch<&wgrad_wave_kernel<true>>(p, a, st) : wgrad_launch<&wgrad_wave_kernel<false>>(p, a, st);
         default: REGT_CHECK_ARG(false, "wgrad: kernel %d is not an fp32-MFMA kernel", (int)p.kernel);
     }
     return REGT_OK;
