@@ -492,6 +492,30 @@ int32_t regt_gru_backward(const regt_gru_dims* dims, const float* x, const float
  *   from residual and y; gamma may hold zeros.  dz must not alias an input.  scratch:
  *   regt_stae_add_layernorm_backward_scratch_floats floats (0: arguments out of range).  D % 32 == 0, 32 <= D <= 256;
  *   1 <= M < 2^31 / 4; eps > 0; every pointer 16-byte aligned.
+ *
+ * Training of the whole model (regtgcn_amd.nn.STAEformerTrainable composes these with the layer's entries above).  Additive
+ * entries, fp32, no float atomics, bit-reproducible; nothing outside the documented windows is written.  dims is checked as for
+ * regt_stae_forward (same limits), M = batch * in_steps * num_nodes rows of D = model_dim floats, rows (b T + t) N + n.
+ * regt_stae_embed: layer 0's input X0 (M x D, dense rows) from x -- the very kernel regt_stae_forward starts with.  params: the
+ *   first six entries of the table above (node_emb, adaptive_embedding, input_proj.weight, .bias, tod_embedding.weight,
+ *   dow_embedding.weight; NULL where the width is 0).
+ * regt_stae_embed_backward: given x and dx0 (M x D, dense rows) writes the gradients of those six entries into grads (same order,
+ *   same shapes, NULL where the width is 0 -- both ways); x gets no gradient.  A table row's gradient goes to the row the forward
+ *   read AFTER its clamp; a row no input hits gets exactly 0.  Limit: input_embedding_dim * (input_dim + 1) + steps_per_day *
+ *   tod_embedding_dim + days_per_week * dow_embedding_dim <= 15360 floats (one chunk's partial sums live in the LDS).  scratch:
+ *   regt_stae_embed_backward_scratch_floats floats (0: arguments out of range): one partial of that many floats per chunk of rows.
+ * regt_stae_output_proj: out (batch, out_steps, num_nodes, output_dim), contiguous, = the use_mixed_proj tail of x (M x D) -- the
+ *   very kernel regt_stae_forward ends with.  w (out_steps * output_dim, in_steps * D), bias (out_steps * output_dim).
+ * regt_stae_output_proj_backward: dout[b, o, n, c] is read at dout + b sb + o so + n sn + c sc (element strides >= 0: a strided
+ *   window is fine); writes dx (M x D, dense rows; NULL: not wanted), dw and db (shapes of w and bias).  scratch:
+ *   regt_stae_output_proj_backward_scratch_floats floats (0: arguments out of range): partial dw | db per chunk of (b, n) pairs.
+ * regt_stae_drop_add_layernorm: out = LayerNorm(residual + keep y / (1 - p)) * gamma + beta: regt_stae_add_layernorm with dropout
+ *   on the branch y.  keep: (M, D / 32) 32-bit words, row-major, 4-byte aligned; bit j of word w keeps column 32 w + j.  keep ==
+ *   NULL: no dropout and no scaling, the bits of regt_stae_add_layernorm.  0 <= p < 1; other limits as regt_stae_add_layernorm.
+ * regt_stae_drop_add_layernorm_backward: dz (M x D) = dL/dresidual, dy (M x D) = dL/dy = keep dz / (1 - p), written in the same
+ *   pass, dgamma, dbeta.  keep == NULL: regt_stae_add_layernorm_backward (dz is the gradient of y too; dy is not touched and may be
+ *   NULL).  dz and dy must not alias an input or each other.  scratch: regt_stae_drop_add_layernorm_backward_scratch_floats floats
+ *   (0: arguments out of range).  Limits as regt_stae_add_layernorm_backward; 0 <= p < 1.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t batch, in_steps, num_nodes, in_features, input_dim;
@@ -517,6 +541,22 @@ size_t regt_stae_add_layernorm_backward_scratch_floats(int64_t rows, int32_t wid
 int32_t regt_stae_add_layernorm_backward(const float* residual, const float* y, const float* gamma, const float* dout, float eps,
                                          int64_t rows, int32_t width, float* dz, float* dgamma, float* dbeta, float* scratch,
                                          regt_stream_t stream);
+int32_t regt_stae_embed(const regt_stae_dims* dims, const float* x, const float* const* params, float* out, regt_stream_t stream);
+size_t regt_stae_embed_backward_scratch_floats(const regt_stae_dims* dims);
+int32_t regt_stae_embed_backward(const regt_stae_dims* dims, const float* x, const float* dx0, float* const* grads, float* scratch,
+                                 regt_stream_t stream);
+int32_t regt_stae_output_proj(const regt_stae_dims* dims, const float* x, const float* w, const float* bias, float* out,
+                              regt_stream_t stream);
+size_t regt_stae_output_proj_backward_scratch_floats(const regt_stae_dims* dims);
+int32_t regt_stae_output_proj_backward(const regt_stae_dims* dims, const float* x, const float* w, const float* dout, int64_t sb,
+                                       int64_t so, int64_t sn, int64_t sc, float* dx, float* dw, float* db, float* scratch,
+                                       regt_stream_t stream);
+int32_t regt_stae_drop_add_layernorm(const float* residual, const float* y, const uint32_t* keep, float p, const float* gamma,
+                                     const float* beta, float eps, int64_t rows, int32_t width, float* out, regt_stream_t stream);
+size_t regt_stae_drop_add_layernorm_backward_scratch_floats(int64_t rows, int32_t width);
+int32_t regt_stae_drop_add_layernorm_backward(const float* residual, const float* y, const uint32_t* keep, float p, const float* gamma,
+                                              const float* dout, float eps, int64_t rows, int32_t width, float* dz, float* dy,
+                                              float* dgamma, float* dbeta, float* scratch, regt_stream_t stream);
 
 /* relu's gradient in place: d[i] = 0 where y[i] <= 0, y the relu's output (the head of StackedGRU between two regt_linear calls).
  * 1 <= n < 2^31. */

@@ -167,6 +167,16 @@ SIGNATURES = {
                                                  C.c_int32, vp, vp, vp, C.c_int64, vp, vp]),
     "regt_stae_add_layernorm_backward_scratch_floats": (C.c_size_t, [C.c_int64, C.c_int32]),
     "regt_stae_add_layernorm_backward": (C.c_int32, [vp, vp, vp, vp, C.c_float, C.c_int64, C.c_int32, vp, vp, vp, vp, vp]),
+    "regt_stae_embed": (C.c_int32, [vp, vp, vp, vp, vp]),
+    "regt_stae_embed_backward_scratch_floats": (C.c_size_t, [vp]),
+    "regt_stae_embed_backward": (C.c_int32, [vp, vp, vp, vp, vp, vp]),
+    "regt_stae_output_proj": (C.c_int32, [vp, vp, vp, vp, vp, vp]),
+    "regt_stae_output_proj_backward_scratch_floats": (C.c_size_t, [vp]),
+    "regt_stae_output_proj_backward": (C.c_int32, [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]),
+    "regt_stae_drop_add_layernorm": (C.c_int32, [vp, vp, vp, C.c_float, vp, vp, C.c_float, C.c_int64, C.c_int32, vp, vp]),
+    "regt_stae_drop_add_layernorm_backward_scratch_floats": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "regt_stae_drop_add_layernorm_backward": (C.c_int32, [vp, vp, vp, C.c_float, vp, vp, C.c_float, C.c_int64, C.c_int32, vp, vp, vp, vp,
+                                                          vp, vp]),
     "regt_relu_backward": (C.c_int32, [vp, vp, C.c_int64, vp]),
     "regt_mse_loss_grad": (C.c_int32, [vp, vp, vp, vp, C.c_int64, C.c_int64, vp]),
 }

@@ -1,5 +1,6 @@
-// Entry points of the baselines with their argument checks: SpatialGCN, STNorm, STID, StackedGRU, STAEformer (inference, and the
-// op-site forward / backward entries of its trainable self-attention layer).
+// Entry points of the baselines with their argument checks: SpatialGCN, STNorm, STID, StackedGRU, STAEformer (inference, the op-site
+// forward / backward entries of its trainable self-attention layer, and those of whole-model training: embedding, output projection,
+// keep-bit dropout folded into add+LayerNorm).
 #include "api_internal.h"
 
 using namespace regt;
@@ -398,6 +399,101 @@ int32_t regt_stae_add_layernorm_backward(const float* residual, const float* y, 
                    "regt_stae_add_layernorm_backward: every pointer must be 16-byte aligned");
     REGT_CHECK_ARG(dz != residual && dz != y && dz != dout, "regt_stae_add_layernorm_backward: dz must not alias residual, y or dout");
     return regt::launch_stae_add_layernorm_bwd(residual, y, gamma, dout, eps, (long)M, D, dz, dgamma, dbeta, scratch, (hipStream_t)st);
+}
+
+// ---- whole-model training: the embedding, the output projection and keep-bit dropout folded into add+LayerNorm ----------------------
+
+int32_t regt_stae_embed(const regt_stae_dims* d, const float* x, const float* const* params, float* out, regt_stream_t st) {
+    regt::StaeDims s;
+    if (int rc = stae_check("regt_stae_embed", d, &s)) return rc;
+    REGT_CHECK_ARG(x && out && params, "regt_stae_embed: x, out or the parameter table is NULL");
+    const bool need[6] = {s.e_sp > 0, s.e_adp > 0, true, true, s.e_tod > 0, s.e_dow > 0};
+    for (int k = 0; k < 6; ++k) REGT_CHECK_ARG(!need[k] || params[k] != nullptr, "regt_stae_embed: head entry %d is NULL", k);
+    return regt::launch_stae_embed(s, x, params, out, (hipStream_t)st);
+}
+
+size_t regt_stae_embed_backward_scratch_floats(const regt_stae_dims* d) {
+    regt::StaeDims s;
+    if (stae_check("regt_stae_embed_backward_scratch_floats", d, &s)) return 0;
+    if (regt::stae_embed_bwd_partial_floats(s) > regt::STAE_EMBED_BWD_MAX_LDS) {
+        regt::set_error("regt_stae_embed_backward_scratch_floats: the input projection and the two tables exceed %d floats",
+                        regt::STAE_EMBED_BWD_MAX_LDS);
+        return 0;
+    }
+    return regt::stae_embed_bwd_scratch_floats(s);
+}
+
+int32_t regt_stae_embed_backward(const regt_stae_dims* d, const float* x, const float* dx0, float* const* grads, float* scratch,
+                                 regt_stream_t st) {
+    regt::StaeDims s;
+    if (int rc = stae_check("regt_stae_embed_backward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && dx0 && grads && scratch, "regt_stae_embed_backward: x, dx0, the gradient table or scratch is NULL");
+    const bool need[6] = {s.e_sp > 0, s.e_adp > 0, true, true, s.e_tod > 0, s.e_dow > 0};
+    for (int k = 0; k < 6; ++k) REGT_CHECK_ARG(!need[k] || grads[k] != nullptr, "regt_stae_embed_backward: gradient entry %d is NULL", k);
+    return regt::launch_stae_embed_bwd(s, x, dx0, grads, scratch, (hipStream_t)st);
+}
+
+int32_t regt_stae_output_proj(const regt_stae_dims* d, const float* x, const float* w, const float* bias, float* out, regt_stream_t st) {
+    regt::StaeDims s;
+    if (int rc = stae_check("regt_stae_output_proj", d, &s)) return rc;
+    REGT_CHECK_ARG(x && w && bias && out, "regt_stae_output_proj: NULL pointer");
+    return regt::launch_stae_output_proj(s, x, w, bias, out, (hipStream_t)st);
+}
+
+size_t regt_stae_output_proj_backward_scratch_floats(const regt_stae_dims* d) {
+    regt::StaeDims s;
+    if (stae_check("regt_stae_output_proj_backward_scratch_floats", d, &s)) return 0;
+    return regt::stae_output_proj_bwd_scratch_floats(s);
+}
+
+int32_t regt_stae_output_proj_backward(const regt_stae_dims* d, const float* x, const float* w, const float* dout, int64_t sb, int64_t so,
+                                       int64_t sn, int64_t sc, float* dx, float* dw, float* db, float* scratch, regt_stream_t st) {
+    regt::StaeDims s;
+    if (int rc = stae_check("regt_stae_output_proj_backward", d, &s)) return rc;
+    REGT_CHECK_ARG(x && w && dout && dw && db && scratch, "regt_stae_output_proj_backward: NULL pointer (only dx may be NULL)");
+    REGT_CHECK_ARG(sb >= 0 && so >= 0 && sn >= 0 && sc >= 0, "regt_stae_output_proj_backward: dout strides must be >= 0, got %ld, %ld, %ld, %ld",
+                   (long)sb, (long)so, (long)sn, (long)sc);
+    REGT_CHECK_ARG(dx != x, "regt_stae_output_proj_backward: dx must not alias x");
+    return regt::launch_stae_output_proj_bwd(s, x, w, dout, (long)sb, (long)so, (long)sn, (long)sc, dx, dw, db, scratch, (hipStream_t)st);
+}
+
+static int stae_drop_check(const char* what, const void* keep, float p) {
+    REGT_CHECK_ARG(p >= 0.f && p < 1.f, "%s: p must be in [0, 1), got %g", what, (double)p);
+    REGT_CHECK_ARG((reinterpret_cast<uintptr_t>(keep) & 3) == 0, "%s: keep must be 4-byte aligned", what);
+    return REGT_OK;
+}
+
+int32_t regt_stae_drop_add_layernorm(const float* residual, const float* y, const uint32_t* keep, float p, const float* gamma,
+                                     const float* beta, float eps, int64_t M, int32_t D, float* out, regt_stream_t st) {
+    if (int rc = stae_drop_check("regt_stae_drop_add_layernorm", keep, p)) return rc;
+    if (!keep) return regt_stae_add_layernorm(residual, y, gamma, beta, eps, M, D, out, st);
+    REGT_CHECK_ARG(residual && y && gamma && beta && out, "regt_stae_drop_add_layernorm: NULL pointer");
+    REGT_CHECK_ARG(D >= 32 && D % 32 == 0 && D <= regt::STAE_MAX_DIM, "regt_stae_drop_add_layernorm: D must be a multiple of 32 in [32, %d], got %d",
+                   regt::STAE_MAX_DIM, D);
+    REGT_CHECK_ARG(M >= 1 && M < (1L << 31), "regt_stae_drop_add_layernorm: M must be in [1, 2^31), got %ld", (long)M);
+    REGT_CHECK_ARG(eps > 0.f, "regt_stae_drop_add_layernorm: eps must be > 0, got %g", (double)eps);
+    return regt::launch_stae_drop_add_layernorm(residual, y, keep, 1.0f / (1.0f - p), gamma, beta, eps, (long)M, D, out, (hipStream_t)st);
+}
+
+size_t regt_stae_drop_add_layernorm_backward_scratch_floats(int64_t M, int32_t D) {
+    if (stae_ln_backward_check("regt_stae_drop_add_layernorm_backward_scratch_floats", M, D)) return 0;
+    return regt::stae_add_layernorm_bwd_scratch_floats((long)M, D);
+}
+
+int32_t regt_stae_drop_add_layernorm_backward(const float* residual, const float* y, const uint32_t* keep, float p, const float* gamma,
+                                              const float* dout, float eps, int64_t M, int32_t D, float* dz, float* dy, float* dgamma,
+                                              float* dbeta, float* scratch, regt_stream_t st) {
+    if (int rc = stae_drop_check("regt_stae_drop_add_layernorm_backward", keep, p)) return rc;
+    if (!keep) return regt_stae_add_layernorm_backward(residual, y, gamma, dout, eps, M, D, dz, dgamma, dbeta, scratch, st);
+    REGT_CHECK_ARG(residual && y && gamma && dout && dz && dy && dgamma && dbeta && scratch, "regt_stae_drop_add_layernorm_backward: NULL pointer");
+    if (int rc = stae_ln_backward_check("regt_stae_drop_add_layernorm_backward", M, D)) return rc;
+    REGT_CHECK_ARG(eps > 0.f, "regt_stae_drop_add_layernorm_backward: eps must be > 0, got %g", (double)eps);
+    REGT_CHECK_ARG(al16(residual) && al16(y) && al16(gamma) && al16(dout) && al16(dz) && al16(dy) && al16(dgamma) && al16(dbeta) && al16(scratch),
+                   "regt_stae_drop_add_layernorm_backward: every float pointer must be 16-byte aligned");
+    REGT_CHECK_ARG(dz != residual && dz != y && dz != dout && dy != residual && dy != y && dy != dout && dy != dz,
+                   "regt_stae_drop_add_layernorm_backward: dz and dy must not alias an input or each other");
+    return regt::launch_stae_add_layernorm_bwd(residual, y, gamma, dout, eps, (long)M, D, dz, dgamma, dbeta, scratch, (hipStream_t)st, keep,
+                                               1.0f / (1.0f - p), dy);
 }
 
 }  // extern "C"

@@ -436,9 +436,32 @@ int launch_stae_attention_bwd(const float* q, const float* k, const float* v, lo
                               float* scratch, hipStream_t st);
 // Add+LayerNorm: dz (the gradient of residual and of y; no alias with an input), dgamma, dbeta; scratch: per-wave partial sums.
 size_t stae_add_layernorm_bwd_scratch_floats(long M, int D);
+// keep (M, D / 32 words: bit j of word w keeps column 32 w + j), optional: the branch y went through dropout, z = residual + keep y s;
+// dz is then the gradient of residual only and dy = keep dz s (M x D, written in the same pass) that of y
 int launch_stae_add_layernorm_bwd(const float* residual, const float* y, const float* gamma, const float* dout, float eps, long M, int D,
-                                  float* dz, float* dgamma, float* dbeta, float* scratch, hipStream_t st);
+                                  float* dz, float* dgamma, float* dbeta, float* scratch, hipStream_t st, const uint32_t* keep = nullptr,
+                                  float s = 1.0f, float* dy = nullptr);
 int launch_stae_output_proj(const StaeDims& s, const float* x, const float* w, const float* bias, float* out, hipStream_t st);
+// Column sums of (nparts, width) partial rows in 256 interleaved running sums combined pairwise; segment k of the result, columns
+// [end[k-1], end[k]), goes to out[k].
+struct ColSegs {
+    static constexpr int MAX = 4;
+    float* out[MAX];
+    long end[MAX];
+};
+int launch_stae_col_reduce(const float* partial, long nparts, long width, const ColSegs& segs, hipStream_t st);
+// STAEformer whole-model training (staeformer_train.hip): keep-bit dropout folded into add+LayerNorm, and the gradients of the
+// embedding and of the output projection.  grads of the embedding: node_emb, adaptive_embedding, input_proj w, b, tod, dow (the first
+// six table entries; NULL where the width is 0).  dout of the output projection is read through four element strides.
+constexpr int STAE_EMBED_BWD_MAX_LDS = 15360;      // floats of one chunk's partial: input_proj w, b and the two tables
+int launch_stae_drop_add_layernorm(const float* residual, const float* y, const uint32_t* keep, float s, const float* gamma, const float* beta,
+                                   float eps, long M, int D, float* out, hipStream_t st);
+long stae_embed_bwd_partial_floats(const StaeDims& s);
+size_t stae_embed_bwd_scratch_floats(const StaeDims& s);
+int launch_stae_embed_bwd(const StaeDims& s, const float* x, const float* dx0, float* const* grads, float* scratch, hipStream_t st);
+size_t stae_output_proj_bwd_scratch_floats(const StaeDims& s);
+int launch_stae_output_proj_bwd(const StaeDims& s, const float* x, const float* w, const float* dout, long sb, long so, long sn, long sc,
+                                float* dx, float* dw, float* db, float* scratch, hipStream_t st);
 
 // ---- per-device launch state ------------------------------------------------------------------------------------
 // What a launcher needs to know about the device it is about to launch on is keyed by the device's ordinal, never by the process.

@@ -18,8 +18,8 @@
 //   each (row, head)'s m + log(l), from which staeformer_bwd.hip rebuilds the probabilities.
 //
 // stae_add_layernorm_kernel: out = LayerNorm(residual + y) gamma + beta over D (biased variance, as nn.LayerNorm), one wave per
-// row, the row held in registers (mean first, then the centred squares; ln_centre_row of stae_rows.h, which the backward kernel
-// calls too); out may alias residual.
+// row, the row held in registers (mean first, then the centred squares); the kernel is the DROP = false instance of the template in
+// stae_rows.h, whose DROP = true instance (staeformer_train.hip) applies keep-bit dropout to y; out may alias residual.
 //
 // stae_embed_kernel: layer 0's input, columns in the reference's concatenation order (models/STAEformer.py:203-229):
 // input_proj(x[..., :input_dim]) | tod_embedding[(x[..., 1] steps_per_day).long()] | dow_embedding[x[..., 2].long()] | node_emb |
@@ -124,34 +124,12 @@ __global__ __launch_bounds__(THREADS) void stae_attention_kernel(const AttnArgs 
     }
 }
 
-// residual and out may be the same array: a lane reads its own elements before it writes them
-__global__ __launch_bounds__(THREADS) void stae_add_layernorm_kernel(const float* residual, const float* __restrict__ y,
-                                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                     float eps, long M, int D, float* out) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
-    if (row >= M) return;
-    float v[4];
-    const float rstd = ln_centre_row(residual + row * D, y + row * D, lane, D, eps, v);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int d = lane + 64 * j;
-        if (d < D) out[row * D + d] = v[j] * rstd * gamma[d] + beta[d];
-    }
-}
-
 struct EmbedArgs {
     const float *x, *w_in, *b_in, *tod, *dow, *node, *adp;
     float* out;
     long total;
     int T, N, F, Cin, e_in, e_tod, e_dow, e_sp, e_adp, D, spd, dpw;
 };
-
-// (long)v clamped into [0, size): truncation toward zero; negative and NaN give 0
-__device__ __forceinline__ int table_index(float v, int size) {
-    if (!(v >= 1.0f)) return 0;
-    return v >= (float)size ? size - 1 : (int)v;
-}
 
 __global__ __launch_bounds__(THREADS) void stae_embed_kernel(const EmbedArgs a) {
     const long e = (long)blockIdx.x * THREADS + threadIdx.x;
@@ -220,7 +198,8 @@ int launch_stae_add_layernorm(const float* residual, const float* y, const float
                               float* out, hipStream_t st) {
     const long blocks = (M + THREADS / 64 - 1) / (THREADS / 64);
     REGT_CHECK_ARG(blocks < (1L << 31), "stae add_layernorm: %ld workgroups exceed the grid", blocks);
-    hipLaunchKernelGGL(stae_add_layernorm_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, residual, y, gamma, beta, eps, M, D, out);
+    hipLaunchKernelGGL(stae_add_layernorm_kernel<false>, dim3((unsigned)blocks), dim3(THREADS), 0, st, residual, y, nullptr, 1.0f, gamma, beta, eps,
+                       M, D, out);
     REGT_CHECK_LAUNCH();
     return REGT_OK;
 }

@@ -25,9 +25,11 @@
 // Add+LayerNorm backward.  One wave per row recomputes z = residual + y, its mean and rstd with the forward's own code
 // (ln_centre_row), x^ = (z - mean) rstd, g = dout gamma, and writes dz = rstd (g - mean(g) - x^ mean(g x^)), the gradient of both
 // residual and y.  x^ comes from the inputs: nothing is divided by gamma.  dgamma = sum_rows dout x^ and dbeta = sum_rows dout: a
-// wave carries its 16 consecutive rows in registers and writes one partial row of 2 D floats; stae_ln_reduce_kernel then sums each
+// wave carries its 16 consecutive rows in registers and writes one partial row of 2 D floats; stae_col_reduce_kernel then sums each
 // column's partials in 256 interleaved running sums combined pairwise (the split csrc/stnorm.hip's op_accumulate uses, for the
-// same reason: one running sum over all M rows loses the bits a cancelling column needs).
+// same reason: one running sum over all M rows loses the bits a cancelling column needs).  The kernel is a template of stae_rows.h:
+// its DROP instance also writes dy = keep dz s, the gradient of a branch that went through keep-bit dropout, in the same pass.  The
+// column reduction (launch_stae_col_reduce) also serves the embedding and output-projection gradients of staeformer_train.hip.
 #include "stae_rows.h"
 
 namespace regt {
@@ -36,7 +38,6 @@ namespace {
 
 using namespace stae;
 
-constexpr int LN_ROWS = 16;               // rows per wave of the add+LayerNorm backward
 constexpr float SCALE = 0.17677669529663687f;                // 1 / sqrt(32)
 
 struct AttnBwdArgs {
@@ -193,66 +194,26 @@ __global__ __launch_bounds__(THREADS) void stae_attention_dkv_kernel(const AttnB
     }
 }
 
-// partial (nwaves, 2, D): wave w's sums of dout x^ and of dout over rows [LN_ROWS w, LN_ROWS w + LN_ROWS)
-__global__ __launch_bounds__(THREADS) void stae_add_layernorm_bwd_kernel(const float* __restrict__ residual, const float* __restrict__ y,
-                                                                         const float* __restrict__ gamma, const float* __restrict__ dout,
-                                                                         float eps, long M, int D, float* __restrict__ dz,
-                                                                         float* __restrict__ partial) {
-    const int lane = threadIdx.x & 63;
-    const long w = (long)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
-    const long r0 = w * LN_ROWS;
-    if (r0 >= M) return;
-    float gm[4], dg[4], db[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int d = lane + 64 * j;
-        gm[j] = d < D ? gamma[d] : 0.f;
-        dg[j] = 0.f, db[j] = 0.f;
-    }
-    const long r1 = r0 + LN_ROWS < M ? r0 + LN_ROWS : M;
-    for (long row = r0; row < r1; ++row) {
-        float v[4], g[4];
-        const float rstd = ln_centre_row(residual + row * D, y + row * D, lane, D, eps, v);
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int d = lane + 64 * j;
-            const float dy = d < D ? dout[row * D + d] : 0.f;
-            v[j] *= rstd;                                    // x^
-            g[j] = dy * gm[j];
-            s1 += g[j];
-            s2 = fmaf(g[j], v[j], s2);
-            dg[j] = fmaf(dy, v[j], dg[j]);
-            db[j] += dy;
-        }
-        const float m1 = wave_sum(s1) / (float)D, m2 = wave_sum(s2) / (float)D;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int d = lane + 64 * j;
-            if (d < D) dz[row * D + d] = rstd * (g[j] - m1 - v[j] * m2);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int d = lane + 64 * j;
-        if (d < D) partial[w * 2 * D + d] = dg[j], partial[w * 2 * D + D + d] = db[j];
-    }
-}
-
-// one workgroup per column c of the (nwaves, 2 D) partials: thread t adds partials t, t + 256, ... in order, then a pairwise tree
-__global__ __launch_bounds__(THREADS) void stae_ln_reduce_kernel(const float* __restrict__ partial, long nwaves, int D,
-                                                                 float* __restrict__ dgamma, float* __restrict__ dbeta) {
+// one workgroup per column c of the (nparts, width) partials: thread t adds partials t, t + 256, ... in order, then a pairwise tree
+__global__ __launch_bounds__(THREADS) void stae_col_reduce_kernel(const float* __restrict__ partial, long nparts, long width, const ColSegs segs) {
     __shared__ float sm[THREADS];
-    const int c = blockIdx.x;
+    const long c = blockIdx.x;
     float s = 0.f;
-    for (long w = threadIdx.x; w < nwaves; w += THREADS) s += partial[w * 2 * D + c];
+    for (long w = threadIdx.x; w < nparts; w += THREADS) s += partial[w * width + c];
     sm[threadIdx.x] = s;
     __syncthreads();
     for (int half = THREADS / 2; half >= 1; half >>= 1) {
         if ((int)threadIdx.x < half) sm[threadIdx.x] += sm[threadIdx.x + half];
         __syncthreads();
     }
-    if (threadIdx.x == 0) (c < D ? dgamma[c] : dbeta[c - D]) = sm[0];
+    if (threadIdx.x == 0) {
+        long lo = 0;
+#pragma unroll
+        for (int k = 0; k < ColSegs::MAX; ++k) {
+            if (c >= lo && c < segs.end[k]) segs.out[k][c - lo] = sm[0];
+            lo = segs.end[k] > lo ? segs.end[k] : lo;
+        }
+    }
 }
 
 }  // namespace
@@ -278,16 +239,30 @@ int launch_stae_attention_bwd(const float* q, const float* k, const float* v, lo
     return REGT_OK;
 }
 
-int launch_stae_add_layernorm_bwd(const float* residual, const float* y, const float* gamma, const float* dout, float eps, long M, int D,
-                                  float* dz, float* dgamma, float* dbeta, float* scratch, hipStream_t st) {
-    const long nwaves = (M + LN_ROWS - 1) / LN_ROWS;
-    const long blocks = (nwaves + THREADS / 64 - 1) / (THREADS / 64);
-    hipLaunchKernelGGL(stae_add_layernorm_bwd_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, residual, y, gamma, dout, eps, M, D, dz,
-                       scratch);
-    REGT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(stae_ln_reduce_kernel, dim3((unsigned)(2 * D)), dim3(THREADS), 0, st, scratch, nwaves, D, dgamma, dbeta);
+// out segment k takes columns [end[k-1], end[k]) of the summed partials (an empty segment has end[k] == end[k-1])
+int launch_stae_col_reduce(const float* partial, long nparts, long width, const ColSegs& segs, hipStream_t st) {
+    REGT_CHECK_ARG(width >= 1 && width < (1L << 31), "stae column reduction: %ld columns exceed the grid", width);
+    hipLaunchKernelGGL(stae_col_reduce_kernel, dim3((unsigned)width), dim3(THREADS), 0, st, partial, nparts, width, segs);
     REGT_CHECK_LAUNCH();
     return REGT_OK;
+}
+
+// keep == nullptr: no dropout, dz is the gradient of both inputs and dy is not touched
+int launch_stae_add_layernorm_bwd(const float* residual, const float* y, const float* gamma, const float* dout, float eps, long M, int D,
+                                  float* dz, float* dgamma, float* dbeta, float* scratch, hipStream_t st, const uint32_t* keep, float s,
+                                  float* dy) {
+    const long nwaves = (M + LN_ROWS - 1) / LN_ROWS;
+    const long blocks = (nwaves + THREADS / 64 - 1) / (THREADS / 64);
+    if (keep)
+        hipLaunchKernelGGL(stae_add_layernorm_bwd_kernel<true>, dim3((unsigned)blocks), dim3(THREADS), 0, st, residual, y, keep, s, gamma, dout,
+                           eps, M, D, dz, dy, scratch);
+    else
+        hipLaunchKernelGGL(stae_add_layernorm_bwd_kernel<false>, dim3((unsigned)blocks), dim3(THREADS), 0, st, residual, y, nullptr, 1.0f, gamma,
+                           dout, eps, M, D, dz, nullptr, scratch);
+    REGT_CHECK_LAUNCH();
+    ColSegs segs{};
+    segs.out[0] = dgamma, segs.end[0] = D, segs.out[1] = dbeta, segs.end[1] = 2 * D, segs.end[2] = segs.end[3] = 2 * D;
+    return launch_stae_col_reduce(scratch, nwaves, 2 * D, segs, st);
 }
 
 }  // namespace regt

@@ -897,3 +897,82 @@ def regt_gcn_forward(x, graph: PreparedGraph, params: Dict[str, torch.Tensor], r
     where no gradient can be asked for (:func:`regt_run`)."""
     names = param_names(regional)
     return regt_run(x, graph, regional, slope, False, *[params[n] for n in names])
+
+
+# ---- STAEformer, the whole model (nn.STAEformerTrainable) ----------------------------------------------------------------------------
+
+class STAEEmbedFunction(torch.autograd.Function):
+    """(x (B, T, N, F), dims, node_emb, adaptive_embedding, input_proj.weight, .bias, tod_embedding.weight, dow_embedding.weight -- None
+    where an embedding is off) -> layer 0's input (M, model_dim) (regt_stae_embed / regt_stae_embed_backward).  x gets no gradient
+    (the reference's .long() indices and data have none to give).  Honours :func:`set_grad_accumulation_in_backward`."""
+
+    @staticmethod
+    def forward(ctx, x, dims, *params):
+        from . import ops
+        out = ops.stae_embed(dims, x, [None if p is None else p.detach() for p in params])
+        if any(ctx.needs_input_grad[2:]):
+            ctx.save_for_backward(x)
+            ctx.dims, ctx.leaf_params = dims, params
+        return out
+
+    @staticmethod
+    def backward(ctx, dx0):
+        from . import ops
+        need = ctx.needs_input_grad[2:]
+        if not any(need):                        # only x asked (every parameter frozen): it has no gradient, nothing was kept
+            return (None,) * (2 + len(need))
+        x, = ctx.saved_tensors
+        grads = ops.stae_embed_backward(ctx.dims, x, dx0)
+        params = [p if n_ else None for p, n_ in zip(ctx.leaf_params, need)]
+        return (None, None) + _deliver_grads(params, [g if n_ else None for g, n_ in zip(grads, need)])
+
+
+class STAEOutputProjFunction(torch.autograd.Function):
+    """(x (M, model_dim), dims, output_proj.weight, .bias) -> (B, out_steps, N, output_dim), the use_mixed_proj tail
+    (regt_stae_output_proj / regt_stae_output_proj_backward).  The upstream gradient is read in place through its strides.  Honours
+    :func:`set_grad_accumulation_in_backward`."""
+
+    @staticmethod
+    def forward(ctx, x, dims, w, b):
+        from . import ops
+        out = ops.stae_output_proj(dims, x, w.detach(), b.detach())
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(x)
+            ctx.dims, ctx.leaf_params = dims, (w, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import ops
+        x, = ctx.saved_tensors
+        w, b = ctx.leaf_params
+        need = ctx.needs_input_grad
+        dx, dw, db = ops.stae_output_proj_backward(ctx.dims, x, w.detach(), dout, need_dx=need[0])
+        return (dx, None) + _deliver_grads((w if need[2] else None, b if need[3] else None), (dw, db))
+
+
+class STAEDropAddLayerNormFunction(torch.autograd.Function):
+    """(residual (M, D), y (M, D), keep int32 (M, D / 32) or None, p, gamma, beta, eps) -> LayerNorm(residual + keep y / (1 - p)) gamma +
+    beta (regt_stae_drop_add_layernorm / _backward): the reference's ``ln(residual + dropout(out))``.  The backward recomputes the row
+    statistics from residual, y and keep, which is all the forward keeps, and writes both gradients in one pass.  ``keep=None`` is
+    :class:`STAEAddLayerNormFunction`'s arithmetic.  Honours :func:`set_grad_accumulation_in_backward`."""
+
+    @staticmethod
+    def forward(ctx, residual, y, keep, p, gamma, beta, eps):
+        from . import ops
+        out = ops.stae_drop_add_layernorm(residual, y, keep, p, gamma.detach(), beta.detach(), eps)
+        need = ctx.needs_input_grad
+        if need[0] or need[1] or need[4] or need[5]:
+            ctx.save_for_backward(residual, y)
+            ctx.keep, ctx.p, ctx.eps, ctx.leaf_params = keep, p, eps, (gamma, beta)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import ops
+        residual, y = ctx.saved_tensors
+        gamma, beta = ctx.leaf_params
+        dz, dy, dgamma, dbeta = ops.stae_drop_add_layernorm_backward(residual, y, ctx.keep, ctx.p, gamma.detach(), dout, ctx.eps)
+        need = ctx.needs_input_grad
+        return (dz if need[0] else None, dy if need[1] else None, None, None) + \
+            _deliver_grads((gamma if need[4] else None, beta if need[5] else None), (dgamma, dbeta)) + (None,)

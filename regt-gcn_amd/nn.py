@@ -14,6 +14,7 @@ unchanged:
 * :class:`StackedGRU`           <-> models/StackedGRU.py:4-30
 * :class:`STAEformer`           <-> models/STAEformer.py:110-255 (inference only)
 * :class:`SelfAttentionLayer`   <-> models/STAEformer.py:76-107 (trainable)
+* :class:`STAEformerTrainable`  <-> models/STAEformer.py:110-255 (trainable, keep-bit dropout)
 
 The modules only *hold* parameters; all arithmetic runs in libregtgcn_hip.so through
 :class:`regt-gcn_amd.functional.RegTGCNFunction`.  There is no CPU implementation here: calling
@@ -31,7 +32,7 @@ from . import _lib
 from . import ops
 from .functional import (HEAD_HIDDEN, PARAM_NAMES_CELL, AggregateFunction, Cell0Function, CellFunction, GatAggregateFunction,
                          GRUFunction, LinearFunction, MLPHeadFunction, RegTGCNFunction, SpatialEmbedFunction, STAEAddLayerNormFunction,
-                         STAEPackedAttentionFunction, STIDFunction, STNormFunction, ZeroGradAnchor, cell_run, param_names, regt_run)
+                         STAEDropAddLayerNormFunction, STAEEmbedFunction, STAEOutputProjFunction, STAEPackedAttentionFunction, STIDFunction, STNormFunction, ZeroGradAnchor, cell_run, param_names, regt_run)
 from .graph import (AttentionPattern, GcnOperator, MeanOperator, PreparedGraph, fingerprint, prepare_attention_pattern,
                     prepare_cheb_operator, prepare_gcn_operator, prepare_graph, prepare_mean_operator)
 
@@ -980,13 +981,16 @@ class STAEformer(nn.Module):
                              self.steps_per_day, self.days_per_week, self.num_heads, self.feed_forward_dim, self.num_layers, self.out_steps,
                              self.output_dim, int(bool(self.use_mixed_proj)), float(self.attn_layers_t[0].ln1.eps))
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def _check_x(self, x: torch.Tensor):
         _need_cuda(x)
         need = max(self.input_dim, 2 if self.tod_embedding_dim > 0 else 0, 3 if self.dow_embedding_dim > 0 else 0)
         if x.dim() != 4 or x.shape[1] != self.in_steps or x.shape[2] != self.num_nodes or x.shape[3] < need:
             raise ValueError(f"x must be (B, {self.in_steps}, {self.num_nodes}, F >= {need}), got {tuple(x.shape)}")
         if x.dtype != torch.float32:
             raise _lib.RegtError(f"STAEformer input must be float32, got {x.dtype}")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        self._check_x(x)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("STAEformer is inference only here (no backward kernels): call it under torch.no_grad()")
         if self.training and self.dropout > 0:
@@ -1036,11 +1040,85 @@ class SelfAttentionLayer(_STAELayerParams):
                              f"{tuple(x.shape)}, dim={dim}")
         if b < 1 or t < 1 or n < 1:
             raise ValueError(f"x must have no empty axis, got {tuple(x.shape)}")
-        p = self.table()
         rows = x.contiguous().view(b * t * n, d)
-        qkv = LinearFunction.apply(rows, torch.cat([p[0], p[2], p[4]]), torch.cat([p[1], p[3], p[5]]))
-        a = STAEPackedAttentionFunction.apply(qkv, b, t, n, self.num_heads, axis)
-        y = LinearFunction.apply(a, p[6], p[7])
-        h = STAEAddLayerNormFunction.apply(rows, y, p[12], p[13], float(self.ln1.eps))
-        f = MLPHeadFunction.apply(h, p[8], p[9], p[10], p[11])
-        return STAEAddLayerNormFunction.apply(h, f, p[14], p[15], float(self.ln2.eps)).view(x.shape)
+        return _stae_layer_rows(rows, self.table(), b, t, n, self.num_heads, axis, float(self.ln1.eps), float(self.ln2.eps)).view(x.shape)
+
+
+def _stae_layer_rows(rows: torch.Tensor, p, b: int, t: int, n: int, heads: int, axis: int, eps1: float, eps2: float,
+                     keep1: Optional[torch.Tensor] = None, keep2: Optional[torch.Tensor] = None, drop: float = 0.0) -> torch.Tensor:
+    """One self-attention layer on (M, model_dim) rows; ``p`` the layer's 16-entry table (``_STAELayerParams.table``).  ``keep1`` /
+    ``keep2``: int32 (M, model_dim / 32) keep words of dropout1 / dropout2 with probability ``drop`` (models/STAEformer.py:98-104), folded
+    into the add+LayerNorm that follows; None: no dropout."""
+    qkv = LinearFunction.apply(rows, torch.cat([p[0], p[2], p[4]]), torch.cat([p[1], p[3], p[5]]))
+    a = STAEPackedAttentionFunction.apply(qkv, b, t, n, heads, axis)
+    y = LinearFunction.apply(a, p[6], p[7])
+    if keep1 is None:
+        h = STAEAddLayerNormFunction.apply(rows, y, p[12], p[13], eps1)
+    else:
+        h = STAEDropAddLayerNormFunction.apply(rows, y, keep1, drop, p[12], p[13], eps1)
+    f = MLPHeadFunction.apply(h, p[8], p[9], p[10], p[11])
+    if keep2 is None:
+        return STAEAddLayerNormFunction.apply(h, f, p[14], p[15], eps2)
+    return STAEDropAddLayerNormFunction.apply(h, f, keep2, drop, p[14], p[15], eps2)
+
+
+def draw_stae_keep(num_layers: int, rows: int, model_dim: int, device, p: float) -> torch.Tensor:
+    """nn.Dropout(p) keep bits for STAEformer: int32 (4 * num_layers, rows, model_dim / 32), one site per dropout call -- the temporal
+    layers first, then the spatial ones, within a layer dropout1 before dropout2.  Bit j of word w keeps column 32w + j, every bit an
+    independent Bernoulli(1 - p) draw from torch's generator of ``device``.  The bits are packed bytewise and the bytes viewed as
+    int32, so the top bit of a word is as live as the others (see :func:`draw_stid_keep`)."""
+    weights = (2 ** torch.arange(8, device=device)).to(torch.uint8)
+    out = torch.empty(4 * num_layers, rows, model_dim // 32, dtype=torch.int32, device=device)
+    for site in range(4 * num_layers):                            # site by site: bounds the transient to 128 bytes per word
+        bits = torch.rand(rows, model_dim // 8, 8, device=device) >= p
+        out[site] = (bits.to(torch.uint8) * weights).sum(-1, dtype=torch.uint8).view(torch.int32)
+    return out
+
+
+class STAEformerTrainable(STAEformer):
+    """:class:`STAEformer`, TRAINABLE: the same constructor, limits, parameter creation order, state_dict and checkpoints, so a
+    checkpoint written here loads into :class:`STAEformer` (``evaluate --model STAEformer``) and back.
+
+    ``forward(x, *, keep=None)``.  Where nothing can ask for a gradient (``torch.no_grad()`` or no input requiring grad) and no dropout
+    is due (eval mode or ``dropout == 0``) it is the parent's one-call inference path, bit for bit.  Otherwise it composes the op-site
+    Functions: embedding, the temporal then the spatial layers (the layer body :class:`SelfAttentionLayer` runs), output projection;
+    every hot path is a HIP kernel and every parameter receives its gradient.  Dropout follows ``self.training``: a training-mode
+    call with ``dropout > 0`` draws fresh keep bits on the device (:func:`draw_stae_keep`) unless ``keep=`` supplies them -- int32
+    (4 * num_layers, B * in_steps * num_nodes, model_dim / 32) -- and leaves the bits it used in ``self.last_keep``; ``dropout == 0``
+    and eval mode ignore ``keep``.  The time-of-day / day-of-week indices are clamped into their tables, and a row's gradient goes
+    to the table row the forward read.
+
+    Kept per row and layer until the backward runs: 8 model_dim + feed_forward_dim floats (the layer's input, Q|K|V, the attention
+    output, out_proj's output, the first LayerNorm's output, the feed-forward hidden and output) plus num_heads floats of softmax
+    statistics, and, with dropout, 2 model_dim / 32 keep words."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.last_keep = None
+
+    def forward(self, x: torch.Tensor, *, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._check_x(x)
+        drop = self.training and self.dropout > 0
+        if not drop and not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            return super().forward(x)
+        b, t, n, d = x.shape[0], self.in_steps, self.num_nodes, self.model_dim
+        m = b * t * n
+        dims = self.dims(b, x.shape[3])
+        params = self.param_table()
+        ops.stae_check_tables(dims, x.device, params, "STAEformerTrainable")     # raw pointers: device, dtype, shape, layout
+        if drop:
+            shape = (4 * self.num_layers, m, d // 32)
+            if keep is None:
+                keep = draw_stae_keep(self.num_layers, m, d, x.device, self.dropout)
+            elif keep.dtype != torch.int32 or tuple(keep.shape) != shape or keep.device != x.device:
+                raise _lib.RegtError(f"keep must be an int32 {shape} tensor on {x.device}, got {keep.dtype} {tuple(keep.shape)} on {keep.device}")
+            self.last_keep = keep
+        else:
+            keep = None
+        rows = STAEEmbedFunction.apply(x.contiguous(), dims, *params[:6])
+        eps = float(self.attn_layers_t[0].ln1.eps)
+        for i, layer in enumerate(list(self.attn_layers_t) + list(self.attn_layers_s)):
+            k1, k2 = (None, None) if keep is None else (keep[2 * i].contiguous(), keep[2 * i + 1].contiguous())
+            rows = _stae_layer_rows(rows, layer.table(), b, t, n, self.num_heads, 1 if i < self.num_layers else 2, eps, eps, k1, k2,
+                                    self.dropout if drop else 0.0)
+        return STAEOutputProjFunction.apply(rows, dims, params[6], params[7])

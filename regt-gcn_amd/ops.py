@@ -734,3 +734,137 @@ def stae_add_layernorm_backward(residual: torch.Tensor, y: torch.Tensor, gamma: 
                                                     _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(scratch), _stream()),
                "regt_stae_add_layernorm_backward")
     return dz, dgamma, dbeta
+
+
+# ---- STAEformer training: the whole model (csrc/staeformer_train.hip) -------------------------------------------------------------------
+
+def _scratch(lib, name: str, device, *args) -> torch.Tensor:
+    n = getattr(lib, name)(*args)
+    if n == 0:
+        raise _lib.RegtError(f"{name}: " + lib.regt_last_error().decode("utf-8", "replace"))
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def _stae_x(dims: _lib.StaeDims, x: torch.Tensor) -> torch.Tensor:
+    x = _f32c(x, "x")
+    shape = (dims.batch, dims.in_steps, dims.num_nodes, dims.in_features)
+    if tuple(x.shape) != shape:
+        raise ValueError(f"x must be {shape}, got {tuple(x.shape)}")
+    return x
+
+
+def _stae_act(dims: _lib.StaeDims, t: torch.Tensor, name: str) -> torch.Tensor:
+    t = _f32c(t, name)
+    shape = (dims.batch * dims.in_steps * dims.num_nodes, stae_model_dim(dims))
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    return t
+
+
+def stae_embed(dims: _lib.StaeDims, x: torch.Tensor, params) -> torch.Tensor:
+    """Layer 0's input (M, model_dim) for x (B, T, N, F): input_proj | tod | dow | node_emb | adaptive_embedding, by the kernel
+    regt_stae_forward starts with.  ``params``: the first six entries of the parameter table (None where an embedding is off)."""
+    x = _stae_x(dims, x)
+    _check_table("regt_stae_embed", "parameter", params, stae_table_shapes(dims)[:6], x.device, "embedding width 0")
+    out = torch.empty(dims.batch * dims.in_steps * dims.num_nodes, stae_model_dim(dims), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().regt_stae_embed(ctypes.byref(dims), _lib.ptr(x), _ptr_table(list(params)), _lib.ptr(out), _stream()),
+               "regt_stae_embed")
+    return out
+
+
+def stae_embed_backward(dims: _lib.StaeDims, x: torch.Tensor, dx0: torch.Tensor):
+    """Gradients of :func:`stae_embed`'s six parameters given dL/dX0 (M, model_dim), in table order (None where an embedding is off).
+    A table row's gradient goes to the row the forward read after its clamp; x gets none."""
+    x, dx0 = _stae_x(dims, x), _stae_act(dims, dx0, "dx0")
+    lib = _lib.load()
+    scratch = _scratch(lib, "regt_stae_embed_backward_scratch_floats", x.device, ctypes.byref(dims))
+    grads = [None if s is None else torch.empty(s, dtype=torch.float32, device=x.device) for s in stae_table_shapes(dims)[:6]]
+    _lib.check(lib.regt_stae_embed_backward(ctypes.byref(dims), _lib.ptr(x), _lib.ptr(dx0), _ptr_table(grads), _lib.ptr(scratch), _stream()),
+               "regt_stae_embed_backward")
+    return grads
+
+
+def _stae_proj_params(dims: _lib.StaeDims, w: torch.Tensor, b: Optional[torch.Tensor], device):
+    shapes = stae_table_shapes(dims)[6:8]
+    _check_table("regt_stae_output_proj", "parameter", [w] if b is None else [w, b], shapes[:1] if b is None else shapes, device)
+
+
+def stae_output_proj(dims: _lib.StaeDims, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """out (B, out_steps, N, output_dim) of the use_mixed_proj tail for x (M, model_dim), by the kernel regt_stae_forward ends with."""
+    x = _stae_act(dims, x, "x")
+    _stae_proj_params(dims, w, b, x.device)
+    out = torch.empty(dims.batch, dims.out_steps, dims.num_nodes, dims.output_dim, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().regt_stae_output_proj(ctypes.byref(dims), _lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), _stream()),
+               "regt_stae_output_proj")
+    return out
+
+
+def stae_output_proj_backward(dims: _lib.StaeDims, x: torch.Tensor, w: torch.Tensor, dout: torch.Tensor, need_dx: bool = True):
+    """(dx, dw, db) of :func:`stae_output_proj` given dL/dout (B, out_steps, N, output_dim), read in place through its strides (a
+    strided window or an expanded tensor is fine); dx is None unless ``need_dx``."""
+    x = _stae_act(dims, x, "x")
+    _stae_proj_params(dims, w, None, x.device)
+    shape = (dims.batch, dims.out_steps, dims.num_nodes, dims.output_dim)
+    if not dout.is_cuda or dout.dtype != torch.float32:
+        raise _lib.RegtError("dout must be a float32 CUDA tensor (no CPU path)")
+    _check_dout(dout, shape, x.device)
+    if any(s < 0 for s in dout.stride()):
+        dout = dout.contiguous()
+    lib = _lib.load()
+    scratch = _scratch(lib, "regt_stae_output_proj_backward_scratch_floats", x.device, ctypes.byref(dims))
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(w)
+    db = torch.empty(w.shape[0], dtype=torch.float32, device=x.device)
+    _lib.check(lib.regt_stae_output_proj_backward(ctypes.byref(dims), _lib.ptr(x), _lib.ptr(w), _lib.ptr(dout), *dout.stride(), _lib.ptr(dx),
+                                                  _lib.ptr(dw), _lib.ptr(db), _lib.ptr(scratch), _stream()), "regt_stae_output_proj_backward")
+    return dx, dw, db
+
+
+def _stae_keep(keep: Optional[torch.Tensor], m: int, d: int, device, p: float) -> Optional[torch.Tensor]:
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"p must be in [0, 1), got {p}")
+    if keep is None:
+        return None
+    if keep.dtype != torch.int32 or tuple(keep.shape) != (m, d // 32) or keep.device != device or not keep.is_contiguous():
+        raise _lib.RegtError(f"keep must be a contiguous int32 ({m}, {d // 32}) tensor on {device}, got {keep.dtype} {tuple(keep.shape)} "
+                             f"on {keep.device}")
+    return keep
+
+
+def stae_drop_add_layernorm(residual: torch.Tensor, y: torch.Tensor, keep: Optional[torch.Tensor], p: float, gamma: torch.Tensor,
+                            beta: torch.Tensor, eps: float = STAE_LN_EPS) -> torch.Tensor:
+    """LayerNorm(residual + keep * y / (1 - p)) * gamma + beta over (M, D) rows; ``keep`` int32 (M, D / 32), bit j of word w keeps column
+    32 w + j.  ``keep=None``: no dropout and no scaling, the bits of :func:`stae_add_layernorm`."""
+    residual, y, gamma, beta = _f32c(residual, "residual"), _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta")
+    if residual.dim() != 2:
+        raise ValueError(f"residual must be (M, D), got {tuple(residual.shape)}")
+    m, d = residual.shape
+    if tuple(y.shape) != (m, d) or tuple(gamma.shape) != (d,) or tuple(beta.shape) != (d,):
+        raise ValueError(f"y must be ({m}, {d}) and gamma, beta ({d},)")
+    keep = _stae_keep(keep, m, d, residual.device, p)
+    out = torch.empty_like(residual)
+    _lib.check(_lib.load().regt_stae_drop_add_layernorm(_lib.ptr(residual), _lib.ptr(y), _lib.ptr(keep), p, _lib.ptr(gamma), _lib.ptr(beta), eps,
+                                                        m, d, _lib.ptr(out), _stream()), "regt_stae_drop_add_layernorm")
+    return out
+
+
+def stae_drop_add_layernorm_backward(residual: torch.Tensor, y: torch.Tensor, keep: Optional[torch.Tensor], p: float, gamma: torch.Tensor,
+                                     dout: torch.Tensor, eps: float = STAE_LN_EPS):
+    """(dz, dy, dgamma, dbeta) of :func:`stae_drop_add_layernorm` given dL/dout: dz (M, D) the gradient of residual, dy = keep * dz /
+    (1 - p) that of y, written in the same pass.  ``keep=None``: dy is dz itself."""
+    residual, y, gamma, dout = _f32c(residual, "residual"), _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(dout, "dout")
+    if residual.dim() != 2:
+        raise ValueError(f"residual must be (M, D), got {tuple(residual.shape)}")
+    m, d = residual.shape
+    if tuple(y.shape) != (m, d) or tuple(dout.shape) != (m, d) or tuple(gamma.shape) != (d,):
+        raise ValueError(f"y and dout must be ({m}, {d}) and gamma ({d},)")
+    keep = _stae_keep(keep, m, d, residual.device, p)
+    lib = _lib.load()
+    scratch = _scratch(lib, "regt_stae_drop_add_layernorm_backward_scratch_floats", residual.device, m, d)
+    dz = torch.empty_like(residual)
+    dy = None if keep is None else torch.empty_like(residual)
+    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+    _lib.check(lib.regt_stae_drop_add_layernorm_backward(_lib.ptr(residual), _lib.ptr(y), _lib.ptr(keep), p, _lib.ptr(gamma), _lib.ptr(dout), eps,
+                                                         m, d, _lib.ptr(dz), _lib.ptr(dy), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(scratch),
+                                                         _stream()), "regt_stae_drop_add_layernorm_backward")
+    return dz, (dz if keep is None else dy), dgamma, dbeta

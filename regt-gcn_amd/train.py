@@ -189,7 +189,8 @@ def split(xs, ys, ratio: float):
 # layers, run.py:117-118), STNorm (gated dilated convolutions with temporal / spatial normalisation, no graph, run.py:135-136) and
 # STID (a per-node MLP on the node's history and a learned node embedding, no graph, run.py:133-134) and StackedGRU (two GRU layers
 # whose sequence runs over the nodes, no graph, run.py:123-124); TemporalGConvLSTM (which run.py:122 cannot construct) is out of scope.  STAEformer
-# (run.py:131-132) runs for inference only (nn.STAEformer, evaluate.py --model STAEformer): training it is not offered here
+# (run.py:131-132) trains through its own command, ``python -m regtgcn_amd.train_staeformer`` (nn.STAEformerTrainable,
+# train_epoch_staeformer below), and is evaluated with evaluate.py --model STAEformer; this tuple and --model stay as they are
 MODELS = ("RegionalTemporalGCN", "RandomTemporalGCN", "TemporalGCN", "ConvStackedTemporalGCN", "GraphSAGETemporalGCN", "GAT", "GATTemporal",
           "SpatialGCN", "STNorm", "STID", "StackedGRU")
 
@@ -298,44 +299,76 @@ def evaluate_gru(model, store: "WindowStore", snap_batch: int) -> Tuple[float, f
     return _evaluate_windows(model, store, snap_batch, gru_batch, lambda x, y, i, b: _gru_last_rows(model(x), b) - y)
 
 
+# ---- STAEformer (run.py:131-132, 181-186, 217-222) ---------------------------------------------------------------------------------------
+# run.py feeds it what it feeds STNorm and STID, (1, T, N, F), and takes the same loss and metric; out is (1, O, N, output_dim = 1).  A
+# batch of B snapshots is B independent rows of one call.  Its own command is ``python -m regtgcn_amd.train_staeformer``.
+
+def staeformer_batch(store: "WindowStore", i: int, b: int):
+    """Snapshots i .. i+b-1 as STAEformer's input (b, T, N, F) and their targets (b, N, O)."""
+    return stnorm_batch(store, i, b)
+
+
+def train_epoch_staeformer(model, store: "WindowStore", optimizer, snap_batch: int,
+                           keeps: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """run.py::train() for nn.STAEformerTrainable; returns (last snapshot's loss, all per-snapshot losses).  ``keeps``: the dropout keep
+    bits of all snapshots, int32 (4 num_layers, len(store), T N, model_dim / 32), instead of a fresh draw per call."""
+    def losses_of(x, y, i, b):
+        keep = None if keeps is None else keeps[:, i:i + b].reshape(keeps.shape[0], -1, keeps.shape[-1])
+        return _window_losses(model(x, keep=keep), y)
+    return _train_epoch_windows(model, store, optimizer, snap_batch, staeformer_batch, losses_of)
+
+
+def evaluate_staeformer(model, store: "WindowStore", snap_batch: int) -> Tuple[float, float]:
+    """run.py::test() for STAEformer: (rmse, mse) of out[0][0] (N, output_dim) against y (N, O)."""
+    return _evaluate_windows(model, store, snap_batch, staeformer_batch, lambda x, y, i, b: model(x)[:, 0] - y)
+
+
+def add_flags(ap: argparse.ArgumentParser, only: Optional[Sequence[str]] = None) -> argparse.ArgumentParser:
+    """run.py's flags and this package's own, added to ``ap``; ``only``: the flags (by their first name) a command takes, the others
+    are left out.  One statement of every flag's names, default and help for train.py and train_staeformer.py."""
+    def add(*names, **kw):
+        if only is None or names[0] in only:
+            ap.add_argument(*names, **kw)
+    add("--seed", default=42, type=int)
+    add("--epochs", default=30, type=int)
+    add("--lr", default=1e-3, type=float)
+    add("--decay", default=1e-4, type=float)
+    add("--momentum", default=0.9, type=float, help="accepted, unused (as in run.py)")
+    add("--bs", "--batch_size", default=32, type=int, dest="bs", help="accepted, unused (as in run.py)")
+    add("--tr", "--train_ratio", default=0.8, type=float, dest="tr")
+    add("--tf", "--train_feature", default="available", type=str, dest="tf", help="occrate / available: the target column (run.py:31)")
+    add("--edge_cut", default=None, type=str, help="dataloading_type 1 only in run.py; accepted, unused")
+    add("--dataset_path", default=None, type=str, help="the reference's dataset/ directory (= --dataset_root)")
+    add("--checkpoint_path", default="../checkpoints/", type=str, help="accepted, unused (as in run.py)")
+    add("--dataloading_type", default=2, type=int, help="2 (TruckParkingDataset2 semantics) is what this loader implements")
+    add("--decomp_type", default=None, type=str, help="regional: the five state link files; random: run.py's random decomposition "
+                                                                  "(load_dataset.py:324-329) of the full graph into five overlapping parts")
+    add("--num_timesteps_in", default=8, type=int)
+    add("--num_timesteps_out", default=4, type=int)
+    add("--model", default="TemporalGCN", choices=list(MODELS))
+    add("--is_preprocessed", action="store_true", help="accepted: the data source decides (a .pkl / .npz is preprocessed by definition)")
+    add("--is_pretrained", action="store_true")
+    add("--pretrained_model", default="")
+    add("--pretrained_model_epoch", default="0")
+    add("--logs", action="store_true", help="also write the epoch lines to ./logs/<date>.txt (run.py:48-49)")
+    # this package's own flags
+    add("--fixture", help=".npz with node_data (N,F,steps), edge_index, edge_attr, edge_<R>_index/attr")
+    add("--dataset_root", help="the reference's dataset/ directory (read through regtgcn_amd.etl)")
+    add("--max_steps", type=int, default=None, help="with --dataset_root: use the first MAX_STEPS timesteps")
+    add("--out_dir", default="pretrained")
+    add("--loss_digits", default=4, type=int, help="decimals of the printed epoch line (run.py prints 4)")
+    add("--fused_step", action="store_true", help="train through functional.FusedTrainStep (no autograd; faster on small graphs)")
+    add("--snap_batch", type=int, default=1,
+                    help="snapshots per forward / backward (block-diagonal graph of B copies; same accumulated gradients and metrics, "
+                         "run.py:170-192 / 208-216 are additive over snapshots).  1 = one launch sequence per snapshot, as run.py")
+    return ap
+
+
 def build_parser() -> argparse.ArgumentParser:
     """run.py's flag set (run.py:22-45) -- the reference's own launch lines parse unchanged, e.g. scripts/RegionalTemporalGCN.sh:1 --
     plus this package's data-source flags.  Flags run.py parses and never reads (--momentum, --bs, --checkpoint_path: RMSprop is
     built from lr / decay only, run.py:145; snapshots are not batched, run.py:170) are accepted and ignored here too."""
-    ap = argparse.ArgumentParser(description="RegT-GCN training loop (reference run.py flags)")
-    ap.add_argument("--seed", default=42, type=int)
-    ap.add_argument("--epochs", default=30, type=int)
-    ap.add_argument("--lr", default=1e-3, type=float)
-    ap.add_argument("--decay", default=1e-4, type=float)
-    ap.add_argument("--momentum", default=0.9, type=float, help="accepted, unused (as in run.py)")
-    ap.add_argument("--bs", "--batch_size", default=32, type=int, dest="bs", help="accepted, unused (as in run.py)")
-    ap.add_argument("--tr", "--train_ratio", default=0.8, type=float, dest="tr")
-    ap.add_argument("--tf", "--train_feature", default="available", type=str, dest="tf", help="occrate / available: the target column (run.py:31)")
-    ap.add_argument("--edge_cut", default=None, type=str, help="dataloading_type 1 only in run.py; accepted, unused")
-    ap.add_argument("--dataset_path", default=None, type=str, help="the reference's dataset/ directory (= --dataset_root)")
-    ap.add_argument("--checkpoint_path", default="../checkpoints/", type=str, help="accepted, unused (as in run.py)")
-    ap.add_argument("--dataloading_type", default=2, type=int, help="2 (TruckParkingDataset2 semantics) is what this loader implements")
-    ap.add_argument("--decomp_type", default=None, type=str, help="regional: the five state link files; random: run.py's random decomposition "
-                                                                  "(load_dataset.py:324-329) of the full graph into five overlapping parts")
-    ap.add_argument("--num_timesteps_in", default=8, type=int)
-    ap.add_argument("--num_timesteps_out", default=4, type=int)
-    ap.add_argument("--model", default="TemporalGCN", choices=list(MODELS))
-    ap.add_argument("--is_preprocessed", action="store_true", help="accepted: the data source decides (a .pkl / .npz is preprocessed by definition)")
-    ap.add_argument("--is_pretrained", action="store_true")
-    ap.add_argument("--pretrained_model", default="")
-    ap.add_argument("--pretrained_model_epoch", default="0")
-    ap.add_argument("--logs", action="store_true", help="also write the epoch lines to ./logs/<date>.txt (run.py:48-49)")
-    # this package's own flags
-    ap.add_argument("--fixture", help=".npz with node_data (N,F,steps), edge_index, edge_attr, edge_<R>_index/attr")
-    ap.add_argument("--dataset_root", help="the reference's dataset/ directory (read through regtgcn_amd.etl)")
-    ap.add_argument("--max_steps", type=int, default=None, help="with --dataset_root: use the first MAX_STEPS timesteps")
-    ap.add_argument("--out_dir", default="pretrained")
-    ap.add_argument("--loss_digits", default=4, type=int, help="decimals of the printed epoch line (run.py prints 4)")
-    ap.add_argument("--fused_step", action="store_true", help="train through functional.FusedTrainStep (no autograd; faster on small graphs)")
-    ap.add_argument("--snap_batch", type=int, default=1,
-                    help="snapshots per forward / backward (block-diagonal graph of B copies; same accumulated gradients and metrics, "
-                         "run.py:170-192 / 208-216 are additive over snapshots).  1 = one launch sequence per snapshot, as run.py")
-    return ap
+    return add_flags(argparse.ArgumentParser(description="RegT-GCN training loop (reference run.py flags)"))
 
 
 def random_decomposition(edge_index: torch.Tensor, edge_attr: torch.Tensor, parts: int = 5, seed: int = 42):
@@ -353,10 +386,8 @@ def random_decomposition(edge_index: torch.Tensor, edge_attr: torch.Tensor, part
     return idx, att
 
 
-def main(argv=None):
-    a = build_parser().parse_args(argv)
-    torch.manual_seed(a.seed)
-    dev = torch.device("cuda:0")
+def load_windows(a, dev):
+    """The data source the flags name -> (its arrays, N, F, (train xs, ys), (test xs, ys)), windows on ``dev`` (run.py:60-75)."""
     if a.dataloading_type != 2:
         raise SystemExit("--dataloading_type 2 (TruckParkingDataset2: full graph + five regional graphs) is the loader this package implements")
     root = a.dataset_root or (a.dataset_path if a.dataset_path and os.path.isdir(os.path.join(a.dataset_path, "nodes")) else None)
@@ -373,7 +404,30 @@ def main(argv=None):
     n, f = node_data.shape[:2]
     xs, ys = snapshot_windows(node_data, a.num_timesteps_in, a.num_timesteps_out)
     xs, ys = [x.to(dev) for x in xs], [y.to(dev) for y in ys]
-    (tx, ty), (vx, vy) = split(xs, ys, a.tr)
+    return d, n, f, *split(xs, ys, a.tr)
+
+
+def make_optimizer(model, a):
+    return torch.optim.RMSprop(model.parameters(), lr=a.lr, weight_decay=a.decay)          # run.py:145
+
+
+def open_outputs(a, model_name: str):
+    """(checkpoint directory pretrained/<tf>/<model>/ of run.py:138, 243, the --logs file or None)."""
+    out_dir = os.path.join(a.out_dir, a.tf, model_name)
+    os.makedirs(out_dir, exist_ok=True)
+    log = None
+    if a.logs:
+        import datetime
+        os.makedirs("logs", exist_ok=True)
+        log = open(os.path.join("logs", datetime.datetime.now().strftime("%y-%m-%d_%H-%M") + ".txt"), "a")
+    return out_dir, log
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    torch.manual_seed(a.seed)
+    dev = torch.device("cuda:0")
+    d, n, f, (tx, ty), (vx, vy) = load_windows(a, dev)
     ei = torch.from_numpy(d["edge_index"]).to(dev)
     ea = torch.from_numpy(d["edge_attr"]).to(dev)
     if a.model in ("RegionalTemporalGCN", "RandomTemporalGCN"):             # run.py:115-116: one class for both decompositions
@@ -425,14 +479,8 @@ def main(argv=None):
         graph = model.prepare_graph(ei, n)
     if a.is_pretrained:
         model.load_state_dict(torch.load(a.pretrained_model, map_location=dev, weights_only=True))
-    opt = torch.optim.RMSprop(model.parameters(), lr=a.lr, weight_decay=a.decay)
-    out_dir = os.path.join(a.out_dir, a.tf, a.model)                         # run.py:138, 243: pretrained/<tf>/<model>/
-    os.makedirs(out_dir, exist_ok=True)
-    log = None
-    if a.logs:
-        import datetime
-        os.makedirs("logs", exist_ok=True)
-        log = open(os.path.join("logs", datetime.datetime.now().strftime("%y-%m-%d_%H-%M") + ".txt"), "a")
+    opt = make_optimizer(model, a)
+    out_dir, log = open_outputs(a, a.model)
     batched = None
     if a.model in ("STNorm", "STID", "StackedGRU"):
         from_store = (WindowStore(tx, ty), WindowStore(vx, vy))
