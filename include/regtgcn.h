@@ -302,6 +302,36 @@ int32_t regt_cell_backward(const regt_dims* dims, const regt_graph* graph, const
                            const float* h_in, float* dh_in, void* workspace, size_t workspace_bytes, regt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Streaming inference: the attention-weighted sum over a RING of cached per-time-step cell outputs, then the head.
+ *
+ * RegionalA3TGCN.forward / A3TGCN.forward call the cell with H = None in every period (models/RegionalTemporalGCN.py:134-146,
+ * models/TemporalGCN.py:84-90), so the cell's output S_s (N, C) of raw time step s does not depend on the window it is read through.
+ * S_s is what regt_forward returns as `hidden` for T = 1 with a ONE-element attention tensor (a single logit has probability exactly
+ * 1); REGT_DIMS_FORWARD_ONLY applies.  A caller keeps the last outputs in `ring` and replaces T - 1 of every window's T cell
+ * evaluations by reads:
+ *     hidden[w, n, c] = sum_{p < T} softmax(attention)_p * ring[(first_slot + w + p) % ring_len, n, c]        w < windows
+ *     pred[w]         = linear2(relu(linear1(relu(hidden[w]))))
+ * Layout: ring (ring_len, N, C) fp32 contiguous, slab s = the cell output of one time step; window w covers slots first_slot + w ..
+ * first_slot + w + T - 1, modulo ring_len; pred (windows, N, O), hidden (windows, N, C); attention (T) are the model's logits, the
+ * head tensors are regt_params' head1_w/b, head2_w/b.  ring, hidden and workspace 16-byte aligned.
+ * Order: every element of hidden is accumulated p = 0, 1, .., T - 1 with one fused multiply-add each, starting from 0: a window's
+ * hidden (and pred) is the same bits for every windows, first_slot, ring_len it is computed with.  Slabs outside the
+ * windows + T - 1 slots named above are not read.  The head runs in the process arithmetic (regt_set_gemm_mode).
+ * Limits: C % 4 == 0, 1 <= T <= 255, windows * N < 2^31, windows <= 65535 * regt_window_chunk(2) (= 1 048 560).
+ * Refused before anything is launched (message in regt_last_error): a NULL pointer; ring_len < T; first_slot outside [0, ring_len);
+ * windows > 1 with windows + T - 1 > ring_len (the windows would wrap onto themselves; a single window may start anywhere); C % 4 != 0;
+ * T > 255; a limit above exceeded; workspace_bytes below regt_window_workspace_bytes(N, C, H1, O, windows) (0 = refused dimensions).
+ * regt_window_chunk(windows): how many windows one thread of the kernel accumulates at once for a call of `windows` windows (1 for a
+ * single window, the chunk width WC otherwise): a chunk of nw <= WC windows reads nw + T - 1 slabs and writes nw.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t regt_window_chunk(int32_t windows);
+size_t regt_window_workspace_bytes(int32_t N, int32_t C, int32_t H1, int32_t O, int32_t windows);
+int32_t regt_window_forward(const float* ring, int32_t ring_len, int32_t first_slot, int32_t windows, int32_t N, int32_t T,
+                            int32_t C, int32_t O, int32_t H1, const float* attention, const float* head1_w, const float* head1_b,
+                            const float* head2_w, const float* head2_b, float* pred, float* hidden, void* workspace,
+                            size_t workspace_bytes, regt_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Zero-hidden TGCN cell + attention over periods + head, on gate inputs the CALLER aggregated.
  *
  * The reference's GraphSAGETemporalGCN and GATTemporal call `self._base_tgcn(X[:, :, period], edge_index, H)`
@@ -567,6 +597,8 @@ int32_t regt_relu_backward(const float* y, float* d, int64_t n, regt_stream_t st
  * accumulation -- fp32-level rounding error (dropped terms <= 3 * 2^-24 of a product), ~2x the matrix-pipe rate.
  * Also selectable with REGT_GEMM_MODE=bf16x3 before the first call.  Returns the previous mode. */
 int32_t regt_set_gemm_mode(int32_t mode);
+/* The current mode, read only (what regt_set_gemm_mode would return, without setting anything). */
+int32_t regt_gemm_mode(void);
 
 /* Developer switches (A/B timing and the bit-for-bit comparisons of tests/test_gpu_fused.py): stores the value as the switch
  * normalises it and returns the previous value; -1 for an unknown name.  Host state only (one table, csrc/options.hip); the five

@@ -103,6 +103,7 @@ class Cell0Grads(C.Structure):
 SIGNATURES = {
     "regt_abi_version": (C.c_int32, []),
     "regt_set_gemm_mode": (C.c_int32, [C.c_int32]),
+    "regt_gemm_mode": (C.c_int32, []),
     "regt_set_option": (C.c_int32, [C.c_char_p, C.c_int32]),
     "regt_cell_forward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "regt_cell_backward": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
@@ -134,6 +135,9 @@ SIGNATURES = {
                                         C.c_size_t, vp]),
     "regt_backward": (C.c_int32, [C.POINTER(Dims), C.POINTER(Graph), C.POINTER(Params), C.POINTER(Grads), vp, vp, vp,
                                   vp, vp, C.c_size_t, vp]),
+    "regt_window_chunk": (C.c_int32, [C.c_int32]),
+    "regt_window_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "regt_window_forward": (C.c_int32, [vp] + [C.c_int32] * 8 + [vp] * 8 + [C.c_size_t, vp]),
     "regt_mean_csr": (C.c_int32, [vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "regt_cell0_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.c_int32, C.c_int32]),
     "regt_cell0_forward": (C.c_int32, [C.POINTER(Dims), C.POINTER(Cell0Args), vp, vp, vp, C.c_size_t, vp]),
@@ -209,6 +213,11 @@ def check(rc: int, what: str):
     if rc != 0:
         msg = load().regt_last_error().decode("utf-8", "replace")
         raise RegtError(f"{what} failed (code {rc}): {msg}")
+
+
+def gemm_mode() -> int:
+    """The process default GEMM arithmetic (0 fp32, 1 bf16x3, 2 bf16); reads only."""
+    return load().regt_gemm_mode()
 
 
 def ptr(t):

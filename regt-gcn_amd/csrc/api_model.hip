@@ -187,4 +187,57 @@ int32_t regt_cell_backward(const regt_dims* dims, const regt_graph* graph, const
     return backward_impl(*dims, *graph, *params, *grads, dpred, dhidden, hidden, nullptr, L, (hipStream_t)st, qbf, h_in, dh_in);
 }
 
+/* ---- streaming inference: attention-weighted window sum over cached cell outputs + head (regtgcn.h) ---- */
+// workspace: the T attention probabilities (a fixed 255-float region: the size does not depend on T), then the head's (rows x H1) activation
+static const size_t WINDOW_PROBS_BYTES = 1024;
+static size_t window_ws_bytes(long rows, int H1) { return WINDOW_PROBS_BYTES + (((size_t)rows * H1 * sizeof(float) + 255) & ~(size_t)255); }
+
+int32_t regt_window_chunk(int32_t windows) { return window_chunk(windows); }
+
+size_t regt_window_workspace_bytes(int32_t N, int32_t C, int32_t H1, int32_t O, int32_t windows) {
+    if (!(N > 0 && C > 0 && H1 > 0 && O > 0 && windows > 0 && (long)N * windows <= INT_MAX)) {
+        set_error("regt_window_workspace_bytes: N, C, H1, O, windows must be positive and windows * N below 2^31 (N=%d C=%d H1=%d O=%d windows=%d)",
+                  N, C, H1, O, windows);
+        return 0;
+    }
+    return window_ws_bytes((long)N * windows, H1);
+}
+
+int32_t regt_window_forward(const float* ring, int32_t ring_len, int32_t first_slot, int32_t windows, int32_t N, int32_t T, int32_t C,
+                            int32_t O, int32_t H1, const float* attention, const float* head1_w, const float* head1_b,
+                            const float* head2_w, const float* head2_b, float* pred, float* hidden, void* ws, size_t ws_bytes,
+                            regt_stream_t st) {
+    REGT_CHECK_ARG(ring && attention && head1_w && head1_b && head2_w && head2_b && pred && hidden && ws, "regt_window_forward: NULL pointer");
+    REGT_CHECK_ARG(N > 0 && C > 0 && O > 0 && H1 > 0 && T > 0 && windows > 0 && ring_len > 0,
+                   "regt_window_forward: ring_len, windows, N, T, C, O, H1 must be positive (ring_len=%d windows=%d N=%d T=%d C=%d O=%d H1=%d)",
+                   ring_len, windows, N, T, C, O, H1);
+    REGT_CHECK_ARG(C % 4 == 0, "regt_window_forward: C=%d must be a multiple of 4", C);
+    REGT_CHECK_ARG(T <= 255, "regt_window_forward: T=%d exceeds 255 periods", T);
+    REGT_CHECK_ARG(ring_len >= T, "regt_window_forward: ring_len=%d < T=%d", ring_len, T);
+    REGT_CHECK_ARG(first_slot >= 0 && first_slot < ring_len, "regt_window_forward: first_slot=%d outside [0, ring_len=%d)", first_slot, ring_len);
+    REGT_CHECK_ARG(windows == 1 || (long)windows + T - 1 <= ring_len,
+                   "regt_window_forward: windows=%d of T=%d periods would wrap onto themselves in a ring of %d slots (only a single window may use all of it)",
+                   windows, T, ring_len);
+    REGT_CHECK_ARG((long)N * windows <= INT_MAX, "regt_window_forward: windows * N too large");
+    REGT_CHECK_ARG(windows <= WINDOW_MAX_CHUNKS * WINDOW_WC, "regt_window_forward: windows=%d exceeds the %d one call covers", windows,
+                   WINDOW_MAX_CHUNKS * WINDOW_WC);
+    REGT_CHECK_ARG(al16(ring) && al16(hidden) && al16(ws), "regt_window_forward: ring, hidden and workspace must be 16-byte aligned");
+    const size_t need = window_ws_bytes((long)N * windows, H1);
+    REGT_CHECK_ARG(ws_bytes >= need, "regt_window_forward: workspace %zu < required %zu bytes (regt_window_workspace_bytes)", ws_bytes, need);
+    hipStream_t hs = (hipStream_t)st;
+    float* probs = static_cast<float*>(ws);
+    float* y1 = reinterpret_cast<float*>(static_cast<char*>(ws) + WINDOW_PROBS_BYTES);
+    {
+        PROF("window_sum", hs);
+        TRY(launch_softmax_small(attention, probs, T, hs));      // the launch regt_forward's own attention weights come from
+        TRY(launch_window_sum(ring, probs, hidden, ring_len, first_slot, windows, N, T, C, hs));
+    }
+    // the head of regt_forward's tail, on windows * N rows
+    regt_dims d{};
+    d.N = N * windows; d.T = T; d.C = C; d.O = O; d.H1 = H1;
+    regt_params p{};
+    p.head1_w = head1_w; p.head1_b = head1_b; p.head2_w = head2_w; p.head2_b = head2_b;
+    return head_forward(d, p, hidden, y1, pred, hs);
+}
+
 }  // extern "C"

@@ -197,6 +197,7 @@ int32_t regt_set_gemm_mode(int32_t mode) {
     set_option(OPT_GEMM_MODE, mode);
     return prev;
 }
+int32_t regt_gemm_mode(void) { return gemm_mode(); }      // (as the calling thread sees it; reads only)
 const char* regt_last_error(void) { return g_err; }
 
 int32_t regt_set_option(const char* name, int32_t value) {

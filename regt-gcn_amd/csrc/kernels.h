@@ -342,6 +342,14 @@ int launch_head2_wgrad(const float* dpred, const float* y1, float* slab, int N, 
 // S[i, j] = sum_r W[i, r*C + j]: the sum of the R (C x C) blocks of tgnn.linear.weight (cell.hip)
 int launch_sum_region_blocks(const float* W, float* S, int C, int R, hipStream_t st);
 int launch_softmax_small(const float* att, float* probs, int T, hipStream_t st);
+// attention-weighted window sum over a ring of per-time-step cell outputs (window.hip): hidden[w] = sum_p probs[p] ring[(first_slot + w + p)
+// % ring_len], every element in the order p = 0 .. T - 1 with fmaf from 0.  windows == 1 reads T slabs; more run in chunks of WINDOW_WC
+// windows per thread, WINDOW_WC + T - 1 slab reads per chunk.
+constexpr int WINDOW_WC = 16;
+constexpr int WINDOW_MAX_CHUNKS = 65535;      // chunks of one launch (grid.y): the entry point refuses more windows than that covers
+int window_chunk(int windows);      // windows a thread accumulates at once: 1 or WINDOW_WC (regt_window_chunk hands it to tools and tests)
+int launch_window_sum(const float* ring, const float* probs, float* hidden, int ring_len, int first_slot, int windows, int N, int T, int C,
+                      hipStream_t st);
 struct CellBwdArgs {
     const float* dOH; const float* probs; const float* ZR; const float* h; const float* Ht;
     float* dhp; float* dzr; float* dp_partial; int num_nodes, T, C; int nodes_per_block;

@@ -16,7 +16,7 @@ import torch
 
 from . import nn as rnn
 from .data import snapshot_windows
-from .train import REGIONS, split
+from .train import REGIONS, split, streamed_split
 
 
 @torch.no_grad()
@@ -62,6 +62,35 @@ def predict_metrics_batched(model, store, graphs, snap_batch: int) -> Tuple[floa
         ape_n += ok.sum() * per
     n = float(store.Y.numel())
     return float(ae) / n, (float(se) / n) ** 0.5, (float(ape) / float(ape_n) * 100 if float(ape_n) else float("nan"))
+
+
+@torch.no_grad()
+def predict_metrics_streamed(model, node_data: torch.Tensor, t_in: int, t_out: int, build_graph, first: int, count: int,
+                             step_batch: int = 64) -> Tuple[float, float, float]:
+    """predict_metrics() over the ``count`` windows ``first .. first + count - 1`` of ``node_data`` (N, F, steps) as loaded, with every
+    raw time step's cell output computed once (serve.window_outputs): about 1 / t_in of the GEMM work, and no WindowStore -- the data
+    is held once, not t_in times.  ``build_graph(b)``: the model's graph prepared with ``copies=b``.  RegionalTemporalGCN / TemporalGCN,
+    fp32-storage arithmetics."""
+    from .serve import window_outputs
+    model.eval()
+    if first + count + t_in + t_out - 1 > node_data.shape[2]:
+        raise ValueError(f"window {first + count - 1} has no {t_out}-step target inside {node_data.shape[2]} time steps")
+    ae, se, ape = [], [], []
+    for i, out, _ in window_outputs(model, node_data, t_in, build_graph, first, count, step_batch):
+        b = out.shape[0]
+        y = torch.stack([node_data[:, -1, k + t_in:k + t_in + t_out] for k in range(i, i + b)]).to(out.device, torch.float32)
+        d = (y - out).abs()
+        ae.append(d.flatten(0, 1))
+        se.append(((y - out) ** 2).flatten(0, 1))
+        q = torch.quantile(y.flatten(1).double(), 0.95, dim=1).to(d.dtype)         # per snapshot, as predict_metrics
+        r = d / q.view(b, 1, 1)
+        ok = ~torch.isinf(r).flatten(1).any(dim=1)
+        ape.append(r[ok].flatten(0, 1))
+    mae = float(torch.cat(ae, dim=0).mean())
+    rmse = float(torch.cat(se, dim=0).mean().sqrt())
+    ape = torch.cat(ape, dim=0)
+    mape = float(ape.mean()) * 100 if ape.numel() else float("nan")
+    return mae, rmse, mape
 
 
 def load_processed_pickle(path: str) -> Dict[str, torch.Tensor]:
@@ -143,11 +172,17 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num_timesteps_out", default=1, type=int)
     ap.add_argument("--tr", "--train_ratio", default=0.2, type=float, dest="tr")
     ap.add_argument("--snap_batch", type=int, default=1, help="test snapshots per forward (block-diagonal graph of B copies; same metrics)")
+    ap.add_argument("--streamed", action="store_true",
+                    help="RegionalTemporalGCN / TemporalGCN: compute every time step's cell output once and form the windows from the cached "
+                         "outputs (predict_metrics_streamed; same metrics, about 1 / num_timesteps_in of the GEMM work)")
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    if a.streamed:
+        from .serve import refuse_streamed
+        refuse_streamed(a.model)
     if a.pickle:
         d = load_processed_pickle(a.pickle)
     elif a.fixture:
@@ -157,8 +192,12 @@ def main(argv=None):
         raise SystemExit("give --fixture or --pickle")
     dev = torch.device("cuda:0")
     n, f = d["node_data"].shape[:2]
-    xs, ys = snapshot_windows(d["node_data"], a.num_timesteps_in, a.num_timesteps_out)
-    _, (vx, vy) = split([x.to(dev) for x in xs], [y.to(dev) for y in ys], a.tr)
+    if a.streamed:                                            # no window is built: the test split is a range of window numbers
+        first, count = streamed_split(d["node_data"].shape[2], a.num_timesteps_in, a.num_timesteps_out, a.tr)
+        vx = vy = None
+    else:
+        xs, ys = snapshot_windows(d["node_data"], a.num_timesteps_in, a.num_timesteps_out)
+        _, (vx, vy) = split([x.to(dev) for x in xs], [y.to(dev) for y in ys], a.tr)
     if a.model == "STNorm":                                   # predict.py:134-135, 173-180
         model = rnn.STNorm(num_nodes=n, in_dim=f, out_dim=a.num_timesteps_out).to(dev)
         model.load_state_dict(torch.load(a.checkpoint, map_location=dev, weights_only=True))
@@ -196,7 +235,14 @@ def main(argv=None):
         model = rnn.TemporalGCN(f, a.num_timesteps_in, a.num_timesteps_out).to(dev)
         graph = model.prepare_graph(d["edge_index"].to(dev), d["edge_attr"].to(dev), n)
     model.load_state_dict(torch.load(a.checkpoint, map_location=dev, weights_only=True))
-    if a.snap_batch > 1:
+    if a.streamed:
+        if a.model == "RegionalTemporalGCN":
+            idx, att = [d[f"edge_{r}_index"].to(dev) for r in REGIONS], [d[f"edge_{r}_attr"].to(dev) for r in REGIONS]
+            build = lambda b: model.prepare_graph(d["edge_index"].to(dev), idx, att, copies=b)      # noqa: E731
+        else:
+            build = lambda b: model.prepare_graph(d["edge_index"].to(dev), d["edge_attr"].to(dev), n, copies=b)      # noqa: E731
+        mae, rmse, mape = predict_metrics_streamed(model, d["node_data"], a.num_timesteps_in, a.num_timesteps_out, build, first, count)
+    elif a.snap_batch > 1:
         from .train import BatchedGraphs, WindowStore
         if a.model == "RegionalTemporalGCN":
             idx, att = [d[f"edge_{r}_index"].to(dev) for r in REGIONS], [d[f"edge_{r}_attr"].to(dev) for r in REGIONS]

@@ -215,9 +215,11 @@ class _FwdState:
             setattr(self, k, v)
 
 
-def _regt_forward_call(x: torch.Tensor, graph: PreparedGraph, regional: bool, slope: float, packed, params, forward_only: bool):
+def _regt_forward_call(x: torch.Tensor, graph: PreparedGraph, regional: bool, slope: float, packed, params, forward_only: bool,
+                       hidden_out: Optional[torch.Tensor] = None):
     """The library call behind :class:`RegTGCNFunction` and :func:`regt_run`: returns ``(pred, hidden, state)``; ``state`` is
-    None for a forward-only call (its workspace block is back in the pool)."""
+    None for a forward-only call (its workspace block is back in the pool).  ``hidden_out``: a contiguous float32 (N, C) tensor the
+    library writes ``hidden`` into instead of a fresh one (a ring slab of serve.StreamingPredictor)."""
     arith = flags = 0
     if isinstance(packed, tuple):
         packed, arith, flags = packed
@@ -293,7 +295,13 @@ def _regt_forward_call(x: torch.Tensor, graph: PreparedGraph, regional: bool, sl
     handle = _WsHandle(wsb, x.device)
     ws = handle.ws
     pred = torch.empty(N, O, dtype=torch.float32, device=x.device)
-    hidden = torch.empty(N, Cdim, dtype=torch.float32, device=x.device)
+    if hidden_out is None:
+        hidden = torch.empty(N, Cdim, dtype=torch.float32, device=x.device)
+    else:
+        if (hidden_out.dtype != torch.float32 or hidden_out.device != x.device or tuple(hidden_out.shape) != (N, Cdim)
+                or not hidden_out.is_contiguous() or hidden_out.data_ptr() % 16):
+            raise ValueError(f"hidden_out must be a contiguous, 16-byte aligned float32 ({N}, {Cdim}) tensor on {x.device}")
+        hidden = hidden_out
     if xbf:
         _lib.check(lib.regt_forward_packed_bf16(C.byref(dims), C.byref(gs), C.byref(ps), _lib.ptr(x), x_rows, _lib.ptr(pred),
                                                 _lib.ptr(hidden), _lib.ptr(ws), wsb, _stream()), "regt_forward_packed_bf16")

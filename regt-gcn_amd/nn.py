@@ -32,7 +32,8 @@ from . import _lib
 from . import ops
 from .functional import (HEAD_HIDDEN, PARAM_NAMES_CELL, AggregateFunction, Cell0Function, CellFunction, GatAggregateFunction,
                          GRUFunction, LinearFunction, MLPHeadFunction, RegTGCNFunction, SpatialEmbedFunction, STAEAddLayerNormFunction,
-                         STAEDropAddLayerNormFunction, STAEEmbedFunction, STAEOutputProjFunction, STAEPackedAttentionFunction, STIDFunction, STNormFunction, ZeroGradAnchor, cell_run, param_names, regt_run)
+                         STAEDropAddLayerNormFunction, STAEEmbedFunction, STAEOutputProjFunction, STAEPackedAttentionFunction, STIDFunction, STNormFunction, ZeroGradAnchor, _regt_forward_call, cell_run, param_names,
+                         regt_run)
 from .graph import (AttentionPattern, GcnOperator, MeanOperator, PreparedGraph, fingerprint, prepare_attention_pattern,
                     prepare_cheb_operator, prepare_gcn_operator, prepare_graph, prepare_mean_operator)
 
@@ -223,6 +224,35 @@ class _FusedModel(nn.Module):
         # before apply: inside Function.forward grad mode is always off)
         return regt_run(x, graph, self.regional, LEAKY_SLOPE, (packed, arith, flags) if (arith or flags) else packed,
                         *self._params_in_order())
+
+    @torch.no_grad()
+    def period_outputs(self, x_steps: torch.Tensor, graph: PreparedGraph, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The cell's output S (B, N, C) of B raw time steps ``x_steps`` (B, N, F); ``graph`` prepared with ``copies=B`` (a plain prepared
+        graph for B = 1).  The reference calls the cell with H = None in every period, so S of a time step does not depend on the window
+        it is read through: ``hidden(window i) = sum_p softmax(_attention)_p S_{i+p}`` (serve.StreamingPredictor, ops.window_forward).
+        One forward-only library call at T = 1 on (B N, F, 1) with a one-element attention tensor in place of ``_attention``: a single
+        logit has probability exactly 1, so that call's ``hidden`` IS the cell output (its ``pred`` is dropped).  Never differentiable.
+        ``out``: a contiguous float32 (B, N, C) tensor the library writes S into (a ring slab, a stretch of a timeline) and that is
+        returned, instead of a fresh one.
+        fp32-storage arithmetics only ("fp32", "bf16x3")."""
+        _need_cuda(x_steps)
+        if x_steps.dim() != 3 or x_steps.dtype != torch.float32:
+            raise ValueError(f"x_steps must be float32 (B, N, F), got {x_steps.dtype} {tuple(x_steps.shape)}")
+        arith = _lib.arith_code(self.arithmetic)
+        if arith == _lib.ARITH_BF16 or (arith == _lib.ARITH_DEFAULT and _lib.gemm_mode() == 2):
+            raise NotImplementedError("period_outputs / streaming inference covers the fp32-storage arithmetics (fp32, bf16x3); the bf16 "
+                                      "arithmetic rounds per window and is out of scope (DESIGN.md 4b)")
+        b, n, f = x_steps.shape
+        if b * n != graph.num_nodes:
+            raise ValueError(f"x_steps holds {b} steps of {n} nodes but the prepared graph has {graph.num_nodes} nodes (prepare it with copies={b})")
+        params = [p.detach() for p in self._params_in_order()]
+        params[0] = params[0].new_zeros(1)                     # tgnn._attention -> one logit: softmax = [1.0]
+        flags = int(self.call_flags)
+        if out is not None and (out.dim() != 3 or tuple(out.shape[:2]) != (b, n) or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous ({b}, {n}, C) tensor, got {tuple(out.shape)} strides {out.stride()}")
+        _, s, _ = _regt_forward_call(x_steps.reshape(b * n, f, 1), graph, self.regional, LEAKY_SLOPE, (False, arith, flags), params, True,
+                                     hidden_out=None if out is None else out.view(b * n, out.shape[2]))
+        return s.view(b, n, -1) if out is None else out
 
     def forward_packed(self, x_packed_ext: torch.Tensor, graph: PreparedGraph):
         """Region-sharded entry: ``x_packed_ext`` (x_rows, T, F) = own packed rows + gathered halo rows (dist.py)."""

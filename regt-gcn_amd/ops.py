@@ -123,6 +123,59 @@ def mse_loss_grad(pred: torch.Tensor, y: torch.Tensor, global_count: Optional[in
     return loss, dpred
 
 
+WINDOW_MAX_T = 255
+
+
+def window_forward(ring: torch.Tensor, first_slot: int, windows: int, attention: torch.Tensor, l1w: torch.Tensor, l1b: torch.Tensor,
+                   l2w: torch.Tensor, l2b: torch.Tensor, pred: Optional[torch.Tensor] = None, hidden: Optional[torch.Tensor] = None):
+    """Streaming inference (regt_window_forward): ``ring`` (ring_len, N, C) holds per-time-step cell outputs; window w < ``windows`` is
+    ``hidden[w] = sum_p softmax(attention)_p * ring[(first_slot + w + p) % ring_len]`` (p ascending, one fmaf each: the same bits
+    whatever ``windows`` / ``first_slot`` / ``ring_len``), ``pred[w]`` the head on it.  Returns ``(pred (windows, N, O), hidden
+    (windows, N, C))``; ``pred`` / ``hidden``: contiguous float32 outputs of those shapes to write into, allocated when None.
+    ``ring`` must be contiguous (it is not copied); more than one window needs ``windows + T - 1 <= ring_len``."""
+    tensors = {"ring": ring, "attention": attention, "l1w": l1w, "l1b": l1b, "l2w": l2w, "l2b": l2b}
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise _lib.RegtError(f"{name} must be a float32 CUDA tensor (no CPU path)")
+    if ring.dim() != 3 or not ring.is_contiguous():
+        raise ValueError(f"ring must be a contiguous (ring_len, N, C) tensor, got {tuple(ring.shape)} strides {ring.stride()}")
+    ring_len, n, c = ring.shape
+    if attention.dim() != 1 or not 1 <= attention.numel() <= WINDOW_MAX_T:
+        raise ValueError(f"attention must hold 1 .. {WINDOW_MAX_T} logits, got {tuple(attention.shape)}")
+    t = attention.numel()
+    if l1w.dim() != 2 or l1w.shape[1] != c or l2w.dim() != 2 or l2w.shape[1] != l1w.shape[0]:
+        raise ValueError(f"l1w must be (H1, {c}) and l2w (O, H1), got {tuple(l1w.shape)} and {tuple(l2w.shape)}")
+    h1, o = l1w.shape[0], l2w.shape[0]
+    if tuple(l1b.shape) != (h1,) or tuple(l2b.shape) != (o,):
+        raise ValueError(f"l1b must be ({h1},) and l2b ({o},), got {tuple(l1b.shape)} and {tuple(l2b.shape)}")
+    first_slot, windows = int(first_slot), int(windows)
+    if n < 1 or c < 4 or c % 4:
+        raise ValueError(f"ring needs N >= 1 and C a positive multiple of 4, got N={n} C={c}")
+    if ring_len < t or not 0 <= first_slot < ring_len or windows < 1:
+        raise ValueError(f"need ring_len >= T, 0 <= first_slot < ring_len and windows >= 1 (ring_len={ring_len} T={t} first_slot={first_slot} "
+                         f"windows={windows})")
+    if windows > 1 and windows + t - 1 > ring_len:
+        raise ValueError(f"{windows} windows of {t} periods need {windows + t - 1} slots, the ring has {ring_len} (only a single window may wrap)")
+    attention, l1w, l1b, l2w, l2b = (x.detach().contiguous() for x in (attention, l1w, l1b, l2w, l2b))
+    for name, out, shape in (("pred", pred, (windows, n, o)), ("hidden", hidden, (windows, n, c))):
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != ring.device
+                                or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 {shape} tensor on {ring.device}")
+    if pred is None:
+        pred = torch.empty(windows, n, o, dtype=torch.float32, device=ring.device)
+    if hidden is None:
+        hidden = torch.empty(windows, n, c, dtype=torch.float32, device=ring.device)
+    lib = _lib.load()
+    nbytes = lib.regt_window_workspace_bytes(n, c, h1, o, windows)
+    if nbytes == 0:
+        _lib.check(1, "regt_window_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=ring.device)
+    _lib.check(lib.regt_window_forward(_lib.ptr(ring), ring_len, first_slot, windows, n, t, c, o, h1, _lib.ptr(attention), _lib.ptr(l1w),
+                                       _lib.ptr(l1b), _lib.ptr(l2w), _lib.ptr(l2b), _lib.ptr(pred), _lib.ptr(hidden), _lib.ptr(ws), nbytes,
+                                       _stream()), "regt_window_forward")
+    return pred, hidden
+
+
 def gat_forward(rowptr: torch.Tensor, col: torch.Tensor, xp: torch.Tensor, u_src: torch.Tensor, u_dst: torch.Tensor, slope: float = 0.2):
     """GATConv attention aggregation on packed input rows xp (N,T,F): returns (out (N,T,F), stats (N*T,4))."""
     xp, u_src, u_dst = _f32c(xp, "xp"), _f32c(u_src, "u_src"), _f32c(u_dst, "u_dst")

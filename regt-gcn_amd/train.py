@@ -180,6 +180,31 @@ def evaluate_sharded(model, xs, ys, shard: Shard, pipe: HaloPipeline, global_nod
     return float(m.sqrt()), float(m)
 
 
+@torch.no_grad()
+def evaluate_streamed(model, node_data: torch.Tensor, t_in: int, t_out: int, build_graph, first: int, count: int,
+                      step_batch: int = 64) -> Tuple[float, float]:
+    """run.py::test() over the windows ``first .. first + count - 1`` of ``node_data`` (N, F, steps) as loaded: the (rmse, mse) of
+    evaluate(), with every raw time step's cell output computed once and shared by the t_in windows that contain it
+    (serve.window_outputs).  ``build_graph(b)``: the model's graph prepared with ``copies=b``.  RegionalTemporalGCN / TemporalGCN."""
+    from .serve import window_outputs
+    model.eval()
+    if first + count + t_in + t_out - 1 > node_data.shape[2]:
+        raise ValueError(f"window {first + count - 1} has no {t_out}-step target inside {node_data.shape[2]} time steps")
+    se = []
+    for i, out, _ in window_outputs(model, node_data, t_in, build_graph, first, count, step_batch):
+        y = torch.stack([node_data[:, -1, k + t_in:k + t_in + t_out] for k in range(i, i + out.shape[0])]).to(out.device, torch.float32)
+        se.append(((out - y) ** 2).flatten(0, 1))
+    m = torch.cat(se, dim=0).mean()
+    return float(m.sqrt()), float(m)
+
+
+def streamed_split(steps: int, t_in: int, t_out: int, ratio: float) -> Tuple[int, int]:
+    """(first window, window count) of the test split that split() cuts from snapshot_windows()' list, from the step count alone."""
+    windows = max(steps - (t_in + t_out) + 1, 0)
+    k = int(ratio * windows)
+    return k, windows - k
+
+
 def split(xs, ys, ratio: float):
     k = int(ratio * len(xs))          # temporal_signal_split: first int(ratio*n) snapshots train, rest test
     return (xs[:k], ys[:k]), (xs[k:], ys[k:])
@@ -361,6 +386,9 @@ def add_flags(ap: argparse.ArgumentParser, only: Optional[Sequence[str]] = None)
     add("--snap_batch", type=int, default=1,
                     help="snapshots per forward / backward (block-diagonal graph of B copies; same accumulated gradients and metrics, "
                          "run.py:170-192 / 208-216 are additive over snapshots).  1 = one launch sequence per snapshot, as run.py")
+    add("--streamed", action="store_true",
+        help="RegionalTemporalGCN / RandomTemporalGCN / TemporalGCN: the per-epoch test pass computes every time step's cell output once "
+             "and forms the windows from the cached outputs (evaluate_streamed; same metrics)")
     return ap
 
 
@@ -402,6 +430,12 @@ def load_windows(a, dev):
         raise SystemExit("give --fixture, --dataset_root or a --dataset_path that holds the reference's dataset/ directory")
     node_data = torch.from_numpy(d["node_data"])
     n, f = node_data.shape[:2]
+    if getattr(a, "streamed", False):
+        # the test pass reads node_data as loaded (evaluate_streamed): only the train split's windows are built and moved
+        k, _ = streamed_split(node_data.shape[2], a.num_timesteps_in, a.num_timesteps_out, a.tr)
+        xs, ys = snapshot_windows(node_data[:, :, :k + a.num_timesteps_in + a.num_timesteps_out - 1] if k else node_data[:, :, :0],
+                                  a.num_timesteps_in, a.num_timesteps_out)
+        return d, n, f, ([x.to(dev) for x in xs], [y.to(dev) for y in ys]), ([], [])
     xs, ys = snapshot_windows(node_data, a.num_timesteps_in, a.num_timesteps_out)
     xs, ys = [x.to(dev) for x in xs], [y.to(dev) for y in ys]
     return d, n, f, *split(xs, ys, a.tr)
@@ -425,6 +459,9 @@ def open_outputs(a, model_name: str):
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    if a.streamed:
+        from .serve import refuse_streamed
+        refuse_streamed(a.model)
     torch.manual_seed(a.seed)
     dev = torch.device("cuda:0")
     d, n, f, (tx, ty), (vx, vy) = load_windows(a, dev)
@@ -509,12 +546,24 @@ def main(argv=None):
             raise SystemExit("--fused_step covers RegionalTemporalGCN (regional decomposition) / TemporalGCN")
         from .functional import FusedTrainStep
         stepper = FusedTrainStep(model, graph, f, a.num_timesteps_in)
+    streamed = None
+    if a.streamed:                                            # the test pass only: test windows len(tx) .. of the data as loaded
+        if a.model == "TemporalGCN":
+            s_graphs = BatchedGraphs(lambda b: model.prepare_graph(ei, ea, n, copies=b))
+        else:
+            s_graphs = BatchedGraphs(lambda b: model.prepare_graph(ei, r_idx, r_att, copies=b))
+        nd = torch.from_numpy(np.asarray(d["node_data"]))
+        streamed = (nd, s_graphs.get, *streamed_split(nd.shape[2], a.num_timesteps_in, a.num_timesteps_out, a.tr))
     for epoch in range(a.epochs + 1):
         if batched:
             last, _ = train_epoch_batched(model, batched[0], batched[2], opt, a.snap_batch)
-            rmse, mse = evaluate_batched(model, batched[1], batched[2], a.snap_batch)
         else:
             last, _ = train_epoch(model, tx, ty, graph, opt, stepper)
+        if streamed:
+            rmse, mse = evaluate_streamed(model, streamed[0], a.num_timesteps_in, a.num_timesteps_out, streamed[1], streamed[2], streamed[3])
+        elif batched:
+            rmse, mse = evaluate_batched(model, batched[1], batched[2], a.snap_batch)
+        else:
             rmse, mse = evaluate(model, vx, vy, graph)
         _report(a, log, out_dir, model, epoch, last, rmse, mse)
 
