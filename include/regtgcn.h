@@ -166,6 +166,7 @@ typedef struct regt_dims {
 #define REGT_DIMS_NO_FUSED_BWD 2u   /* bf16 arithmetic with the three data-gradient launches (= regt_set_option("fused_bwd", 0)) */
 #define REGT_DIMS_NO_SIDE_STREAM 4u /* every kernel of this call on `stream` itself (no library side stream) */
 #define REGT_DIMS_FORWARD_ONLY 8u   /* regt_forward / _packed / _packed_bf16 / regt_cell_forward: no backward will follow (see below) */
+#define REGT_DIMS_NO_HEAD 16u       /* regt_forward / regt_backward without the head (see regt_backward below) */
 
 typedef struct regt_graph {
     const int32_t* rowptr;        /* (2N+1) */
@@ -283,6 +284,13 @@ int32_t regt_forward_packed_bf16(const regt_dims* dims, const regt_graph* graph,
 /* Gradients of all parameters given dL/dpred (N,O) and optionally dL/dhidden (N,C) (may be NULL).
  * Must follow regt_forward on the same workspace; `hidden` is that forward's hidden output;
  * x_packed is NULL after regt_forward, or the buffer given to regt_forward_packed. */
+/* REGT_DIMS_NO_HEAD in dims->flags: the cell alone, for a caller that runs the head elsewhere (regt_window_backward).
+ *   regt_forward:  pred may be NULL and is not written; the head is not run.  Combines with REGT_DIMS_FORWARD_ONLY.
+ *   regt_backward: dpred may be NULL and is not read; dhidden is required (16-byte aligned) and is the WHOLE upstream gradient of
+ *     `hidden`; the head launches are skipped and grads->head1_w / head1_b / head2_w / head2_b are neither read nor written.  Every
+ *     other gradient is what a call without the flag gives for dpred = 0 and the same dhidden, bit for bit.
+ * Without the flag everything is as before (a NULL dpred is refused).  regt_forward_packed / _packed_bf16 and regt_cell_forward /
+ * regt_cell_backward refuse the flag. */
 int32_t regt_backward(const regt_dims* dims, const regt_graph* graph, const regt_params* params,
                       const regt_grads* grads, const float* dpred, const float* dhidden, const float* hidden,
                       const float* x_packed, void* workspace, size_t workspace_bytes, regt_stream_t stream);
@@ -330,6 +338,36 @@ int32_t regt_window_forward(const float* ring, int32_t ring_len, int32_t first_s
                             int32_t C, int32_t O, int32_t H1, const float* attention, const float* head1_w, const float* head1_b,
                             const float* head2_w, const float* head2_b, float* pred, float* hidden, void* workspace,
                             size_t workspace_bytes, regt_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Streamed training: the backward of regt_window_forward.
+ *
+ * With fixed weights the gradient of a run of consecutive stride-1 windows factors through the per-step cell outputs S_s:
+ *     dring[slot(j)]  (+)= sum_{w : 0 <= j - w < T} prob[j - w] * dhidden[w]          j < windows + T - 1   (the step's dS)
+ *     d_attention[p]  (+)= prob[p] * (dprob[p] - sum_q prob[q] dprob[q]),   dprob[p] = sum_{w, n, c} dhidden[w, n, c] * ring[slot(w + p), n, c]
+ * with slot(j) = (first_slot + j) % ring_len, prob = softmax(attention) and dhidden = the head's backward on dpred.  The call recomputes
+ * the head's hidden activation from `hidden` (the forward's output; its workspace is not needed), runs the head's backward on
+ * windows * N rows (dhidden stays in the workspace) and then the two passes above.  ring, hidden, dpred as in regt_window_forward;
+ * dring has the ring's shape and slot mapping.
+ * accumulate = 0: d_attention, d_head1_w, d_head1_b, d_head2_w, d_head2_b and the windows + T - 1 covered slots of dring are written;
+ * accumulate = 1: they are added to.  Slots of dring outside the covered ones are not touched.
+ * Order: a covered slot's accumulator starts from the value dring holds (accumulate = 1) or from 0 and receives its windows in
+ * ascending window order, one fused multiply-add each.  So the dS of a step is the same bits whether its windows arrive in one call
+ * or split over consecutive accumulating calls in ascending order, whatever chunk of the kernel it falls in and whatever first_slot /
+ * ring_len are: a batch of windows hands its partial sums to the next one through dring.  d_attention is reduced in a fixed order that
+ * depends on the arguments and the device's CU count only (two calls give the same bits).
+ * Limits: regt_window_forward's, T <= regt_window_backward_max_t() (32), windows + T - 1 <= ring_len for every window count.
+ * Refused before anything is launched: regt_window_forward's list, a larger T, workspace_bytes below
+ * regt_window_backward_workspace_bytes(N, C, H1, O, windows, T) (0 = refused dimensions; it depends on the CU count of the current
+ * device), dring / hidden / workspace not 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+size_t regt_window_backward_workspace_bytes(int32_t N, int32_t C, int32_t H1, int32_t O, int32_t windows, int32_t T);
+int32_t regt_window_backward_max_t(void);
+int32_t regt_window_backward(const float* ring, int32_t ring_len, int32_t first_slot, int32_t windows, int32_t N, int32_t T,
+                             int32_t C, int32_t O, int32_t H1, const float* attention, const float* head1_w, const float* head1_b,
+                             const float* head2_w, const float* head2_b, const float* hidden, const float* dpred, float* dring,
+                             int32_t accumulate, float* d_attention, float* d_head1_w, float* d_head1_b, float* d_head2_w,
+                             float* d_head2_b, void* workspace, size_t workspace_bytes, regt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Zero-hidden TGCN cell + attention over periods + head, on gate inputs the CALLER aggregated.

@@ -35,6 +35,7 @@ ARITH_DEFAULT, ARITH_FP32, ARITH_BF16X3, ARITH_BF16 = 0, 1, 2, 3
 ARITH_NAMES = {None: ARITH_DEFAULT, "default": ARITH_DEFAULT, "fp32": ARITH_FP32, "bf16x3": ARITH_BF16X3, "bf16": ARITH_BF16}
 DIMS_NO_BF16_ROWS, DIMS_NO_FUSED_BWD, DIMS_NO_SIDE_STREAM = 1, 2, 4
 DIMS_FORWARD_ONLY = 8      # forward entry points: no backward follows; workspace of regt_forward_only_workspace_bytes
+DIMS_NO_HEAD = 16          # regt_forward / regt_backward: the cell alone (pred / dpred may be NULL, dhidden is the whole upstream gradient)
 
 
 def arith_code(arith) -> int:
@@ -138,6 +139,9 @@ SIGNATURES = {
     "regt_window_chunk": (C.c_int32, [C.c_int32]),
     "regt_window_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
     "regt_window_forward": (C.c_int32, [vp] + [C.c_int32] * 8 + [vp] * 8 + [C.c_size_t, vp]),
+    "regt_window_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 6),
+    "regt_window_backward_max_t": (C.c_int32, []),
+    "regt_window_backward": (C.c_int32, [vp] + [C.c_int32] * 8 + [vp] * 8 + [C.c_int32] + [vp] * 6 + [C.c_size_t, vp]),
     "regt_mean_csr": (C.c_int32, [vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "regt_cell0_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.c_int32, C.c_int32]),
     "regt_cell0_forward": (C.c_int32, [C.POINTER(Dims), C.POINTER(Cell0Args), vp, vp, vp, C.c_size_t, vp]),

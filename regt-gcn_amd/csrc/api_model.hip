@@ -41,7 +41,9 @@ static int32_t forward_common(const regt_dims* dims, const regt_graph* graph, co
     CallScope call(dims);
     REGT_CHECK_ARG(graph && graph->rowptr && graph->col && graph->val && (graph->node_region || graph->overlap), "regt_forward: graph incomplete");
     TRY(check_ptrs(params, *dims));
-    REGT_CHECK_ARG((x || xp_ext) && pred && hidden && ws, "regt_forward: NULL pointer");
+    const bool no_head = (dims->flags & REGT_DIMS_NO_HEAD) != 0;
+    REGT_CHECK_ARG(!no_head || !xp_ext, "regt_forward_packed: REGT_DIMS_NO_HEAD is for regt_forward / regt_backward");
+    REGT_CHECK_ARG((x || xp_ext) && (pred || no_head) && hidden && ws, "regt_forward: NULL pointer");
     REGT_CHECK_ARG(al16(x) && al16(xp_ext) && al16(hidden) && al16(ws),
                    "regt_forward: x, hidden and workspace must be 16-byte aligned");
     REGT_CHECK_ARG(!xp_ext || x_rows >= dims->N, "regt_forward_packed: x_rows=%d < N=%d", x_rows, dims->N);
@@ -105,10 +107,14 @@ int32_t regt_backward(const regt_dims* dims, const regt_graph* graph, const regt
     CallScope call(dims);
     REGT_CHECK_ARG(graph && graph->rowptr && (graph->node_region || graph->overlap), "regt_backward: graph incomplete");
     TRY(check_ptrs(params, *dims));
-    REGT_CHECK_ARG(grads && dpred && hidden && ws, "regt_backward: NULL pointer");
+    const bool no_head = (dims->flags & REGT_DIMS_NO_HEAD) != 0;
+    REGT_CHECK_ARG(grads && (dpred || no_head) && hidden && ws, "regt_backward: NULL pointer");
+    REGT_CHECK_ARG(!no_head || (dhidden && al16(dhidden)), "regt_backward (REGT_DIMS_NO_HEAD): dhidden is the whole upstream gradient: it must be "
+                   "given, 16-byte aligned");
+    REGT_CHECK_ARG(!no_head || !x_packed, "regt_backward: REGT_DIMS_NO_HEAD does not combine with a packed input");
     {
         const regt_grads& g = *grads;
-        bool ok = g.cheb_w0 && g.cheb_w1 && g.cheb_bias && g.head1_w && g.head1_b && g.head2_w && g.head2_b;
+        bool ok = g.cheb_w0 && g.cheb_w1 && g.cheb_bias && (no_head || (g.head1_w && g.head1_b && g.head2_w && g.head2_b));
         for (int k = 0; k < 3; ++k) ok = ok && g.conv_lin_w[k] && g.conv_bias[k] && g.gate_w[k] && g.gate_b[k];
         if (dims->regional) ok = ok && g.region_w && g.region_b;
         REGT_CHECK_ARG(ok, "regt_backward: a required gradient pointer is NULL (only `attention` may be NULL)");
@@ -142,6 +148,7 @@ int32_t regt_cell_forward(const regt_dims* dims, const regt_graph* graph, const 
     TRY(check_dims(dims));
     CallScope call(dims);
     REGT_CHECK_ARG(dims->regional == 0, "regt_cell_forward: dims.regional must be 0");
+    REGT_CHECK_ARG(!(dims->flags & REGT_DIMS_NO_HEAD), "regt_cell_forward: REGT_DIMS_NO_HEAD is for regt_forward / regt_backward");
     REGT_CHECK_ARG(graph && graph->rowptr && graph->col && graph->val && !graph->overlap, "regt_cell_forward: graph incomplete");
     TRY(check_ptrs(params, *dims, true));
     REGT_CHECK_ARG(x && h_in && pred && hidden && ws, "regt_cell_forward: NULL pointer");
@@ -167,6 +174,7 @@ int32_t regt_cell_backward(const regt_dims* dims, const regt_graph* graph, const
     TRY(check_dims(dims));
     CallScope call(dims);
     REGT_CHECK_ARG(dims->regional == 0, "regt_cell_backward: dims.regional must be 0");
+    REGT_CHECK_ARG(!(dims->flags & REGT_DIMS_NO_HEAD), "regt_cell_backward: REGT_DIMS_NO_HEAD is for regt_forward / regt_backward");
     REGT_CHECK_ARG(graph && graph->rowptr && !graph->overlap, "regt_cell_backward: graph incomplete");
     TRY(check_ptrs(params, *dims, true));
     REGT_CHECK_ARG(grads && dpred && hidden && h_in && dh_in && ws, "regt_cell_backward: NULL pointer");
@@ -238,6 +246,115 @@ int32_t regt_window_forward(const float* ring, int32_t ring_len, int32_t first_s
     regt_params p{};
     p.head1_w = head1_w; p.head1_b = head1_b; p.head2_w = head2_w; p.head2_b = head2_b;
     return head_forward(d, p, hidden, y1, pred, hs);
+}
+
+/* ---- streamed training: the backward of regt_window_forward (regtgcn.h) ---- */
+namespace {
+// workspace: the T probabilities (WINDOW_PROBS_BYTES), the head's activation y1 and its gradient d1 (rows x H1 each), dhidden (rows x C),
+// the head's four gradients of this call (delivered to the caller's tensors in one launch: written or added), the slabs of the head's
+// weight gradients (make_layout's head terms), the attention gradient's partial rows (one per workgroup)
+struct WindowBwdLayout {
+    float *probs, *y1, *d1, *dhidden, *g1w, *g1b, *g2w, *g2b, *slab, *partial;
+    long slab_floats;
+    size_t bytes;
+};
+WindowBwdLayout window_bwd_layout(long rows, int windows, int N, int C, int H1, int O, int T, char* base) {
+    WindowBwdLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t nbytes) {
+        float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
+        off += (nbytes + 255) & ~(size_t)255;
+        return p;
+    };
+    L.probs = take(WINDOW_PROBS_BYTES);
+    L.y1 = take((size_t)rows * H1 * 4);
+    L.d1 = take((size_t)rows * H1 * 4);
+    L.dhidden = take((size_t)rows * C * 4);
+    L.g1w = take((size_t)H1 * C * 4);
+    L.g1b = take((size_t)H1 * 4);
+    L.g2w = take((size_t)O * H1 * 4);
+    L.g2b = take((size_t)O * 4);
+    const HeadChunks hc = head_chunks(rows, H1, C);
+    L.slab_floats = (long)hc.n1 * ((long)H1 * C + H1 + (long)O * H1 + O) + (long)hc.n2 * ((long)O * H1 + O) + 16 * 64;
+    L.slab = take((size_t)L.slab_floats * 4);
+    L.partial = take((size_t)window_attgrad_blocks(windows, N, C) * T * 4);
+    L.bytes = off;
+    return L;
+}
+bool window_bwd_dims_ok(int N, int C, int H1, int O, int windows, int T) {
+    return N > 0 && C > 0 && H1 > 0 && O > 0 && windows > 0 && T > 0 && C % 4 == 0 && T <= WINDOW_BWD_MAX_T && (long)N * windows <= INT_MAX &&
+           (long)windows + T - 1 <= (long)WINDOW_MAX_CHUNKS * WINDOW_WC;
+}
+}  // namespace
+
+int32_t regt_window_backward_max_t(void) { return WINDOW_BWD_MAX_T; }
+
+size_t regt_window_backward_workspace_bytes(int32_t N, int32_t C, int32_t H1, int32_t O, int32_t windows, int32_t T) {
+    if (!window_bwd_dims_ok(N, C, H1, O, windows, T)) {
+        set_error("regt_window_backward_workspace_bytes: N, C, H1, O, windows, T must be positive, C a multiple of 4, T <= %d and windows * N below 2^31 "
+                  "(N=%d C=%d H1=%d O=%d windows=%d T=%d)", WINDOW_BWD_MAX_T, N, C, H1, O, windows, T);
+        return 0;
+    }
+    return window_bwd_layout((long)N * windows, windows, N, C, H1, O, T, nullptr).bytes;
+}
+
+int32_t regt_window_backward(const float* ring, int32_t ring_len, int32_t first_slot, int32_t windows, int32_t N, int32_t T, int32_t C,
+                             int32_t O, int32_t H1, const float* attention, const float* head1_w, const float* head1_b,
+                             const float* head2_w, const float* head2_b, const float* hidden, const float* dpred, float* dring,
+                             int32_t accumulate, float* d_attention, float* d_head1_w, float* d_head1_b, float* d_head2_w,
+                             float* d_head2_b, void* ws, size_t ws_bytes, regt_stream_t st) {
+    REGT_CHECK_ARG(ring && attention && head1_w && head1_b && head2_w && head2_b && hidden && dpred && dring && d_attention && d_head1_w &&
+                   d_head1_b && d_head2_w && d_head2_b && ws, "regt_window_backward: NULL pointer");
+    REGT_CHECK_ARG(N > 0 && C > 0 && O > 0 && H1 > 0 && T > 0 && windows > 0 && ring_len > 0,
+                   "regt_window_backward: ring_len, windows, N, T, C, O, H1 must be positive (ring_len=%d windows=%d N=%d T=%d C=%d O=%d H1=%d)",
+                   ring_len, windows, N, T, C, O, H1);
+    REGT_CHECK_ARG(C % 4 == 0, "regt_window_backward: C=%d must be a multiple of 4", C);
+    REGT_CHECK_ARG(T <= WINDOW_BWD_MAX_T, "regt_window_backward: T=%d exceeds the %d periods the backward covers (regt_window_backward_max_t)", T,
+                   WINDOW_BWD_MAX_T);
+    REGT_CHECK_ARG(ring_len >= T, "regt_window_backward: ring_len=%d < T=%d", ring_len, T);
+    REGT_CHECK_ARG(first_slot >= 0 && first_slot < ring_len, "regt_window_backward: first_slot=%d outside [0, ring_len=%d)", first_slot, ring_len);
+    REGT_CHECK_ARG((long)windows + T - 1 <= ring_len,
+                   "regt_window_backward: windows=%d of T=%d periods would wrap onto themselves in a ring of %d slots", windows, T, ring_len);
+    REGT_CHECK_ARG((long)N * windows <= INT_MAX, "regt_window_backward: windows * N too large");
+    REGT_CHECK_ARG((long)windows + T - 1 <= (long)WINDOW_MAX_CHUNKS * WINDOW_WC, "regt_window_backward: windows=%d exceeds the %d one call covers",
+                   windows, WINDOW_MAX_CHUNKS * WINDOW_WC - T + 1);
+    REGT_CHECK_ARG(al16(ring) && al16(hidden) && al16(dring) && al16(ws),
+                   "regt_window_backward: ring, hidden, dring and workspace must be 16-byte aligned");
+    const long rows = (long)N * windows;
+    const WindowBwdLayout L = window_bwd_layout(rows, windows, N, C, H1, O, T, static_cast<char*>(ws));
+    REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_window_backward: workspace %zu < required %zu bytes (regt_window_backward_workspace_bytes)", ws_bytes,
+                   L.bytes);
+    hipStream_t hs = (hipStream_t)st;
+    regt_dims d{};
+    d.N = (int)rows; d.T = T; d.C = C; d.O = O; d.H1 = H1;
+    regt_params p{};
+    p.head1_w = head1_w; p.head1_b = head1_b; p.head2_w = head2_w; p.head2_b = head2_b;
+    regt_grads gr{};
+    gr.head1_w = L.g1w; gr.head1_b = L.g1b; gr.head2_w = L.g2w; gr.head2_b = L.g2b;
+    TRY(launch_softmax_small(attention, L.probs, T, hs));
+    {   // y1 = relu(linear1(relu(hidden))): the first layer of head_forward, recomputed
+        EpiBiasAct e{L.y1, H1, head1_b, ACT_RELU, 0.f};
+        PROF("head_fwd", hs);
+        TRY(launch_gemm_bias_act(one_seg(make_seg(hidden, C, head1_w, nullptr, C, INT_MAX, C, true, SEG_RELU_A)), (int)rows, H1, e, hs));
+    }
+    ReduceQueue rq(L.slab, L.slab_floats, hs);
+    TRY(head_backward(d, p, gr, dpred, nullptr, hidden, L.y1, L.d1, L.dhidden, rq, hs));
+    TRY(rq.flush());
+    {
+        DeliverArgs a{};
+        a.count = 4; a.accumulate = accumulate ? 1 : 0;
+        a.src[0] = L.g1w; a.dst[0] = d_head1_w; a.n[0] = (long)H1 * C;
+        a.src[1] = L.g1b; a.dst[1] = d_head1_b; a.n[1] = H1;
+        a.src[2] = L.g2w; a.dst[2] = d_head2_w; a.n[2] = (long)O * H1;
+        a.src[3] = L.g2b; a.dst[3] = d_head2_b; a.n[3] = O;
+        TRY(launch_deliver(a, hs));
+    }
+    {
+        PROF("window_adjoint", hs);
+        TRY(launch_window_adjoint(L.dhidden, L.probs, dring, ring_len, first_slot, windows, N, T, C, accumulate ? 1 : 0, hs));
+    }
+    PROF("window_attgrad", hs);
+    return launch_window_attgrad(ring, L.dhidden, L.probs, L.partial, d_attention, ring_len, first_slot, windows, N, T, C, accumulate ? 1 : 0, hs);
 }
 
 }  // extern "C"

@@ -218,6 +218,7 @@ static int forward_bf16_rows(const regt_dims& d, const regt_graph& g, const regt
         if (fused_rows_form(d, g)) TRY(launch_fused_forward_rows(a, C, F, option(OPT_FUSED_ROWS) == 2 ? 4 : 8, st, save));
         else TRY(launch_fused_forward(a, C, F, st, save));
     }
+    if (d.flags & REGT_DIMS_NO_HEAD) return REGT_OK;
     return head_forward(d, p, hidden, L.y1, pred, st);
 }
 
@@ -337,7 +338,8 @@ int forward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, 
         PROF("gemm_candidate", st);
         TRY(launch_gemm_candidate(a, st, save));
     }
-    // 5. head: relu -> linear1 -> relu -> linear2
+    // 5. head: relu -> linear1 -> relu -> linear2  (REGT_DIMS_NO_HEAD: the caller runs it elsewhere)
+    if (d.flags & REGT_DIMS_NO_HEAD) return REGT_OK;
     return head_forward(d, p, hidden, L.y1, pred, st);
 }
 
@@ -713,13 +715,18 @@ static int compose_backward(const Bwd& b) {
 // `h_ext` / `dh_ext` != NULL (regt_cell_backward): the hidden input was supplied by the caller; its gradient is
 // written to dh_ext and the embedding-stage gradients (A0 / A_r / Cheb weights) are skipped.
 int backward_impl(const regt_dims& d, const regt_graph& g, const regt_params& p, const regt_grads& gr,
-                  const float* dpred, const float* dhidden, const float* hidden, const float* xp_ext, const Layout& L,
+                  const float* dpred, const float* dhidden, const float* hidden, const float* xp_ext, const Layout& L0,
                   hipStream_t st, int fmt, const float* h_ext, float* dh_ext) {
     const StepForm f = step_form(d, fmt, h_ext != nullptr);
+    // REGT_DIMS_NO_HEAD: no head stage; the caller's dhidden IS dOH (every stage below only reads it)
+    const bool no_head = (d.flags & REGT_DIMS_NO_HEAD) != 0;
+    Layout Lh = L0;
+    if (no_head) Lh.dOH = const_cast<float*>(dhidden);
+    const Layout& L = Lh;
     const Bwd b{d, g, p, gr, L, f, wb_ptrs(L.Wb, d.C, d.F),
                 (xp_ext && (!f.xbf || (fmt & FMT_XCALLER))) ? xp_ext : L.Xp, h_ext ? h_ext : L.h, dh_ext ? dh_ext : L.dh, h_ext != nullptr, st};
     ReduceQueue rq(L.slab, L.slab_floats, st);
-    TRY(head_backward(d, p, gr, dpred, dhidden, hidden, L.y1, L.d1, L.dOH, rq, st));
+    if (!no_head) TRY(head_backward(d, p, gr, dpred, dhidden, hidden, L.y1, L.d1, L.dOH, rq, st));
     TRY(data_gradients(b));
     TRY(weight_gradients(b, rq));
     TRY(rq.flush());      // every slab reduction of this backward pass, one launch

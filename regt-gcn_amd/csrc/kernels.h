@@ -350,6 +350,21 @@ constexpr int WINDOW_MAX_CHUNKS = 65535;      // chunks of one launch (grid.y): 
 int window_chunk(int windows);      // windows a thread accumulates at once: 1 or WINDOW_WC (regt_window_chunk hands it to tools and tests)
 int launch_window_sum(const float* ring, const float* probs, float* hidden, int ring_len, int first_slot, int windows, int N, int T, int C,
                       hipStream_t st);
+// Backward of the window sum (window_bwd.hip).  The adjoint: dring[(first_slot + j) % ring_len] (+)= sum_w probs[j - w]
+// dhidden[w] over the windows w that contain covered slot j < windows + T - 1, every element from the value dring holds (accumulate) or
+// from 0, its windows ascending, one fmaf each; slots are taken in chunks of window_chunk(windows) per thread.  The attention gradient:
+// dprob[p] = sum_{w, n, c} dhidden[w] ring[slot(w + p)] in one pass -- per-thread sums, one partial row per workgroup in `partial`
+// (window_attgrad_blocks rows of T floats), then one small launch that sums the rows in a fixed order and applies the softmax backward
+// into d_attention (added to under `accumulate`, else written).
+constexpr int WINDOW_BWD_MAX_T = 32;      // periods the backward covers (the attention gradient keeps one accumulator per period in registers)
+int launch_window_adjoint(const float* dhidden, const float* probs, float* dring, int ring_len, int first_slot, int windows, int N, int T,
+                          int C, int accumulate, hipStream_t st);
+long window_attgrad_blocks(int windows, int N, int C);
+int launch_window_attgrad(const float* ring, const float* dhidden, const float* probs, float* partial, float* d_attention, int ring_len,
+                          int first_slot, int windows, int N, int T, int C, int accumulate, hipStream_t st);
+// dst[k][i] = src[k][i] (+ dst[k][i] under `accumulate`) for up to four vectors in one launch
+struct DeliverArgs { const float* src[4]; float* dst[4]; long n[4]; int count; int accumulate; };
+int launch_deliver(const DeliverArgs& a, hipStream_t st);
 struct CellBwdArgs {
     const float* dOH; const float* probs; const float* ZR; const float* h; const float* Ht;
     float* dhp; float* dzr; float* dp_partial; int num_nodes, T, C; int nodes_per_block;

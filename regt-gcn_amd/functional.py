@@ -294,7 +294,8 @@ def _regt_forward_call(x: torch.Tensor, graph: PreparedGraph, regional: bool, sl
     dims, gs, wsb, ps, Cdim, O = plan
     handle = _WsHandle(wsb, x.device)
     ws = handle.ws
-    pred = torch.empty(N, O, dtype=torch.float32, device=x.device)
+    # (DIMS_NO_HEAD: the library runs no head and takes a NULL pred)
+    pred = None if int(flags) & _lib.DIMS_NO_HEAD else torch.empty(N, O, dtype=torch.float32, device=x.device)
     if hidden_out is None:
         hidden = torch.empty(N, Cdim, dtype=torch.float32, device=x.device)
     else:
@@ -368,6 +369,43 @@ class RegTGCNFunction(torch.autograd.Function):
                 if n_ in grads:
                     grads[n_] = grads[n_][:, :st.f_real].contiguous()
         return (None, None, None, None, None) + _deliver_grads(ctx.leaf_params, [grads[n_] for n_ in names])
+
+
+def regt_period_gradients(x: torch.Tensor, graph: PreparedGraph, regional: bool, slope: float, arith: int, flags: int, leaf_params,
+                          d_s: torch.Tensor) -> None:
+    """Streamed training: the cell's backward from dL/dS alone.  ``x`` (rows, F, 1) holds one raw time step per graph
+    copy, ``leaf_params`` the model's parameters in ``param_names`` order with a ONE-element attention tensor in first place,
+    ``d_s`` (rows, C) the gradient of the cell outputs.  One training-layout T = 1 forward without the head (a recompute:
+    DIMS_NO_HEAD) and regt_backward with ``dhidden = d_s``; the gradients of the cell and embedding parameters are added to their
+    ``.grad`` (:func:`_deliver_grads` under :func:`grad_accumulation_in_backward`); the attention logit's and the head's are not formed."""
+    lib = _lib.load()
+    detached = [p.detach() for p in leaf_params]
+    _, hidden, st = _regt_forward_call(x, graph, regional, slope, (False, arith, int(flags) | _lib.DIMS_NO_HEAD), detached, False)
+    dims, names = st.dims, st.names
+    if d_s.dtype != torch.float32 or d_s.device != hidden.device or tuple(d_s.shape) != tuple(hidden.shape) or not d_s.is_contiguous() \
+            or d_s.data_ptr() % 16:
+        raise ValueError(f"d_s must be a contiguous, 16-byte aligned float32 {tuple(hidden.shape)} tensor on {hidden.device}")
+    head = set(PARAM_NAMES_HEAD)
+    sizes = [0 if n_ in head else (p_.numel() + 3) & ~3 for n_, p_ in zip(names, st.saved)]
+    flat = torch.empty(sum(sizes), dtype=torch.float32, device=hidden.device)
+    grads, off = {}, 0
+    for n_, p_, sz in zip(names, st.saved, sizes):
+        if sz:
+            grads[n_] = flat[off:off + p_.numel()].view_as(p_)
+            off += sz
+    gr = _fill(_lib.Grads(), grads, regional)
+    _lib.check(lib.regt_backward(C.byref(dims), C.byref(st.gs), C.byref(st.ps), C.byref(gr), None, _lib.ptr(d_s), _lib.ptr(hidden), None,
+                                 _lib.ptr(st.handle.ws), st.wsb, _stream()), "regt_backward")
+    if st.f_pad:
+        for n_ in F_WIDE_PARAMS:
+            if n_ in grads:
+                grads[n_] = grads[n_][:, :st.f_real].contiguous()
+    # the one-element attention stand-in is no parameter of the model: its dummy gradient is dropped, like the head's absent ones
+    live = [(p_, grads[n_]) for n_, p_ in zip(names, leaf_params) if n_ in grads and n_ != "tgnn._attention"]
+    if not all(p_.is_leaf and p_.requires_grad for p_, _ in live):
+        raise ValueError("period gradients are added to .grad: every cell / embedding parameter must be a leaf that requires grad")
+    with grad_accumulation_in_backward():
+        _deliver_grads([p_ for p_, _ in live], [g_ for _, g_ in live])
 
 
 class MseLossFunction(torch.autograd.Function):

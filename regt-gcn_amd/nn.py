@@ -33,7 +33,7 @@ from . import ops
 from .functional import (HEAD_HIDDEN, PARAM_NAMES_CELL, AggregateFunction, Cell0Function, CellFunction, GatAggregateFunction,
                          GRUFunction, LinearFunction, MLPHeadFunction, RegTGCNFunction, SpatialEmbedFunction, STAEAddLayerNormFunction,
                          STAEDropAddLayerNormFunction, STAEEmbedFunction, STAEOutputProjFunction, STAEPackedAttentionFunction, STIDFunction, STNormFunction, ZeroGradAnchor, _regt_forward_call, cell_run, param_names,
-                         regt_run)
+                         regt_period_gradients, regt_run)
 from .graph import (AttentionPattern, GcnOperator, MeanOperator, PreparedGraph, fingerprint, prepare_attention_pattern,
                     prepare_cheb_operator, prepare_gcn_operator, prepare_graph, prepare_mean_operator)
 
@@ -246,13 +246,49 @@ class _FusedModel(nn.Module):
         if b * n != graph.num_nodes:
             raise ValueError(f"x_steps holds {b} steps of {n} nodes but the prepared graph has {graph.num_nodes} nodes (prepare it with copies={b})")
         params = [p.detach() for p in self._params_in_order()]
-        params[0] = params[0].new_zeros(1)                     # tgnn._attention -> one logit: softmax = [1.0]
-        flags = int(self.call_flags)
+        params[0] = self._one_logit()                          # tgnn._attention -> one logit: softmax = [1.0]
+        flags = int(self.call_flags) | _lib.DIMS_NO_HEAD       # the head's pred of a single step would be dropped: not computed
         if out is not None and (out.dim() != 3 or tuple(out.shape[:2]) != (b, n) or not out.is_contiguous()):
             raise ValueError(f"out must be a contiguous ({b}, {n}, C) tensor, got {tuple(out.shape)} strides {out.stride()}")
         _, s, _ = _regt_forward_call(x_steps.reshape(b * n, f, 1), graph, self.regional, LEAKY_SLOPE, (False, arith, flags), params, True,
                                      hidden_out=None if out is None else out.view(b * n, out.shape[2]))
         return s.view(b, n, -1) if out is None else out
+
+    def _one_logit(self) -> torch.Tensor:
+        """A one-element zero tensor on the model's device, kept: the library's call plans are keyed by the parameters' addresses."""
+        dev = self._params_in_order()[0].device
+        t = self.__dict__.get("_one_logit_tensor")
+        if t is None or t.device != dev:
+            t = self.__dict__["_one_logit_tensor"] = torch.zeros(1, dtype=torch.float32, device=dev)
+        return t
+
+    def _refuse_bf16(self, what: str) -> int:
+        arith = _lib.arith_code(self.arithmetic)
+        if arith == _lib.ARITH_BF16 or (arith == _lib.ARITH_DEFAULT and _lib.gemm_mode() == 2):
+            raise NotImplementedError(f"{what} covers the fp32-storage arithmetics (fp32, bf16x3); the bf16 arithmetic rounds per window "
+                                      "and is out of scope (DESIGN.md 4b, 4c)")
+        return arith
+
+    def period_gradients(self, x_steps: torch.Tensor, graph: PreparedGraph, d_s: torch.Tensor) -> None:
+        """Streamed training: adds to ``.grad`` of the cell and embedding parameters what the cell outputs S (B, N, C) of
+        the B raw time steps ``x_steps`` (B, N, F) pass back from ``d_s`` = dL/dS (B, N, C, contiguous); ``graph`` prepared with
+        ``copies=B``.  One training-layout T = 1 forward without the head (the recompute of :meth:`period_outputs`' S) followed by the
+        library's backward with ``d_s`` as the whole upstream gradient, on a one-element attention tensor whose dummy gradient is dropped.
+        ``tgnn._attention``, ``linear1.*`` and ``linear2.*`` are left alone: their gradients come from ``ops.window_backward``.
+        fp32-storage arithmetics only."""
+        _need_cuda(x_steps)
+        if x_steps.dim() != 3 or x_steps.dtype != torch.float32:
+            raise ValueError(f"x_steps must be float32 (B, N, F), got {x_steps.dtype} {tuple(x_steps.shape)}")
+        arith = self._refuse_bf16("period_gradients / streamed training")
+        b, n, f = x_steps.shape
+        if b * n != graph.num_nodes:
+            raise ValueError(f"x_steps holds {b} steps of {n} nodes but the prepared graph has {graph.num_nodes} nodes (prepare it with copies={b})")
+        if d_s.dim() != 3 or tuple(d_s.shape[:2]) != (b, n) or not d_s.is_contiguous():
+            raise ValueError(f"d_s must be a contiguous ({b}, {n}, C) tensor, got {tuple(d_s.shape)} strides {d_s.stride()}")
+        params = list(self._params_in_order())
+        params[0] = self._one_logit()
+        regt_period_gradients(x_steps.reshape(b * n, f, 1), graph, self.regional, LEAKY_SLOPE, arith, int(self.call_flags), params,
+                              d_s.view(b * n, d_s.shape[2]))
 
     def forward_packed(self, x_packed_ext: torch.Tensor, graph: PreparedGraph):
         """Region-sharded entry: ``x_packed_ext`` (x_rows, T, F) = own packed rows + gathered halo rows (dist.py)."""

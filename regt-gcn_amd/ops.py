@@ -176,6 +176,64 @@ def window_forward(ring: torch.Tensor, first_slot: int, windows: int, attention:
     return pred, hidden
 
 
+def window_backward_max_t() -> int:
+    """Periods the window backward covers (regt_window_backward_max_t)."""
+    return int(_lib.load().regt_window_backward_max_t())
+
+
+def window_backward(ring: torch.Tensor, first_slot: int, windows: int, attention: torch.Tensor, l1w: torch.Tensor, l1b: torch.Tensor,
+                    l2w: torch.Tensor, l2b: torch.Tensor, hidden: torch.Tensor, dpred: torch.Tensor, dring: torch.Tensor,
+                    accumulate: bool, d_attention: torch.Tensor, d_l1w: torch.Tensor, d_l1b: torch.Tensor, d_l2w: torch.Tensor,
+                    d_l2b: torch.Tensor) -> None:
+    """Streamed training (regt_window_backward): the backward of :func:`window_forward` for the same ``ring`` / ``first_slot`` /
+    ``windows``.  ``hidden`` (windows, N, C) is the forward's output, ``dpred`` (windows, N, O) the loss gradient.  The head's backward
+    runs on all windows' rows; then ``dring[(first_slot + j) % ring_len] (+)= sum_w softmax(attention)[j - w] * dhidden[w]`` for the
+    windows + T - 1 covered slots (windows ascending, one fmaf each, starting from the value ``dring`` holds under ``accumulate``, else
+    from 0: the same bits however the windows are split over consecutive accumulating calls), and the gradients of the attention logits
+    and of the head go to ``d_attention`` (T), ``d_l1w``, ``d_l1b``, ``d_l2w``, ``d_l2b`` -- added to under ``accumulate``, written
+    otherwise.  Slots of ``dring`` outside the covered ones are not touched.  Every output is a contiguous float32 CUDA tensor of its
+    parameter's shape, ``dring`` of the ring's; T <= :func:`window_backward_max_t`; ``windows + T - 1 <= ring_len``."""
+    inputs = {"ring": ring, "attention": attention, "l1w": l1w, "l1b": l1b, "l2w": l2w, "l2b": l2b, "hidden": hidden, "dpred": dpred,
+              "dring": dring, "d_attention": d_attention, "d_l1w": d_l1w, "d_l1b": d_l1b, "d_l2w": d_l2w, "d_l2b": d_l2b}
+    for name, t in inputs.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise _lib.RegtError(f"{name} must be a float32 CUDA tensor (no CPU path)")
+    if ring.dim() != 3 or not ring.is_contiguous():
+        raise ValueError(f"ring must be a contiguous (ring_len, N, C) tensor, got {tuple(ring.shape)} strides {ring.stride()}")
+    ring_len, n, c = ring.shape
+    lib = _lib.load()
+    max_t = int(lib.regt_window_backward_max_t())
+    if attention.dim() != 1 or not 1 <= attention.numel() <= max_t:
+        raise ValueError(f"attention must hold 1 .. {max_t} logits (the window backward's limit), got {tuple(attention.shape)}")
+    t = attention.numel()
+    if l1w.dim() != 2 or l1w.shape[1] != c or l2w.dim() != 2 or l2w.shape[1] != l1w.shape[0]:
+        raise ValueError(f"l1w must be (H1, {c}) and l2w (O, H1), got {tuple(l1w.shape)} and {tuple(l2w.shape)}")
+    h1, o = l1w.shape[0], l2w.shape[0]
+    if tuple(l1b.shape) != (h1,) or tuple(l2b.shape) != (o,):
+        raise ValueError(f"l1b must be ({h1},) and l2b ({o},), got {tuple(l1b.shape)} and {tuple(l2b.shape)}")
+    first_slot, windows = int(first_slot), int(windows)
+    if n < 1 or c < 4 or c % 4:
+        raise ValueError(f"ring needs N >= 1 and C a positive multiple of 4, got N={n} C={c}")
+    if ring_len < t or not 0 <= first_slot < ring_len or windows < 1 or windows + t - 1 > ring_len:
+        raise ValueError(f"need 0 <= first_slot < ring_len, windows >= 1 and windows + T - 1 <= ring_len (ring_len={ring_len} T={t} "
+                         f"first_slot={first_slot} windows={windows})")
+    shapes = {"hidden": (windows, n, c), "dpred": (windows, n, o), "dring": (ring_len, n, c), "d_attention": (t,), "d_l1w": (h1, c),
+              "d_l1b": (h1,), "d_l2w": (o, h1), "d_l2b": (o,)}
+    for name, shape in shapes.items():
+        x = inputs[name]
+        if x.device != ring.device or tuple(x.shape) != shape or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 {shape} tensor on {ring.device}, got {tuple(x.shape)} strides {x.stride()}")
+    attention, l1w, l1b, l2w, l2b = (x.detach().contiguous() for x in (attention, l1w, l1b, l2w, l2b))
+    nbytes = lib.regt_window_backward_workspace_bytes(n, c, h1, o, windows, t)
+    if nbytes == 0:
+        _lib.check(1, "regt_window_backward_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=ring.device)
+    _lib.check(lib.regt_window_backward(_lib.ptr(ring), ring_len, first_slot, windows, n, t, c, o, h1, _lib.ptr(attention), _lib.ptr(l1w),
+                                        _lib.ptr(l1b), _lib.ptr(l2w), _lib.ptr(l2b), _lib.ptr(hidden), _lib.ptr(dpred), _lib.ptr(dring),
+                                        1 if accumulate else 0, _lib.ptr(d_attention), _lib.ptr(d_l1w), _lib.ptr(d_l1b), _lib.ptr(d_l2w),
+                                        _lib.ptr(d_l2b), _lib.ptr(ws), nbytes, _stream()), "regt_window_backward")
+
+
 def gat_forward(rowptr: torch.Tensor, col: torch.Tensor, xp: torch.Tensor, u_src: torch.Tensor, u_dst: torch.Tensor, slope: float = 0.2):
     """GATConv attention aggregation on packed input rows xp (N,T,F): returns (out (N,T,F), stats (N*T,4))."""
     xp, u_src, u_dst = _f32c(xp, "xp"), _f32c(u_src, "u_src"), _f32c(u_dst, "u_dst")

@@ -198,6 +198,104 @@ def evaluate_streamed(model, node_data: torch.Tensor, t_in: int, t_out: int, bui
     return float(m.sqrt()), float(m)
 
 
+def refuse_streamed_train(a) -> None:
+    """SystemExit with the reason unless ``--streamed_train`` covers the run the flags describe."""
+    from .serve import STREAMED_MODELS
+    if a.model not in STREAMED_MODELS:
+        raise SystemExit(f"--streamed_train covers {' / '.join(STREAMED_MODELS)}: their cell starts from H = None in every period, so a time "
+                         f"step's cell forward and backward are shared by every window that contains it; {a.model} trains window by window")
+    if a.fused_step:
+        raise SystemExit("--streamed_train and --fused_step are alternatives: the streamed epoch runs no per-window step that "
+                         "FusedTrainStep could replace")
+    if a.snap_batch > 1:
+        raise SystemExit("--streamed_train and --snap_batch are alternatives: the streamed epoch batches raw time steps, not windows")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--streamed_train runs on one GPU: the region-sharded forward_packed path is out of its scope")
+
+
+def train_epoch_streamed(model, node_data: torch.Tensor, t_in: int, t_out: int, build_graph, first: int, count: int, optimizer,
+                         step_batch: int = 64) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """train_epoch() over the ``count`` stride-1 windows ``first .. first + count - 1`` of ``node_data`` (N, F, steps) as loaded, with
+    every raw time step's cell forward AND backward run once: the weights are fixed until the epoch's single optimizer
+    step, the epoch's gradient is a sum over windows, and that sum factors through the per-step cell outputs S_s.  Returns (last
+    window's loss, all per-window losses), as train_epoch_batched.  ``build_graph(b)``: the model's graph prepared with ``copies=b``.
+
+    Per batch of at most serve.WINDOW_BATCH windows, on two timelines S and dS of WINDOW_BATCH + t_in - 1 slabs (N, C): the batch's new
+    S slabs (period_outputs), the window sum and head (ops.window_forward), the loss gradient with one window's N * O as divisor,
+    ops.window_backward accumulating into dS and into ``.grad`` of ``tgnn._attention`` and the head; the steps whose dS is now complete
+    (no later window contains them) go through model.period_gradients, always in the same groups of ``step_batch`` consecutive steps
+    counted from the epoch's first one -- a group that straddles two batches waits in a staging buffer of ``step_batch`` slabs --, so
+    the cell and embedding gradients are the same bits whatever WINDOW_BATCH is; then the last t_in - 1 slabs of both timelines move
+    to the front.  The memory does not grow with ``count``.  RegionalTemporalGCN / TemporalGCN, fp32-storage arithmetics."""
+    from . import ops, serve
+    if t_in != int(model.tgnn.periods):
+        raise ValueError(f"the model was built for {model.tgnn.periods} periods, got t_in={t_in}")
+    if count < 1 or first < 0 or step_batch < 1 or first + count + t_in + t_out - 1 > node_data.shape[2]:
+        raise ValueError(f"windows {first} .. {first + count - 1} of {t_in} steps and their {t_out}-step targets do not fit "
+                         f"{node_data.shape[2]} time steps (step_batch={step_batch})")
+    if t_in > ops.window_backward_max_t():
+        raise ValueError(f"streamed training covers t_in <= {ops.window_backward_max_t()} (the window backward's limit), got {t_in}")
+    model.train()
+    att, l1, l2 = model.tgnn._attention, model.linear1, model.linear2
+    direct = [att, l1.weight, l1.bias, l2.weight, l2.bias]        # the parameters ops.window_backward accumulates into
+    dev = l1.weight.device
+    for p in direct:
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+    n, c, o = node_data.shape[0], int(model.tgnn.out_channels), l2.weight.shape[0]
+    wb = serve.WINDOW_BATCH
+    slabs = min(count, wb) + t_in - 1
+    s_line = torch.empty(slabs, n, c, dtype=torch.float32, device=dev)
+    ds_line = torch.zeros(slabs, n, c, dtype=torch.float32, device=dev)
+    stage = torch.empty(step_batch, n, c, dtype=torch.float32, device=dev)      # dS of the steps waiting for their group to fill
+    graphs, losses = {}, []
+
+    def graph_of(k):
+        if k not in graphs:
+            graphs[k] = build_graph(k)
+        return graphs[k]
+
+    def steps(a, k):                                   # raw time steps a .. a + k - 1 as (k, N, F)
+        return node_data[:, :, a:a + k].permute(2, 0, 1).to(dev, torch.float32).contiguous()
+
+    staged = 0                                         # slabs in `stage`; they are steps done - staged .. done - 1
+    done = first                                       # the first step whose dS has not been handed on yet
+    have = 0                                           # slabs at the front of both timelines that the batch at hand inherits
+    for i in range(0, count, wb):
+        b = min(wb, count - i)
+        need = b + t_in - 1                            # the batch's windows read steps first + i .. first + i + need - 1
+        for a in range(have, need, step_batch):
+            k = min(step_batch, need - a)
+            model.period_outputs(steps(first + i + a, k), graph_of(k), out=s_line[a:a + k])
+        pred, hidden = ops.window_forward(s_line[:need], 0, b, att, l1.weight, l1.bias, l2.weight, l2.bias)
+        y = torch.stack([node_data[:, -1, k + t_in:k + t_in + t_out] for k in range(first + i, first + i + b)]).to(dev, torch.float32)
+        _, dpred = ops.mse_loss_grad(pred, y.contiguous(), n * o)        # the sum of the b window means: gradients add up as in run.py
+        losses.append(((pred - y) ** 2).view(b, -1).mean(dim=1))
+        ops.window_backward(s_line[:need], 0, b, att, l1.weight, l1.bias, l2.weight, l2.bias, hidden, dpred, ds_line[:need], True,
+                            att.grad, l1.weight.grad, l1.bias.grad, l2.weight.grad, l2.bias.grad)
+        last = i + b == count
+        complete = need if last else b                 # no later window contains the batch's first b steps
+        a = 0
+        while a < complete:
+            k = min(step_batch - staged, complete - a)
+            stage[staged:staged + k].copy_(ds_line[a:a + k])
+            staged, a, done = staged + k, a + k, done + k
+            if staged == step_batch or (last and a == complete):
+                model.period_gradients(steps(done - staged, staged), graph_of(staged), stage[:staged])
+                staged = 0
+        have = t_in - 1
+        if not last:
+            if have:
+                for line in (s_line, ds_line):
+                    line[:have].copy_(line[b:b + have].clone() if b < have else line[b:b + have])
+            ds_line[have:].zero_()
+    allreduce_gradients(list(model.parameters()))
+    optimizer.step()
+    optimizer.zero_grad()
+    all_l = torch.cat(losses)
+    return all_l[-1], list(all_l.unbind(0))
+
+
 def streamed_split(steps: int, t_in: int, t_out: int, ratio: float) -> Tuple[int, int]:
     """(first window, window count) of the test split that split() cuts from snapshot_windows()' list, from the step count alone."""
     windows = max(steps - (t_in + t_out) + 1, 0)
@@ -389,6 +487,9 @@ def add_flags(ap: argparse.ArgumentParser, only: Optional[Sequence[str]] = None)
     add("--streamed", action="store_true",
         help="RegionalTemporalGCN / RandomTemporalGCN / TemporalGCN: the per-epoch test pass computes every time step's cell output once "
              "and forms the windows from the cached outputs (evaluate_streamed; same metrics)")
+    add("--streamed_train", action="store_true",
+        help="RegionalTemporalGCN / RandomTemporalGCN / TemporalGCN: the training pass, too, runs every time step's cell forward and backward "
+             "once per epoch (train_epoch_streamed; same accumulated gradients and losses); implies --streamed for the test pass")
     return ap
 
 
@@ -430,6 +531,8 @@ def load_windows(a, dev):
         raise SystemExit("give --fixture, --dataset_root or a --dataset_path that holds the reference's dataset/ directory")
     node_data = torch.from_numpy(d["node_data"])
     n, f = node_data.shape[:2]
+    if getattr(a, "streamed_train", False):
+        return d, n, f, ([], []), ([], [])      # both passes read node_data as loaded (train_epoch_streamed, evaluate_streamed)
     if getattr(a, "streamed", False):
         # the test pass reads node_data as loaded (evaluate_streamed): only the train split's windows are built and moved
         k, _ = streamed_split(node_data.shape[2], a.num_timesteps_in, a.num_timesteps_out, a.tr)
@@ -459,6 +562,9 @@ def open_outputs(a, model_name: str):
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    if a.streamed_train:
+        refuse_streamed_train(a)
+        a.streamed = True                                     # the test pass streams as well
     if a.streamed:
         from .serve import refuse_streamed
         refuse_streamed(a.model)
@@ -555,7 +661,9 @@ def main(argv=None):
         nd = torch.from_numpy(np.asarray(d["node_data"]))
         streamed = (nd, s_graphs.get, *streamed_split(nd.shape[2], a.num_timesteps_in, a.num_timesteps_out, a.tr))
     for epoch in range(a.epochs + 1):
-        if batched:
+        if a.streamed_train:                                  # the train split: windows 0 .. k - 1 of the data as loaded
+            last, _ = train_epoch_streamed(model, streamed[0], a.num_timesteps_in, a.num_timesteps_out, streamed[1], 0, streamed[2], opt)
+        elif batched:
             last, _ = train_epoch_batched(model, batched[0], batched[2], opt, a.snap_batch)
         else:
             last, _ = train_epoch(model, tx, ty, graph, opt, stepper)
