@@ -53,7 +53,14 @@ def bf16_round(t):
     return t.to(torch.bfloat16).to(torch.float32)
 
 
-def forward_fused(p, x, a_hat, l_list, regional=True, rnd=None, store=None, round_x=False):
+def _blend(zs, h, ht):
+    return zs * h + (1 - zs) * ht
+
+
+OPS = {"sigmoid": torch.sigmoid, "tanh": torch.tanh, "mul": torch.mul, "blend": _blend}
+
+
+def forward_fused(p, x, a_hat, l_list, regional=True, rnd=None, store=None, round_x=False, tap=None, ops=None):
     """x (N,F,T).  Returns (pred, hidden) through the composed-weight formulation using autograd.
 
     ``rnd``: optional rounding applied to both operands of every activation x weight contraction that the HIP path
@@ -62,9 +69,15 @@ def forward_fused(p, x, a_hat, l_list, regional=True, rnd=None, store=None, roun
     activations the pipeline keeps in HBM between kernels (h, Z; ``bf16_round`` when that mode stores them as bf16):
     whatever reads them later -- the GRU blend here -- sees the stored value.  ``round_x``: the snapshot itself is rounded
     before it is aggregated (bf16 rows of x / A_hat x / L~ x, the cfg-5 layout of SURVEY 8(d): where the fused forward kernel
-    applies the packing kernel rounds x once and the aggregation reads and writes bf16 rows)."""
+    applies the packing kernel rounds x once and the aggregation reads and writes bf16 rows).
+
+    ``tap(name, value) -> value``: called on the named (N,T,.) intermediates ("pre", "h", "h_operand", "pz", "pr", "ph", "hn" and the head's
+    (N,.) "y1", the first layer's product in front of its bias) -- a caller's place to round the gradient that flows back through them or to plant an error (tests/bf16_probe.py).
+    ``ops``: replacements for the entries of OPS (the same values forward, another backward).  Neither changes the default result."""
     q = (lambda v: v) if rnd is None else rnd
     st = (lambda v: v) if store is None else store
+    tp = (lambda _k, v: v) if tap is None else tap
+    o = dict(OPS, **(ops or {}))
     n, f, t = x.shape
     R = len(l_list)
     w = compose(p, R, regional)
@@ -75,13 +88,16 @@ def forward_fused(p, x, a_hat, l_list, regional=True, rnd=None, store=None, roun
     pre = q(xp) @ q(w["A0"]).t() + w["b"]
     for r in range(R):
         pre = pre + q(torch.einsum("ij,jtf->itf", l_list[r], xp)) @ q(w["Ar"][r]).t()
+    pre = tp("pre", pre)
     h = st(torch.nn.functional.leaky_relu(pre, LRELU) if regional else pre)
-    z = torch.sigmoid(q(h) @ q(w["Uz"]).t() + q(ax) @ q(w["Gz"]).t() + w["cz"])
-    r_ = torch.sigmoid(q(h) @ q(w["Ur"]).t() + q(ax) @ q(w["Gr"]).t() + w["cr"])
-    ht = torch.tanh(q(h * r_) @ q(w["Uh"]).t() + q(ax) @ q(w["Gh"]).t() + w["ch"])
-    hn = st(z) * h + (1 - st(z)) * ht
+    hg = tp("h_operand", q(h))                           # the A operand of the two K = C gate contractions
+    h = tp("h", h)                                       # what the reset product and the blend read
+    z = o["sigmoid"](tp("pz", hg @ q(w["Uz"]).t() + q(ax) @ q(w["Gz"]).t() + w["cz"]))
+    r_ = o["sigmoid"](tp("pr", hg @ q(w["Ur"]).t() + q(ax) @ q(w["Gr"]).t() + w["cr"]))
+    ht = o["tanh"](tp("ph", q(o["mul"](h, r_)) @ q(w["Uh"]).t() + q(ax) @ q(w["Gh"]).t() + w["ch"]))
+    hn = tp("hn", o["blend"](st(z), h, ht))
     probs = torch.softmax(p["tgnn._attention"], dim=0)
     hidden = (hn * probs.view(1, t, 1)).sum(dim=1)
-    y = q(torch.relu(hidden)) @ q(p["linear1.weight"]).t() + p["linear1.bias"]
+    y = tp("y1", q(torch.relu(hidden)) @ q(p["linear1.weight"]).t()) + p["linear1.bias"]
     y = torch.relu(y) @ p["linear2.weight"].t() + p["linear2.bias"]
     return y, hidden

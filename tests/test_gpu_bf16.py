@@ -12,6 +12,7 @@ The reference has no bf16 path, so the tolerance is derived, not inherited:
   TOL_REL = 8 u = 1.5625e-2 of the reference tensor's max magnitude (outputs) / Frobenius norm (gradients) is the stated bar.
 A second, tight bar pins the arithmetic itself: the HIP result must agree with the CPU emulation of the same rounding to
 EMU_TOL = 1.2e-3 of the tensor's scale (what is left are fp32 summation order and operands that sit on a bf16 rounding boundary).
+Per node row and per probe node, against float64 alone: tests/test_gpu_bf16_bars.py (bars derived in tests/bf16_probe.py).
 """
 import numpy as np
 import pytest
