@@ -231,10 +231,18 @@ static int stae_check(const char* what, const regt_stae_dims* d, regt::StaeDims*
     return REGT_OK;
 }
 
+// the six embedding entries of a parameter or gradient table (node_emb, adaptive_embedding, input_proj w, b, tod, dow): those of
+// width 0 may be NULL
+static int stae_embed_table_check(const char* what, const char* kind, const regt::StaeDims& s, const void* const* p) {
+    const bool need[6] = {s.e_sp > 0, s.e_adp > 0, true, true, s.e_tod > 0, s.e_dow > 0};
+    for (int k = 0; k < 6; ++k) REGT_CHECK_ARG(!need[k] || p[k] != nullptr, "%s: %s entry %d is NULL", what, kind, k);
+    return REGT_OK;
+}
+
 static int stae_check_table(const char* what, const regt::StaeDims& s, const void* const* p) {
     REGT_CHECK_ARG(p != nullptr, "%s: parameter table is NULL", what);
-    const bool need[regt::STAE_HEAD_PARAMS] = {s.e_sp > 0, s.e_adp > 0, true, true, s.e_tod > 0, s.e_dow > 0, true, true};
-    for (int k = 0; k < regt::STAE_HEAD_PARAMS; ++k) REGT_CHECK_ARG(!need[k] || p[k] != nullptr, "%s: head entry %d is NULL", what, k);
+    if (int rc = stae_embed_table_check(what, "head", s, p)) return rc;
+    for (int k = 6; k < regt::STAE_HEAD_PARAMS; ++k) REGT_CHECK_ARG(p[k] != nullptr, "%s: head entry %d is NULL", what, k);
     for (int k = regt::STAE_HEAD_PARAMS; k < regt::STAE_HEAD_PARAMS + 2 * s.num_layers * regt::STAE_LAYER_PARAMS; ++k)
         REGT_CHECK_ARG(p[k] != nullptr, "%s: layer entry %d is NULL", what, k);
     return REGT_OK;
@@ -322,18 +330,26 @@ static int stae_attention_check(const char* what, int32_t B, int32_t T, int32_t 
     return REGT_OK;
 }
 
+// every leading dimension (`names`: "ld and ldo", in the backward "ld, ldo and ldg") covers the 32 * heads columns and keeps a
+// row's float4s aligned
+static int stae_ld_check(const char* what, int32_t heads, const char* names, std::initializer_list<int64_t> lds) {
+    const long D = (long)heads * regt::STAE_HEAD_DIM;
+    char got[96] = "";
+    bool ok = true;
+    for (int64_t ld : lds) {
+        ok = ok && ld >= D && ld % 4 == 0;
+        snprintf(got + strlen(got), sizeof got - strlen(got), "%s%ld", got[0] ? ", " : "", (long)ld);
+    }
+    REGT_CHECK_ARG(ok, "%s: %s must be multiples of 4, at least 32 * heads = %ld, got %s", what, names, D, got);
+    return REGT_OK;
+}
+
 int32_t regt_stae_attention(const float* q, const float* k, const float* v, int64_t ld, int32_t B, int32_t T, int32_t N, int32_t heads,
                             int32_t axis, float* out, int64_t ldo, regt_stream_t st) {
     REGT_CHECK_ARG(q && k && v && out, "regt_stae_attention: NULL pointer");
-    REGT_CHECK_ARG(axis == 1 || axis == 2, "regt_stae_attention: axis must be 1 (temporal) or 2 (spatial), got %d", axis);
-    REGT_CHECK_ARG(B >= 1 && T >= 1 && N >= 1, "regt_stae_attention: batch, in_steps and num_nodes must be >= 1, got %d, %d, %d", B, T, N);
-    REGT_CHECK_ARG(heads >= 1 && heads * regt::STAE_HEAD_DIM <= regt::STAE_MAX_DIM, "regt_stae_attention: heads must be in [1, %d], got %d",
-                   regt::STAE_MAX_DIM / regt::STAE_HEAD_DIM, heads);
-    const long D = (long)heads * regt::STAE_HEAD_DIM;
-    REGT_CHECK_ARG(ld >= D && ldo >= D && ld % 4 == 0 && ldo % 4 == 0, "regt_stae_attention: ld and ldo must be multiples of 4, at least 32 * heads = %ld, got %ld, %ld",
-                   D, (long)ld, (long)ldo);
+    if (int rc = stae_attention_check("regt_stae_attention", B, T, N, heads, axis)) return rc;
+    if (int rc = stae_ld_check("regt_stae_attention", heads, "ld and ldo", {ld, ldo})) return rc;
     REGT_CHECK_ARG(al16(q) && al16(k) && al16(v) && al16(out), "regt_stae_attention: q, k, v and out must be 16-byte aligned");
-    REGT_CHECK_ARG((long)B * T * N < (1L << 31) / 4, "regt_stae_attention: batch * in_steps * num_nodes is too large");
     return regt::launch_stae_attention(q, k, v, (long)ld, B, T, N, heads, axis, out, (long)ldo, (hipStream_t)st);
 }
 
@@ -341,9 +357,7 @@ int32_t regt_stae_attention_train(const float* q, const float* k, const float* v
                                   int32_t axis, float* out, int64_t ldo, float* lse, regt_stream_t st) {
     REGT_CHECK_ARG(q && k && v && out && lse, "regt_stae_attention_train: NULL pointer");
     if (int rc = stae_attention_check("regt_stae_attention_train", B, T, N, heads, axis)) return rc;
-    const long D = (long)heads * regt::STAE_HEAD_DIM;
-    REGT_CHECK_ARG(ld >= D && ldo >= D && ld % 4 == 0 && ldo % 4 == 0,
-                   "regt_stae_attention_train: ld and ldo must be multiples of 4, at least 32 * heads = %ld, got %ld, %ld", D, (long)ld, (long)ldo);
+    if (int rc = stae_ld_check("regt_stae_attention_train", heads, "ld and ldo", {ld, ldo})) return rc;
     REGT_CHECK_ARG(al16(q) && al16(k) && al16(v) && al16(out) && al16(lse), "regt_stae_attention_train: q, k, v, out and lse must be 16-byte aligned");
     return regt::launch_stae_attention(q, k, v, (long)ld, B, T, N, heads, axis, out, (long)ldo, (hipStream_t)st, lse);
 }
@@ -358,43 +372,41 @@ int32_t regt_stae_attention_backward(const float* q, const float* k, const float
                                      float* dk, float* dv, int64_t ldg, float* scratch, regt_stream_t st) {
     REGT_CHECK_ARG(q && k && v && out && dout && lse && dq && dk && dv && scratch, "regt_stae_attention_backward: NULL pointer");
     if (int rc = stae_attention_check("regt_stae_attention_backward", B, T, N, heads, axis)) return rc;
-    const long D = (long)heads * regt::STAE_HEAD_DIM;
-    REGT_CHECK_ARG(ld >= D && ldo >= D && ldg >= D && ld % 4 == 0 && ldo % 4 == 0 && ldg % 4 == 0,
-                   "regt_stae_attention_backward: ld, ldo and ldg must be multiples of 4, at least 32 * heads = %ld, got %ld, %ld, %ld", D, (long)ld,
-                   (long)ldo, (long)ldg);
+    if (int rc = stae_ld_check("regt_stae_attention_backward", heads, "ld, ldo and ldg", {ld, ldo, ldg})) return rc;
     REGT_CHECK_ARG(al16(q) && al16(k) && al16(v) && al16(out) && al16(dout) && al16(lse) && al16(dq) && al16(dk) && al16(dv) && al16(scratch),
                    "regt_stae_attention_backward: every pointer must be 16-byte aligned");
     return regt::launch_stae_attention_bwd(q, k, v, (long)ld, out, dout, (long)ldo, lse, B, T, N, heads, axis, dq, dk, dv, (long)ldg, scratch,
                                            (hipStream_t)st);
 }
 
-int32_t regt_stae_add_layernorm(const float* residual, const float* y, const float* gamma, const float* beta, float eps, int64_t M, int32_t D,
-                                float* out, regt_stream_t st) {
-    REGT_CHECK_ARG(residual && y && gamma && beta && out, "regt_stae_add_layernorm: NULL pointer");
-    REGT_CHECK_ARG(D >= 32 && D % 32 == 0 && D <= regt::STAE_MAX_DIM, "regt_stae_add_layernorm: D must be a multiple of 32 in [32, %d], got %d",
-                   regt::STAE_MAX_DIM, D);
-    REGT_CHECK_ARG(M >= 1 && M < (1L << 31), "regt_stae_add_layernorm: M must be in [1, 2^31), got %ld", (long)M);
-    REGT_CHECK_ARG(eps > 0.f, "regt_stae_add_layernorm: eps must be > 0, got %g", (double)eps);
-    return regt::launch_stae_add_layernorm(residual, y, gamma, beta, eps, (long)M, D, out, (hipStream_t)st);
-}
-
-static int stae_ln_backward_check(const char* what, int64_t M, int32_t D) {
+// The D, M and eps rules of add+LayerNorm.  The forward entries take M < 2^31 rows, the backward entries a quarter of that; the
+// scratch sizes have no eps to check and pass 1.
+constexpr long LN_FWD_ROWS = 1L << 31, LN_BWD_ROWS = (1L << 31) / 4;
+static int stae_ln_check(const char* what, int64_t M, int32_t D, float eps, long m_bound) {
     REGT_CHECK_ARG(D >= 32 && D % 32 == 0 && D <= regt::STAE_MAX_DIM, "%s: D must be a multiple of 32 in [32, %d], got %d", what,
                    regt::STAE_MAX_DIM, D);
-    REGT_CHECK_ARG(M >= 1 && M < (1L << 31) / 4, "%s: M must be in [1, 2^31 / 4), got %ld", what, (long)M);
+    REGT_CHECK_ARG(M >= 1 && M < m_bound, "%s: M must be in [1, %s), got %ld", what, m_bound == LN_FWD_ROWS ? "2^31" : "2^31 / 4", (long)M);
+    REGT_CHECK_ARG(eps > 0.f, "%s: eps must be > 0, got %g", what, (double)eps);
     return REGT_OK;
 }
 
+int32_t regt_stae_add_layernorm(const float* residual, const float* y, const float* gamma, const float* beta, float eps, int64_t M, int32_t D,
+                                float* out, regt_stream_t st) {
+    REGT_CHECK_ARG(residual && y && gamma && beta && out, "regt_stae_add_layernorm: NULL pointer");
+    if (int rc = stae_ln_check("regt_stae_add_layernorm", M, D, eps, LN_FWD_ROWS)) return rc;
+    return regt::launch_stae_add_layernorm(residual, y, gamma, beta, eps, (long)M, D, out, (hipStream_t)st);
+}
+
+
 size_t regt_stae_add_layernorm_backward_scratch_floats(int64_t M, int32_t D) {
-    if (stae_ln_backward_check("regt_stae_add_layernorm_backward_scratch_floats", M, D)) return 0;
+    if (stae_ln_check("regt_stae_add_layernorm_backward_scratch_floats", M, D, 1.f, LN_BWD_ROWS)) return 0;
     return regt::stae_add_layernorm_bwd_scratch_floats((long)M, D);
 }
 
 int32_t regt_stae_add_layernorm_backward(const float* residual, const float* y, const float* gamma, const float* dout, float eps, int64_t M,
                                          int32_t D, float* dz, float* dgamma, float* dbeta, float* scratch, regt_stream_t st) {
     REGT_CHECK_ARG(residual && y && gamma && dout && dz && dgamma && dbeta && scratch, "regt_stae_add_layernorm_backward: NULL pointer");
-    if (int rc = stae_ln_backward_check("regt_stae_add_layernorm_backward", M, D)) return rc;
-    REGT_CHECK_ARG(eps > 0.f, "regt_stae_add_layernorm_backward: eps must be > 0, got %g", (double)eps);
+    if (int rc = stae_ln_check("regt_stae_add_layernorm_backward", M, D, eps, LN_BWD_ROWS)) return rc;
     REGT_CHECK_ARG(al16(residual) && al16(y) && al16(gamma) && al16(dout) && al16(dz) && al16(dgamma) && al16(dbeta) && al16(scratch),
                    "regt_stae_add_layernorm_backward: every pointer must be 16-byte aligned");
     REGT_CHECK_ARG(dz != residual && dz != y && dz != dout, "regt_stae_add_layernorm_backward: dz must not alias residual, y or dout");
@@ -407,8 +419,7 @@ int32_t regt_stae_embed(const regt_stae_dims* d, const float* x, const float* co
     regt::StaeDims s;
     if (int rc = stae_check("regt_stae_embed", d, &s)) return rc;
     REGT_CHECK_ARG(x && out && params, "regt_stae_embed: x, out or the parameter table is NULL");
-    const bool need[6] = {s.e_sp > 0, s.e_adp > 0, true, true, s.e_tod > 0, s.e_dow > 0};
-    for (int k = 0; k < 6; ++k) REGT_CHECK_ARG(!need[k] || params[k] != nullptr, "regt_stae_embed: head entry %d is NULL", k);
+    if (int rc = stae_embed_table_check("regt_stae_embed", "head", s, reinterpret_cast<const void* const*>(params))) return rc;
     return regt::launch_stae_embed(s, x, params, out, (hipStream_t)st);
 }
 
@@ -428,8 +439,7 @@ int32_t regt_stae_embed_backward(const regt_stae_dims* d, const float* x, const 
     regt::StaeDims s;
     if (int rc = stae_check("regt_stae_embed_backward", d, &s)) return rc;
     REGT_CHECK_ARG(x && dx0 && grads && scratch, "regt_stae_embed_backward: x, dx0, the gradient table or scratch is NULL");
-    const bool need[6] = {s.e_sp > 0, s.e_adp > 0, true, true, s.e_tod > 0, s.e_dow > 0};
-    for (int k = 0; k < 6; ++k) REGT_CHECK_ARG(!need[k] || grads[k] != nullptr, "regt_stae_embed_backward: gradient entry %d is NULL", k);
+    if (int rc = stae_embed_table_check("regt_stae_embed_backward", "gradient", s, reinterpret_cast<const void* const*>(grads))) return rc;
     return regt::launch_stae_embed_bwd(s, x, dx0, grads, scratch, (hipStream_t)st);
 }
 
@@ -468,15 +478,12 @@ int32_t regt_stae_drop_add_layernorm(const float* residual, const float* y, cons
     if (int rc = stae_drop_check("regt_stae_drop_add_layernorm", keep, p)) return rc;
     if (!keep) return regt_stae_add_layernorm(residual, y, gamma, beta, eps, M, D, out, st);
     REGT_CHECK_ARG(residual && y && gamma && beta && out, "regt_stae_drop_add_layernorm: NULL pointer");
-    REGT_CHECK_ARG(D >= 32 && D % 32 == 0 && D <= regt::STAE_MAX_DIM, "regt_stae_drop_add_layernorm: D must be a multiple of 32 in [32, %d], got %d",
-                   regt::STAE_MAX_DIM, D);
-    REGT_CHECK_ARG(M >= 1 && M < (1L << 31), "regt_stae_drop_add_layernorm: M must be in [1, 2^31), got %ld", (long)M);
-    REGT_CHECK_ARG(eps > 0.f, "regt_stae_drop_add_layernorm: eps must be > 0, got %g", (double)eps);
+    if (int rc = stae_ln_check("regt_stae_drop_add_layernorm", M, D, eps, LN_FWD_ROWS)) return rc;
     return regt::launch_stae_drop_add_layernorm(residual, y, keep, 1.0f / (1.0f - p), gamma, beta, eps, (long)M, D, out, (hipStream_t)st);
 }
 
 size_t regt_stae_drop_add_layernorm_backward_scratch_floats(int64_t M, int32_t D) {
-    if (stae_ln_backward_check("regt_stae_drop_add_layernorm_backward_scratch_floats", M, D)) return 0;
+    if (stae_ln_check("regt_stae_drop_add_layernorm_backward_scratch_floats", M, D, 1.f, LN_BWD_ROWS)) return 0;
     return regt::stae_add_layernorm_bwd_scratch_floats((long)M, D);
 }
 
@@ -486,8 +493,7 @@ int32_t regt_stae_drop_add_layernorm_backward(const float* residual, const float
     if (int rc = stae_drop_check("regt_stae_drop_add_layernorm_backward", keep, p)) return rc;
     if (!keep) return regt_stae_add_layernorm_backward(residual, y, gamma, dout, eps, M, D, dz, dgamma, dbeta, scratch, st);
     REGT_CHECK_ARG(residual && y && gamma && dout && dz && dy && dgamma && dbeta && scratch, "regt_stae_drop_add_layernorm_backward: NULL pointer");
-    if (int rc = stae_ln_backward_check("regt_stae_drop_add_layernorm_backward", M, D)) return rc;
-    REGT_CHECK_ARG(eps > 0.f, "regt_stae_drop_add_layernorm_backward: eps must be > 0, got %g", (double)eps);
+    if (int rc = stae_ln_check("regt_stae_drop_add_layernorm_backward", M, D, eps, LN_BWD_ROWS)) return rc;
     REGT_CHECK_ARG(al16(residual) && al16(y) && al16(gamma) && al16(dout) && al16(dz) && al16(dy) && al16(dgamma) && al16(dbeta) && al16(scratch),
                    "regt_stae_drop_add_layernorm_backward: every float pointer must be 16-byte aligned");
     REGT_CHECK_ARG(dz != residual && dz != y && dz != dout && dy != residual && dy != y && dy != dout && dy != dz,

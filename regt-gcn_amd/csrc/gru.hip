@@ -7,7 +7,8 @@
 // their partial sums in LDS and every thread finishes two (row, unit) pairs in a fixed order.  The input projection (K = T <= 255)
 // is part of the step.  The backward is the same shape run in reverse; the weight gradients are contractions over all steps and
 // rows, formed afterwards per row chunk and summed in chunk order: no float atomics anywhere, two runs give the same bits.
-#include "kernels.h"
+#include "lane_helpers.h"
+#include "slab_reduce.h"
 
 namespace regt {
 
@@ -35,8 +36,6 @@ struct FwdArgs {
     const float *x, *whhp, *wihp, *b_ih, *b_hh, *h0;
     float *out, *h_last, *hs, *gates;
 };
-
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
 
 // acc[p] += lds[k][2p .. 2p+1] * w for the RT rows of one k (rows are the minor index of the LDS tile)
 __device__ __forceinline__ void load_rows(const float* p, f32x2 (&v)[RT / 2]) {
@@ -141,7 +140,7 @@ __global__ __launch_bounds__(THREADS) void gru_fwd_kernel(const FwdArgs a) {
                 for (int qq = 1; qq < KS; ++qq) v += part[((qq * 4 + g) * RT + r) * H + j];
                 s[g] = v;
             }
-            const float rg = sigmoidf_(s[0] + bi_r), zg = sigmoidf_(s[1] + bi_z), hn = s[2] + b_hn;
+            const float rg = sigm(s[0] + bi_r), zg = sigm(s[1] + bi_z), hn = s[2] + b_hn;
             const float ng = tanhf(s[3] + b_in + rg * hn);
             const float hp = h_s[j * RT + r], hnew = (1.f - zg) * ng + zg * hp;
             h_s[j * RT + r] = hnew;
@@ -316,15 +315,6 @@ __global__ __launch_bounds__(256) void gru_wgrad_kernel(const WgArgs a) {
     if (blockIdx.y == 0 && tid < 64) sl[(long)G * a.nin + c0 + tid] = csum;
 }
 
-__global__ void gru_wgrad_reduce_kernel(const float* __restrict__ slab, int nchunks, long nw, float* __restrict__ dw, float* __restrict__ db) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nw + G) return;
-    float v = slab[i];
-    for (int c = 1; c < nchunks; ++c) v += slab[(long)c * (nw + G) + i];
-    if (i < nw) dw[i] = v;
-    else db[i - nw] = v;
-}
-
 __global__ void relu_mask_kernel(const float* __restrict__ y, float* __restrict__ d, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && !(y[i] > 0.f)) d[i] = 0.f;
@@ -432,9 +422,10 @@ int launch_gru_bwd(const GruDims& s, const float* x, const float* w_hh, const fl
         hipLaunchKernelGGL(gru_wgrad_kernel, dim3(G / 64, cdiv(w.nin, 64), nchunks), dim3(256), 0, st, w);
         REGT_CHECK_LAUNCH();
         const long nw = (long)G * w.nin;
-        hipLaunchKernelGGL(gru_wgrad_reduce_kernel, dim3(cdiv(nw + G, 256)), dim3(256), 0, st, w.slab, nchunks, nw, grads[pass],
-                           grads[2 + pass]);
-        REGT_CHECK_LAUNCH();
+        SlabSegs sg{};
+        add_seg(sg, grads[pass], nw);
+        add_seg(sg, grads[2 + pass], G);
+        if (int rc = launch_slab_reduce_final<true>(w.slab, nchunks, nw + G, sg, st)) return rc;      // the chunks in order, seeded with chunk 0
     }
     return REGT_OK;
 }

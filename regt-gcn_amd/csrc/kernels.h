@@ -465,14 +465,9 @@ int launch_stae_add_layernorm_bwd(const float* residual, const float* y, const f
                                   float* dz, float* dgamma, float* dbeta, float* scratch, hipStream_t st, const uint32_t* keep = nullptr,
                                   float s = 1.0f, float* dy = nullptr);
 int launch_stae_output_proj(const StaeDims& s, const float* x, const float* w, const float* bias, float* out, hipStream_t st);
-// Column sums of (nparts, width) partial rows in 256 interleaved running sums combined pairwise; segment k of the result, columns
-// [end[k-1], end[k]), goes to out[k].
-struct ColSegs {
-    static constexpr int MAX = 4;
-    float* out[MAX];
-    long end[MAX];
-};
-int launch_stae_col_reduce(const float* partial, long nparts, long width, const ColSegs& segs, hipStream_t st);
+// Column sums of (nparts, width) partial rows in 256 interleaved running sums combined pairwise, scattered by segment (slab_reduce.h)
+struct SlabSegs;
+int launch_stae_col_reduce(const float* partial, long nparts, long width, const SlabSegs& segs, hipStream_t st);
 // STAEformer whole-model training (staeformer_train.hip): keep-bit dropout folded into add+LayerNorm, and the gradients of the
 // embedding and of the output projection.  grads of the embedding: node_emb, adaptive_embedding, input_proj w, b, tod, dow (the first
 // six table entries; NULL where the width is 0).  dout of the output projection is read through four element strides.

@@ -14,9 +14,9 @@
 //             stores of S.
 //   backward: A = rows, B = weights (same registers, roles swapped): lane holds channel (lane & 15) of nodes 4q..4q+3, which is
 //             directly the A operand of dW = dG^T [x | L~ x] (the MFMA sums over q, i.e. over 4 nodes per step).  Partial dW / db
-//             per wave go to a slab, reduced in a fixed order by two small kernels (no float atomics: bit-reproducible).
+//             per wave go to a slab, reduced in a fixed order by the two stages of slab_reduce.h (no float atomics: bit-reproducible).
 // Keep mask: uint32 (N*T, 2), row node*T + t, bit j of word w keeps channel 32w + j.
-#include "kernels.h"
+#include "slab_reduce.h"
 
 namespace regt {
 
@@ -233,35 +233,6 @@ __global__ __launch_bounds__(256) void spatial_bwd_kernel(const float* __restric
     }
 }
 
-// stage 1: part[chunk][i] = sum of the wave rows [chunk*SP_CHUNK, ...) in order
-__global__ __launch_bounds__(256) void spatial_reduce_chunks(const float* __restrict__ slab, int nwaves, long stride,
-                                                             float* __restrict__ part) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= stride) return;
-    const int w0 = blockIdx.y * SP_CHUNK, w1 = min(w0 + SP_CHUNK, nwaves);
-    float v[SP_CHUNK];
-#pragma unroll
-    for (int k = 0; k < SP_CHUNK; ++k) v[k] = w0 + k < w1 ? slab[(long)(w0 + k) * stride + i] : 0.f;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < SP_CHUNK; ++k) s += v[k];
-    part[(long)blockIdx.y * stride + i] = s;
-}
-
-// stage 2: the chunk sums in order, scattered to dW0 / dW1 / db
-__global__ __launch_bounds__(256) void spatial_reduce_final(const float* __restrict__ part, int nchunks, int F, float* __restrict__ dw0,
-                                                            float* __restrict__ dw1, float* __restrict__ db) {
-    const long stride = slab_stride(F);
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= stride) return;
-    float s = 0.f;
-    for (int k = 0; k < nchunks; ++k) s += part[(long)k * stride + i];
-    const long wsz = (long)SP_C * F;
-    if (i < wsz) dw0[i] = s;
-    else if (i < 2 * wsz) dw1[i - wsz] = s;
-    else db[i - 2 * wsz] = s;
-}
-
 struct BwdPlan { int tiles_per_wave, nwaves, nchunks; };
 
 BwdPlan bwd_plan(int N) {
@@ -320,12 +291,11 @@ int launch_spatial_bwd(const float* x, const float* lx, const float* w0, const f
     }
     if (rc != REGT_OK) return rc;
     const long stride = slab_stride(F);
-    float* part = slab + (long)pl.nwaves * stride;
-    hipLaunchKernelGGL(spatial_reduce_chunks, dim3(cdiv(stride, 256), pl.nchunks), dim3(256), 0, st, slab, pl.nwaves, stride, part);
-    REGT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(spatial_reduce_final, dim3(cdiv(stride, 256)), dim3(256), 0, st, part, pl.nchunks, F, dw0, dw1, db);
-    REGT_CHECK_LAUNCH();
-    return REGT_OK;
+    SlabSegs sg{};
+    add_seg(sg, dw0, (long)SP_C * F);
+    add_seg(sg, dw1, (long)SP_C * F);
+    add_seg(sg, db, SP_C);
+    return launch_slab_reduce_chunked<SP_CHUNK>(slab, pl.nwaves, stride, slab + (long)pl.nwaves * stride, sg, st);
 }
 
 }  // namespace regt

@@ -4,16 +4,13 @@
 // once as templates.  The backward recomputes a row's mean and rstd with the very code the forward ran, so it gets the forward's bits.
 #pragma once
 #include "kernels.h"
+#include "lane_helpers.h"
 
 namespace regt {
 namespace stae {
 
 constexpr int THREADS = 256;
 constexpr int QT = 32;                    // queries per wave, keys per tile
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-// row of accumulator register i within the 32 x 32 result (the column is lane & 31)
-__device__ __forceinline__ int crow(int i, int lh) { return (i & 3) + 8 * (i >> 2) + 4 * lh; }
 
 // 16 consecutive floats at p (16-byte aligned) or zeros
 __device__ __forceinline__ void load16(float (&r)[16], const float* p, bool live) {
@@ -22,12 +19,6 @@ __device__ __forceinline__ void load16(float (&r)[16], const float* p, bool live
         const float4 v = live ? reinterpret_cast<const float4*>(p)[j] : make_float4(0.f, 0.f, 0.f, 0.f);
         r[4 * j] = v.x, r[4 * j + 1] = v.y, r[4 * j + 2] = v.z, r[4 * j + 3] = v.w;
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {          // every lane gets the same sum, in one fixed order
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 // (long)v clamped into [0, size): truncation toward zero; negative and NaN give 0.  The embedding forward reads the table row this

@@ -25,11 +25,12 @@
 // Add+LayerNorm backward.  One wave per row recomputes z = residual + y, its mean and rstd with the forward's own code
 // (ln_centre_row), x^ = (z - mean) rstd, g = dout gamma, and writes dz = rstd (g - mean(g) - x^ mean(g x^)), the gradient of both
 // residual and y.  x^ comes from the inputs: nothing is divided by gamma.  dgamma = sum_rows dout x^ and dbeta = sum_rows dout: a
-// wave carries its 16 consecutive rows in registers and writes one partial row of 2 D floats; stae_col_reduce_kernel then sums each
+// wave carries its 16 consecutive rows in registers and writes one partial row of 2 D floats; slab_reduce_tree then sums each
 // column's partials in 256 interleaved running sums combined pairwise (the split csrc/stnorm.hip's op_accumulate uses, for the
 // same reason: one running sum over all M rows loses the bits a cancelling column needs).  The kernel is a template of stae_rows.h:
 // its DROP instance also writes dy = keep dz s, the gradient of a branch that went through keep-bit dropout, in the same pass.  The
 // column reduction (launch_stae_col_reduce) also serves the embedding and output-projection gradients of staeformer_train.hip.
+#include "slab_reduce.h"
 #include "stae_rows.h"
 
 namespace regt {
@@ -194,28 +195,6 @@ __global__ __launch_bounds__(THREADS) void stae_attention_dkv_kernel(const AttnB
     }
 }
 
-// one workgroup per column c of the (nparts, width) partials: thread t adds partials t, t + 256, ... in order, then a pairwise tree
-__global__ __launch_bounds__(THREADS) void stae_col_reduce_kernel(const float* __restrict__ partial, long nparts, long width, const ColSegs segs) {
-    __shared__ float sm[THREADS];
-    const long c = blockIdx.x;
-    float s = 0.f;
-    for (long w = threadIdx.x; w < nparts; w += THREADS) s += partial[w * width + c];
-    sm[threadIdx.x] = s;
-    __syncthreads();
-    for (int half = THREADS / 2; half >= 1; half >>= 1) {
-        if ((int)threadIdx.x < half) sm[threadIdx.x] += sm[threadIdx.x + half];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        long lo = 0;
-#pragma unroll
-        for (int k = 0; k < ColSegs::MAX; ++k) {
-            if (c >= lo && c < segs.end[k]) segs.out[k][c - lo] = sm[0];
-            lo = segs.end[k] > lo ? segs.end[k] : lo;
-        }
-    }
-}
-
 }  // namespace
 
 size_t stae_attention_bwd_scratch_floats(long M, int heads) { return (size_t)M * heads; }
@@ -239,10 +218,10 @@ int launch_stae_attention_bwd(const float* q, const float* k, const float* v, lo
     return REGT_OK;
 }
 
-// out segment k takes columns [end[k-1], end[k]) of the summed partials (an empty segment has end[k] == end[k-1])
-int launch_stae_col_reduce(const float* partial, long nparts, long width, const ColSegs& segs, hipStream_t st) {
+// one workgroup per column of the (nparts, width) partials, slab_reduce.h's interleaved-plus-tree order
+int launch_stae_col_reduce(const float* partial, long nparts, long width, const SlabSegs& segs, hipStream_t st) {
     REGT_CHECK_ARG(width >= 1 && width < (1L << 31), "stae column reduction: %ld columns exceed the grid", width);
-    hipLaunchKernelGGL(stae_col_reduce_kernel, dim3((unsigned)width), dim3(THREADS), 0, st, partial, nparts, width, segs);
+    hipLaunchKernelGGL(slab_reduce_tree<THREADS>, dim3((unsigned)width), dim3(THREADS), 0, st, partial, nparts, width, segs);
     REGT_CHECK_LAUNCH();
     return REGT_OK;
 }
@@ -260,8 +239,9 @@ int launch_stae_add_layernorm_bwd(const float* residual, const float* y, const f
         hipLaunchKernelGGL(stae_add_layernorm_bwd_kernel<false>, dim3((unsigned)blocks), dim3(THREADS), 0, st, residual, y, nullptr, 1.0f, gamma,
                            dout, eps, M, D, dz, nullptr, scratch);
     REGT_CHECK_LAUNCH();
-    ColSegs segs{};
-    segs.out[0] = dgamma, segs.end[0] = D, segs.out[1] = dbeta, segs.end[1] = 2 * D, segs.end[2] = segs.end[3] = 2 * D;
+    SlabSegs segs{};
+    add_seg(segs, dgamma, D);
+    add_seg(segs, dbeta, D);
     return launch_stae_col_reduce(scratch, nwaves, 2 * D, segs, st);
 }
 

@@ -30,6 +30,7 @@
 //   running sums combined pairwise, because one running sum over all B N pairs loses the bits a cancelling column needs.  NCH = 64
 //   ceil(J / 16): the partials cost at most an eighth of the floats moved.
 //   Byte floor: X read once, dX written once (2 M D floats), W and dW touched once (2 J K).
+#include "slab_reduce.h"
 #include "stae_rows.h"
 
 namespace regt {
@@ -204,12 +205,11 @@ int launch_stae_embed_bwd(const StaeDims& s, const float* x, const float* dx0, f
     const int threads = 64 * ((s.e_in + s.e_tod + s.e_dow + 63) / 64);                // <= THREADS: the three widths sum to at most D <= 256
     hipLaunchKernelGGL(stae_embed_bwd_chunk_kernel, dim3((unsigned)nchunks), dim3(threads), (size_t)P * sizeof(float), st, a);
     REGT_CHECK_LAUNCH();
-    ColSegs segs{};
-    long end = 0;
-    segs.out[0] = G[2], segs.end[0] = end += (long)s.e_in * s.input_dim;
-    segs.out[1] = G[3], segs.end[1] = end += s.e_in;
-    segs.out[2] = G[4], segs.end[2] = end += (long)s.steps_per_day * s.e_tod;
-    segs.out[3] = G[5], segs.end[3] = end += (long)s.days_per_week * s.e_dow;
+    SlabSegs segs{};
+    add_seg(segs, G[2], (long)s.e_in * s.input_dim);
+    add_seg(segs, G[3], s.e_in);
+    add_seg(segs, G[4], (long)s.steps_per_day * s.e_tod);      // empty (and G[4] NULL) where the width is 0
+    add_seg(segs, G[5], (long)s.days_per_week * s.e_dow);
     if (int rc = launch_stae_col_reduce(scratch, nchunks, P, segs, st)) return rc;
     const long owners = (long)s.num_nodes * s.e_sp + (long)s.in_steps * s.num_nodes * s.e_adp;
     if (owners > 0) {
@@ -244,8 +244,9 @@ int launch_stae_output_proj_bwd(const StaeDims& s, const float* x, const float* 
     else
         hipLaunchKernelGGL(stae_output_proj_bwd_kernel<64>, grid, block, 0, st, a);
     REGT_CHECK_LAUNCH();
-    ColSegs segs{};
-    segs.out[0] = dw, segs.end[0] = a.J * K, segs.out[1] = db, segs.end[1] = a.PW, segs.end[2] = segs.end[3] = a.PW;
+    SlabSegs segs{};
+    add_seg(segs, dw, a.J * K);
+    add_seg(segs, db, a.J);
     return launch_stae_col_reduce(scratch, nchunks, a.PW, segs, st);
 }
 

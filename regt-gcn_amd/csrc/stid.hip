@@ -23,7 +23,8 @@
 //
 // Limits (checked by regt_stid_* before any launch): embed_dim == node_dim == 32; 1 <= num_layer <= 8; 1 <= input_len <= 255;
 // 1 <= input_dim <= in_features <= 256; input_dim * input_len <= 192; 1 <= output_len <= 64; num_nodes, batch >= 1.
-#include "kernels.h"
+#include "lane_helpers.h"
+#include "slab_reduce.h"
 
 namespace regt {
 
@@ -47,8 +48,6 @@ struct Args {
     float* dnode;
 };
 
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
 // acc (32 x 32) += A (32 x K) B (K x 32); fa(k) / fb(k) give this lane's A[lane & 31][k] / B[k][lane & 31]; K even
 template <class FA, class FB>
 __device__ __forceinline__ f32x16 gemm(f32x16 acc, int K, int lh, FA fa, FB fb) {
@@ -65,9 +64,6 @@ __device__ __forceinline__ f32x16 gemm(f32x16 acc, int K, int lh, FA fa, FB fb) 
     for (; k0 < K; k0 += 2) acc = mfma32(fa(k0 + lh), fb(k0 + lh), acc);
     return acc;
 }
-
-// row of accumulator register i within the 32 x 32 result (the column is lane & 31)
-__device__ __forceinline__ int crow(int i, int lh) { return (i & 3) + 8 * (i >> 2) + 4 * lh; }
 
 __device__ __forceinline__ f32x16 splat(float v) {
     f32x16 r;
@@ -380,28 +376,12 @@ __global__ __launch_bounds__(THREADS) void stid_bwd_kernel(const Args a) {
     }
 }
 
-struct Segs {
-    int n;
-    int end[3 + 4 * STID_MAX_LAYERS + 2];
-    float* dst[3 + 4 * STID_MAX_LAYERS + 2];
-};
-
-// grads = the slabs summed in workgroup order; dnode_emb = the per-batch rows summed in batch order
-__global__ void stid_reduce_kernel(const float* __restrict__ slab, int G, int P, Segs sg, const float* __restrict__ dnode, int B, long N32,
-                                   float* __restrict__ gnode) {
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < P) {
-        float v = 0.f;
-        for (int g = 0; g < G; ++g) v += slab[(long)g * P + e];
-        int s = 0, start = 0;
-        while (s < sg.n - 1 && e >= sg.end[s]) start = sg.end[s++];
-        sg.dst[s][e - start] = v;
-    } else if (gnode && e - P < N32) {
-        const long i = e - P;
-        float v = 0.f;
-        for (int b = 0; b < B; ++b) v += dnode[b * N32 + i];
-        gnode[i] = v;
-    }
+// grads = the slabs summed in workgroup order; dnode_emb = the per-batch rows summed in batch order, in the same launch
+__global__ __launch_bounds__(256) void stid_reduce_kernel(const float* __restrict__ slab, int G, int P, const SlabSegs sg,
+                                                          const float* __restrict__ dnode, int B, long N32, float* __restrict__ gnode) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e < P) slab_scatter(sg, e, slab_col_sum<false>(slab, G, P, e));
+    else if (gnode && e - P < N32) gnode[e - P] = slab_col_sum<false>(dnode, B, N32, e - P);
 }
 
 int hidden(const StidDims& s) { return s.embed_dim + (s.if_node ? s.node_dim : 0); }
@@ -461,22 +441,17 @@ int launch_stid_bwd(const StidDims& s, const float* x, const float* const* P, co
         if (int rc = want_dynamic_lds<&stid_bwd_kernel>(LDS_BYTES)) return rc;
     hipLaunchKernelGGL(stid_bwd_kernel, dim3(grid), dim3(THREADS), bytes, st, a);
     REGT_CHECK_LAUNCH();
-    Segs sg{};
-    auto seg = [&](float* dst, int count) {
-        sg.dst[sg.n] = dst;
-        sg.end[sg.n] = (sg.n ? sg.end[sg.n - 1] : 0) + count;
-        ++sg.n;
-    };
-    seg(G[1], 32 * a.Kin);
-    seg(G[2], 32);
+    SlabSegs sg{};
+    add_seg(sg, G[1], 32 * a.Kin);
+    add_seg(sg, G[2], 32);
     for (int l = 0; l < a.NL; ++l) {
-        seg(G[3 + 4 * l], hd * hd);
-        seg(G[4 + 4 * l], hd);
-        seg(G[5 + 4 * l], hd * hd);
-        seg(G[6 + 4 * l], hd);
+        add_seg(sg, G[3 + 4 * l], hd * hd);
+        add_seg(sg, G[4 + 4 * l], hd);
+        add_seg(sg, G[5 + 4 * l], hd * hd);
+        add_seg(sg, G[6 + 4 * l], hd);
     }
-    seg(G[3 + 4 * a.NL], a.O * hd);
-    seg(G[4 + 4 * a.NL], a.O);
+    add_seg(sg, G[3 + 4 * a.NL], a.O * hd);
+    add_seg(sg, G[4 + 4 * a.NL], a.O);
     const long n32 = s.if_node ? (long)a.N * 32 : 0;
     hipLaunchKernelGGL(stid_reduce_kernel, dim3(cdiv(a.P + n32, 256)), dim3(256), 0, st, a.slab, grid, a.P, sg, a.dnode, a.B, n32,
                        s.if_node ? G[0] : nullptr);

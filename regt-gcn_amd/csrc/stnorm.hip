@@ -20,7 +20,8 @@
 // launch through a second seam.  Weight gradients: each wave stages its 64 rows in LDS and accumulates the outer products into its
 // own slab row (each lane owns fixed entries, rows summed in order); the slab rows are then reduced in a fixed order.  No float
 // atomics anywhere: the gradients are bit-reproducible.
-#include "kernels.h"
+#include "lane_helpers.h"
+#include "slab_reduce.h"
 
 namespace regt {
 
@@ -31,8 +32,6 @@ constexpr int WV = 64;                 // nodes per workgroup (one wave)
 constexpr float ST_EPS = 1e-5f;
 constexpr float ST_MOM = 0.1f;
 constexpr int RED_CHUNK = 32;
-
-__device__ __forceinline__ float sigm(float v) { return 1.f / (1.f + expf(-v)); }
 
 // (na, ma, Ma) <- (na, ma, Ma) + (nb, mb, Mb): Chan et al.'s pairwise update of count, mean and sum of squared deviations
 __device__ __forceinline__ void chan(float& na, float& ma, float& Ma, float nb, float mb, float Mb) {
@@ -50,12 +49,6 @@ __device__ __forceinline__ void chan_wave(float& n, float& m, float& M) {
         const float n2 = __shfl_xor(n, off), m2 = __shfl_xor(m, off), M2 = __shfl_xor(M, off);
         chan(n, m, M, n2, m2, M2);
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 struct Dims {
@@ -635,31 +628,6 @@ __global__ __launch_bounds__(WV) void st_start_bwd(StartBwdArgs a) {
         }
 }
 
-// slab reduction in a fixed order: stage 1 sums RED_CHUNK wave rows, stage 2 the chunks, scattered to the gradient tensors
-__global__ __launch_bounds__(256) void st_reduce_chunks(const float* __restrict__ slab, int nw, int E, float* __restrict__ part) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    const int w0 = blockIdx.y * RED_CHUNK, w1 = min(w0 + RED_CHUNK, nw);
-    float s = 0.f;
-    for (int w = w0; w < w1; ++w) s += slab[(long)w * E + e];
-    part[(long)blockIdx.y * E + e] = s;
-}
-
-struct Segs {
-    float* p[8];
-    int off[9];
-    int n;
-};
-
-__global__ __launch_bounds__(256) void st_reduce_final(const float* __restrict__ part, int nchunks, int E, Segs sg) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    float s = 0.f;
-    for (int k = 0; k < nchunks; ++k) s += part[(long)k * E + e];
-    for (int i = 0; i < sg.n; ++i)
-        if (e >= sg.off[i] && e < sg.off[i + 1]) sg.p[i][e - sg.off[i]] = s;
-}
-
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 
 struct Plan {
@@ -743,25 +711,15 @@ LayerP layer_params(const Plan& pl, const float* const* P, float* const* run, in
     return p;
 }
 
-int reduce_slab(const Plan& pl, float* slab, float* part, int E, const Segs& sg, hipStream_t st) {
-    hipLaunchKernelGGL(st_reduce_chunks, dim3(cdiv(E, 256), pl.nchunks), dim3(256), 0, st, slab, pl.d.nw, E, part);
-    REGT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(st_reduce_final, dim3(cdiv(E, 256)), dim3(256), 0, st, part, pl.nchunks, E, sg);
-    REGT_CHECK_LAUNCH();
-    return REGT_OK;
+// slab reduction in a fixed order: stage 1 sums RED_CHUNK wave rows, stage 2 the chunks, scattered to the gradient tensors
+int reduce_slab(const Plan& pl, float* slab, float* part, int E, const SlabSegs& sg, hipStream_t st) {
+    return launch_slab_reduce_chunked<RED_CHUNK>(slab, pl.d.nw, E, part, sg, st);
 }
 
 void add_block(OpBlocks& ob, int a, int na, int b, int nb) {
     ob.a[ob.nblk] = a, ob.na[ob.nblk] = na, ob.b[ob.nblk] = b, ob.nb[ob.nblk] = nb;
     ++ob.nblk;
     ob.E += na * nb;
-}
-
-void add_seg(Segs& sg, float* p, int size) {
-    if (sg.n == 0) sg.off[0] = 0;
-    sg.p[sg.n] = p;
-    sg.off[sg.n + 1] = sg.off[sg.n] + size;
-    ++sg.n;
 }
 
 // LDS rows of the head / start-conv backward grow with out_dim / in_dim: past 64 KB the kernel's limit is raised to what ST_MAX_CH needs
@@ -866,7 +824,7 @@ int launch_stnorm_bwd(const StnDims& s, const float* x, const float* const* P, f
             if (int rc = want_dynamic_lds<&st_head_bwd>(HEAD_LDS_MAX)) return rc;
         hipLaunchKernelGGL(st_head_bwd, dim3(d.nw), dim3(WV), bytes, st, h);
         REGT_CHECK_LAUNCH();
-        Segs sg{};
+        SlabSegs sg{};
         add_seg(sg, Gr[4], O * SC);
         add_seg(sg, Gr[5], O);
         add_seg(sg, Gr[2], SC * SC);
@@ -911,7 +869,7 @@ int launch_stnorm_bwd(const StnDims& s, const float* x, const float* const* P, f
             default: rc = layer_bwd_nz<true, true>(a, st); break;
         }
         if (rc) return rc;
-        Segs sg{};
+        SlabSegs sg{};
         add_seg(sg, g[0], SC * 2 * K);
         add_seg(sg, g[2], SC * 2 * K);
         add_seg(sg, g[4], SC * SC);
@@ -948,7 +906,7 @@ int launch_stnorm_bwd(const StnDims& s, const float* x, const float* const* P, f
         if (int rc = want_dynamic_lds<&st_start_bwd>(START_LDS_MAX)) return rc;
     hipLaunchKernelGGL(st_start_bwd, dim3(d.nw), dim3(WV), bytes, st, sb);
     REGT_CHECK_LAUNCH();
-    Segs sg{};
+    SlabSegs sg{};
     add_seg(sg, Gr[0], SC * d.Cin);
     add_seg(sg, Gr[1], SC);
     return reduce_slab(pl, slab, part, sb.ob.E, sg, st);

@@ -286,8 +286,9 @@ def spatial_embed_forward(xp: torch.Tensor, lxp: torch.Tensor, w0: torch.Tensor,
 
 
 def spatial_embed_backward(xp: torch.Tensor, lxp: torch.Tensor, w0: torch.Tensor, w1: torch.Tensor, bias: torch.Tensor,
-                           keep: Optional[torch.Tensor], ds: torch.Tensor):
-    """(dW0, dW1, db) of :func:`spatial_embed_forward` given dL/dS (N, 64)."""
+                           keep: Optional[torch.Tensor], ds: torch.Tensor, return_scratch: bool = False):
+    """(dW0, dW1, db) of :func:`spatial_embed_forward` given dL/dS (N, 64); with ``return_scratch`` also the slab the kernels left
+    (per-wave partial rows, then the chunk sums), for tests of the reduction order."""
     xp, lxp = _f32c(xp, "x_packed"), _f32c(lxp, "lx_packed")
     w0, w1, bias, ds = _f32c(w0, "w0"), _f32c(w1, "w1"), _f32c(bias, "bias"), _f32c(ds, "ds")
     n, t, f = xp.shape
@@ -303,7 +304,7 @@ def spatial_embed_backward(xp: torch.Tensor, lxp: torch.Tensor, w0: torch.Tensor
     _lib.check(lib.regt_spatial_embed_backward(_lib.ptr(xp), _lib.ptr(lxp), _lib.ptr(w0), _lib.ptr(w1), _lib.ptr(bias),
                                                _keep_ptr(keep, n * t, xp.device), _lib.ptr(ds), n, t, f, _lib.ptr(dw0), _lib.ptr(dw1),
                                                _lib.ptr(db), _lib.ptr(slab), _stream()), "regt_spatial_embed_backward")
-    return dw0, dw1, db
+    return (dw0, dw1, db, slab) if return_scratch else (dw0, dw1, db)
 
 
 # ---- STNorm (models/STNorm.py) -------------------------------------------------------------------------------------------------------
@@ -516,9 +517,11 @@ def stid_forward(dims: _lib.StidDims, x: torch.Tensor, params, keep: Optional[to
     return out, ws
 
 
-def stid_backward(dims: _lib.StidDims, x: torch.Tensor, params, keep: Optional[torch.Tensor], dout: torch.Tensor, ws: torch.Tensor):
+def stid_backward(dims: _lib.StidDims, x: torch.Tensor, params, keep: Optional[torch.Tensor], dout: torch.Tensor, ws: torch.Tensor,
+                  return_scratch: bool = False):
     """Gradients of every entry of ``params`` (None where the entry is None) from dL/dout; ``ws`` is the forward's workspace and
-    ``keep`` the keep bits it ran with."""
+    ``keep`` the keep bits it ran with.  With ``return_scratch``: (gradients, scratch), the scratch as the kernels left it (the
+    workgroups' slabs, then the per-batch node-embedding rows), for tests of the reduction order."""
     x, dout = _stid_x(dims, x), _f32c(dout, "dout")
     stid_check_tables(dims, x.device, params, "regt_stid_backward")
     kp = _stid_keep_ptr(dims, keep, x.device)
@@ -530,7 +533,7 @@ def stid_backward(dims: _lib.StidDims, x: torch.Tensor, params, keep: Optional[t
     grads = [None if p is None else torch.empty_like(p) for p in params]
     _lib.check(_lib.load().regt_stid_backward(ctypes.byref(dims), _lib.ptr(x), _ptr_table(params), kp, _lib.ptr(dout), _ptr_table(grads),
                                               _lib.ptr(ws), _lib.ptr(sc), _stream()), "regt_stid_backward")
-    return grads
+    return (grads, sc) if return_scratch else grads
 
 
 # ---- GRU layer and StackedGRU (models/StackedGRU.py) ---------------------------------------------------------------------------------
@@ -609,9 +612,10 @@ def gru_forward(x: torch.Tensor, weights, h0: Optional[torch.Tensor] = None, wan
 
 
 def gru_backward(dims: _lib.GruDims, x: torch.Tensor, weights, dout: Optional[torch.Tensor], dh_last: Optional[torch.Tensor],
-                 ws: torch.Tensor, want_dh0: bool = False):
+                 ws: torch.Tensor, want_dh0: bool = False, return_scratch: bool = False):
     """(gradients of weight_ih, weight_hh, bias_ih, bias_hh; dh0 (1, rows, 256) | None) from dL/dout and / or dL/dh_last; ``dims``
-    and ``ws`` are what gru_forward(save=True) returned for the same x."""
+    and ``ws`` are what gru_forward(save=True) returned for the same x.  With ``return_scratch`` a third entry: the scratch as the
+    kernels left it (its tail is the hidden gradients' slab), for tests of the reduction order."""
     x = _gru_x(x)
     if tuple(x.shape) != (dims.seq_len, dims.rows, dims.input_size) or tuple(x.stride()) != (dims.x_stride_seq, dims.x_stride_row,
                                                                                              dims.x_stride_t):
@@ -630,7 +634,7 @@ def gru_backward(dims: _lib.GruDims, x: torch.Tensor, weights, dout: Optional[to
     dh0 = torch.empty(1, dims.rows, GRU_HIDDEN, dtype=torch.float32, device=x.device) if want_dh0 else None
     _lib.check(_lib.load().regt_gru_backward(ctypes.byref(dims), _lib.ptr(x), _ptr_table(weights), None, _lib.ptr(dout), _lib.ptr(dh_last),
                                              _ptr_table(grads), _lib.ptr(dh0), _lib.ptr(ws), _lib.ptr(sc), _stream()), "regt_gru_backward")
-    return grads, dh0
+    return (grads, dh0, sc) if return_scratch else (grads, dh0)
 
 
 def relu_backward_(y: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
