@@ -270,7 +270,7 @@ def gat_case(f, t, n=GAT_NODES, slope=0.2):
             "dud64": ud64.grad, "out32": out32.detach(), "dus32": us32.grad, "dud32": ud32.grad}
 
 
-GAT_OUT_BAR = 1e-5             # absolute, on a convex combination of values in [0, 1)
+GAT_OUT_BAR = 1e-5             # absolute, on a convex combination of values in [0, 1); the arithmetic's own per-row bars: gat_math.py
 
 
 def gat_grad_ok(got, ref64, scale):
