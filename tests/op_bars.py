@@ -39,7 +39,7 @@ inputs of ``split_sensitive_inputs`` / ``wgrad_sensitive_inputs``, where any los
 
 The HIP kernels' own r per case is in profiles/op_bars.txt (tools/op_bars.py writes it).
 
-``expected_kernel`` restates the host-side dispatch of csrc/gemm_dispatch.hip, gemm_flat.h, wgrad_dispatch.hip, spmm.hip and api_ops.hip; the GPU cases are labelled
+``expected_kernel`` restates the host-side dispatch of csrc/gemm_dispatch.hip, gemm_flat.h, wgrad_dispatch.hip, spmm_dispatch.hip and api_ops.hip; the GPU cases are labelled
 with its result and tests/test_op_bars_cpu.py asserts that the tables reach every kernel name of KERNELS.
 """
 from __future__ import annotations
@@ -426,22 +426,22 @@ def _cdiv(a: int, b: int) -> int:
 
 
 def panel_wide(nnodes: int) -> bool:
-    # spmm.hip panel_wide (REGT_SPMM_PL unset): an XCD's slice of X at 256 B per node stays around its L2
+    # spmm_dispatch.hip panel_wide (REGT_SPMM_PL unset): an XCD's slice of X at 256 B per node stays around its L2
     return _cdiv(nnodes, 8) * 256 <= SP_WIDE_SLICE_MAX
 
 
 def rows_rpg(nnodes: int, pl: int, bf: bool) -> int:
-    # spmm.hip rows_rpg
+    # spmm_dispatch.hip rows_rpg
     return max(1, _cdiv(_cdiv(nnodes, 8), (256 // pl) * (150 if bf else 240)))
 
 
 def rows_cap(bf: bool) -> int:
-    # spmm.hip rows_cap: LDS entries per workgroup of the row-block kernel
+    # spmm_dispatch.hip rows_cap: LDS entries per workgroup of the row-block kernel
     return (163840 // (5 if bf else 8) - 260 * 4 - 64) // 16
 
 
 def rows_ok(nnodes: int, x_rows: int, rowbytes: int, pl: int, spmm_rows: int) -> bool:
-    # spmm.hip rows_wanted + rows_ok
+    # spmm_dispatch.hip rows_wanted + rows_ok
     return bool(spmm_rows) and rowbytes % (pl * 16) == 0 and x_rows * rowbytes < (1 << 32) - 4096 and \
         nnodes * rowbytes < (1 << 32) - 4096 and (256 // pl) * rows_rpg(nnodes, pl, False) <= 256
 
@@ -500,7 +500,7 @@ def expected_kernel(op: str, mode: int, shape, options: Optional[Dict] = None) -
     if op == "spmm_csr":
         nrows, x_rows, w = shape
         w4 = w // 4
-        # spmm.hip launch_spmm_csr.  regt_spmm_csr (api_ops.hip) always passes nstack = 1, so a stacked operator runs as a plain CSR of
+        # spmm_dispatch.hip spmm_pick, SP_SINGLE (launch_spmm_csr).  regt_spmm_csr (api_ops.hip) always passes nstack = 1, so a stacked operator runs as a plain CSR of
         # 2 n rows over n rows of X: the nstack > 1 indexing of spmm_panel_kernel cannot be reached from the op site
         if w4 % 8 == 0 and x_rows * w * 4 > (24 << 20) and nrows >= 4096:
             pl = 16 if panel_wide(nrows) and w4 % 16 == 0 else 8
@@ -516,7 +516,7 @@ def expected_kernel(op: str, mode: int, shape, options: Optional[Dict] = None) -
     if op == "spmm_dual":
         n, w = shape
         w4 = w // 4
-        # spmm.hip launch_spmm_dual_x (regt_spmm_dual: x_rows = n)
+        # spmm_dispatch.hip spmm_pick, SP_DUAL (launch_spmm_dual_x; regt_spmm_dual: x_rows = n)
         if w % 32 != 0 or (n * w * 4 <= (24 << 20) and w4 <= 512):
             for lim, g, ch in ((8, 8, 1), (16, 16, 1), (32, 32, 1), (64, 64, 1), (128, 64, 2), (256, 64, 4), (512, 64, 8)):
                 if w4 <= lim:
@@ -527,7 +527,7 @@ def expected_kernel(op: str, mode: int, shape, options: Optional[Dict] = None) -
         return f"spmm_dual_panel_kernel<{pl},{pl}>"
     if op == "spmm_dual_bf16":
         n, x_rows, w = shape
-        # spmm.hip launch_spmm_dual_bf16
+        # spmm_dispatch.hip spmm_pick, SP_DUAL_BF16 (launch_spmm_dual_bf16)
         pl = 16 if panel_wide(n) and (2 * w) % 256 == 0 else 8
         if o["spmm_rows"] and (256 // pl) * rows_rpg(n, pl, True) <= 256:
             return f"spmm_rows_kernel<{pl},true,true>"

@@ -1,5 +1,6 @@
 #!/bin/bash
 # PMC passes over tools/spmm_bench.py (run on the GPU box from the repo root): tools/spmm_pmc.sh <tag> [env assignments...]
+# (kernels: csrc/spmm_panel.hip, spmm_csr.hip; which one runs: spmm_pick in csrc/spmm_dispatch.hip)
 tag=$1; shift
 for kv in "$@"; do export "$kv"; done
 mkdir -p gpurun_out
