@@ -310,6 +310,34 @@ int32_t regt_cell_backward(const regt_dims* dims, const regt_graph* graph, const
                            const float* h_in, float* dh_in, void* workspace, size_t workspace_bytes, regt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * One step of the TGCN cell alone -- TGCN.forward(X, edge_index, edge_weight, H), models/utils.py:163-203 -- with no attention and no
+ * head, differentiable in X and H (additive entries: REGT_ABI_VERSION is unchanged).
+ *     H' (N, C) = Z * H + (1 - Z) * H~      x (N, F), A_hat = graph (N rows, regt_gcn_csr), h_in (N, C) or NULL = zeros
+ * dims: T must be 1 and regional 0; R, O and H1 are ignored; arith fp32 or bf16x3 (the bf16 arithmetic is refused).  params / grads:
+ * only conv_lin_w, conv_bias, gate_w and gate_b are used, every other entry may be NULL.
+ * regt_tgcn_forward runs the cell stages of regt_cell_forward at T = 1: h_out is, bit for bit, the `hidden` regt_cell_forward gives
+ * with a ONE-element attention tensor (a single logit has probability exactly 1).  REGT_DIMS_FORWARD_ONLY: same h_out, a smaller
+ * workspace (regt_tgcn_workspace_bytes with the flag set), and regt_tgcn_backward on that workspace is refused.
+ * regt_tgcn_backward must follow regt_tgcn_forward on the same workspace with the same h_in (NULL again where it was NULL); h_out is
+ * that forward's output, dh_out (N, C) the whole upstream gradient.  The parameter gradients (written, not accumulated) and dh_in are
+ * those of regt_cell_backward at T = 1 for dpred = 0 and dhidden = dh_out, bit for bit.  dx (N, F), optional (NULL = not wanted:
+ * nothing is launched for it), is the gradient of x:
+ *     dAx (N, F) = dzp Gz + drp Gr + dhp Gh      (csrc/cell_dx.hip: the three pre-activation gradients are read once, 3 N C floats;
+ *                                                 G_k = U_k[:, :C] W_k are the composed (C, F) weights of the forward)
+ *     dx  (N, F) = A_hat^T dAx                   (regt_spmm_csr over t_rowptr / t_col / t_val, the CSR of A_hat^T)
+ * dh_in (N, C), optional, is the gradient of h_in.  Every sum has a fixed order: bit-reproducible.
+ * Refused before anything is launched (message in regt_last_error): NULL dims / graph / required params, grads or pointers; C % 4 or
+ * F % 4 != 0; T != 1; regional != 0; the bf16 arithmetic; workspace_bytes below regt_tgcn_workspace_bytes(dims) (0 = refused dims);
+ * dx without the transposed operator; x, h_in, h_out, dh_out, dx, dh_in or workspace not 16-byte aligned; F > 64 with dx.
+ * ---------------------------------------------------------------------------------------------- */
+size_t regt_tgcn_workspace_bytes(const regt_dims* dims);
+int32_t regt_tgcn_forward(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const float* x, const float* h_in,
+                          float* h_out, void* workspace, size_t workspace_bytes, regt_stream_t stream);
+int32_t regt_tgcn_backward(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const regt_grads* grads,
+                           const float* dh_out, const float* h_in, const float* h_out, const int32_t* t_rowptr, const int32_t* t_col,
+                           const float* t_val, float* dx, float* dh_in, void* workspace, size_t workspace_bytes, regt_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Streaming inference: the attention-weighted sum over a RING of cached per-time-step cell outputs, then the head.
  *
  * RegionalA3TGCN.forward / A3TGCN.forward call the cell with H = None in every period (models/RegionalTemporalGCN.py:134-146,

@@ -195,6 +195,124 @@ int32_t regt_cell_backward(const regt_dims* dims, const regt_graph* graph, const
     return backward_impl(*dims, *graph, *params, *grads, dpred, dhidden, hidden, nullptr, L, (hipStream_t)st, qbf, h_in, dh_in);
 }
 
+/* ---- one TGCN cell step, no attention, no head, differentiable in x and H (regtgcn.h) ---------------------------- */
+namespace {
+// The step's own layout (training or forward-only) followed by what the cell-only calls add: the one attention logit whose softmax is
+// exactly 1, the zero hidden input of a call without h_in, and dAx (N, F) of the backward.
+struct TgcnLayout { Layout L; float *logit, *h0, *dAx; size_t bytes; };
+TgcnLayout tgcn_layout(const regt_dims& d, bool fwd_only, char* base) {
+    TgcnLayout t{};
+    t.L = fwd_only ? make_layout_fwd(d, 0, false, d.N, base) : make_layout(d, 0, 0, base);
+    size_t off = t.L.bytes;
+    auto take = [&](size_t nbytes) {
+        float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
+        off += (nbytes + 255) & ~(size_t)255;
+        return p;
+    };
+    t.logit = take(4);
+    t.h0 = take((size_t)d.N * d.C * 4);
+    if (!fwd_only) t.dAx = take((size_t)d.N * d.F * 4);
+    t.bytes = off;
+    return t;
+}
+// the caller's dims as the step pipeline takes them: T = 1, no head (R, O, H1 are ignored: any positive value sizes the same arithmetic)
+int tgcn_dims(const regt_dims* dims, const char* what, regt_dims* out) {
+    REGT_CHECK_ARG(dims != nullptr, "%s: dims is NULL", what);
+    regt_dims d = *dims;
+    d.R = 1; d.O = 1; d.H1 = 4;
+    TRY(check_dims(&d));
+    REGT_CHECK_ARG(d.T == 1, "%s: dims.T=%d must be 1 (one cell step)", what, d.T);
+    REGT_CHECK_ARG(d.regional == 0, "%s: dims.regional must be 0", what);
+    d.flags |= REGT_DIMS_NO_HEAD;
+    *out = d;
+    return REGT_OK;
+}
+// (inside a CallScope: gemm_mode() is this call's arithmetic)
+int tgcn_refuse_bf16(const char* what) {
+    REGT_CHECK_ARG(gemm_mode() != 2, "%s: the bf16 arithmetic is not covered (fp32 and bf16x3 are); pass dims.arith = REGT_ARITH_FP32 or "
+                   "REGT_ARITH_BF16X3", what);
+    return REGT_OK;
+}
+int tgcn_check_params(const regt_params* p, const char* what) {
+    REGT_CHECK_ARG(p != nullptr, "%s: params is NULL", what);
+    bool ok = true;
+    for (int k = 0; k < 3; ++k) ok = ok && p->conv_lin_w[k] && p->conv_bias[k] && p->gate_w[k] && p->gate_b[k];
+    REGT_CHECK_ARG(ok, "%s: params: conv_lin_w, conv_bias, gate_w and gate_b must all be given", what);
+    return REGT_OK;
+}
+}  // namespace
+
+size_t regt_tgcn_workspace_bytes(const regt_dims* dims) {
+    regt_dims d;
+    if (tgcn_dims(dims, "regt_tgcn_workspace_bytes", &d)) return 0;
+    CallScope call(&d);
+    if (tgcn_refuse_bf16("regt_tgcn_workspace_bytes")) return 0;
+    return tgcn_layout(d, (d.flags & REGT_DIMS_FORWARD_ONLY) != 0, nullptr).bytes;
+}
+
+int32_t regt_tgcn_forward(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const float* x, const float* h_in,
+                          float* h_out, void* ws, size_t ws_bytes, regt_stream_t st) {
+    regt_dims d;
+    TRY(tgcn_dims(dims, "regt_tgcn_forward", &d));
+    CallScope call(&d);
+    TRY(tgcn_refuse_bf16("regt_tgcn_forward"));
+    REGT_CHECK_ARG(graph && graph->rowptr && graph->col && graph->val && !graph->overlap, "regt_tgcn_forward: graph incomplete");
+    TRY(tgcn_check_params(params, "regt_tgcn_forward"));
+    REGT_CHECK_ARG(x && h_out && ws, "regt_tgcn_forward: NULL pointer");
+    REGT_CHECK_ARG(al16(x) && al16(h_in) && al16(h_out) && al16(ws), "regt_tgcn_forward: x, h_in, h_out and workspace must be 16-byte aligned");
+    const bool fwd_only = (d.flags & REGT_DIMS_FORWARD_ONLY) != 0;
+    const TgcnLayout t = tgcn_layout(d, fwd_only, (char*)ws);
+    REGT_CHECK_ARG(ws_bytes >= t.bytes, "regt_tgcn_forward: workspace %zu < required %zu bytes (regt_tgcn_workspace_bytes)", ws_bytes, t.bytes);
+    note_q_format(ws, fwd_only ? FMT_FWDONLY : 0);
+    hipStream_t hs = (hipStream_t)st;
+    TRY(launch_zero_f32(t.logit, 1, hs));            // softmax of one logit: probability exactly 1
+    if (!h_in) TRY(launch_zero_f32(t.h0, (long)d.N * d.C, hs));
+    regt_params p = *params;
+    p.attention = t.logit;
+    return forward_impl(d, *graph, p, x, nullptr, 0, nullptr, h_out, t.L, hs, false, h_in ? h_in : t.h0, fwd_only ? FMT_FWDONLY : 0);
+}
+
+int32_t regt_tgcn_backward(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const regt_grads* grads,
+                           const float* dh_out, const float* h_in, const float* h_out, const int32_t* t_rowptr, const int32_t* t_col,
+                           const float* t_val, float* dx, float* dh_in, void* ws, size_t ws_bytes, regt_stream_t st) {
+    regt_dims d;
+    TRY(tgcn_dims(dims, "regt_tgcn_backward", &d));
+    CallScope call(&d);
+    TRY(tgcn_refuse_bf16("regt_tgcn_backward"));
+    REGT_CHECK_ARG(!(d.flags & REGT_DIMS_FORWARD_ONLY), "regt_tgcn_backward: REGT_DIMS_FORWARD_ONLY is for the forward");
+    REGT_CHECK_ARG(graph && graph->rowptr && !graph->overlap, "regt_tgcn_backward: graph incomplete");
+    TRY(tgcn_check_params(params, "regt_tgcn_backward"));
+    REGT_CHECK_ARG(grads && dh_out && h_out && ws, "regt_tgcn_backward: NULL pointer");
+    {
+        bool ok = true;
+        for (int k = 0; k < 3; ++k) ok = ok && grads->conv_lin_w[k] && grads->conv_bias[k] && grads->gate_w[k] && grads->gate_b[k];
+        REGT_CHECK_ARG(ok, "regt_tgcn_backward: grads: conv_lin_w, conv_bias, gate_w and gate_b must all be given");
+    }
+    REGT_CHECK_ARG(!dx || (t_rowptr && t_col && t_val), "regt_tgcn_backward: dx needs the transposed operator (t_rowptr, t_col, t_val)");
+    REGT_CHECK_ARG(!dx || d.F <= 64, "regt_tgcn_backward: dx covers F <= 64 (F=%d)", d.F);
+    REGT_CHECK_ARG(al16(dx) && al16(dh_in) && al16(h_out) && al16(h_in) && al16(dh_out) && al16(ws),
+                   "regt_tgcn_backward: dx, dh_in, h_out, h_in, dh_out and workspace must be 16-byte aligned");
+    const int fmt = q_format(ws);
+    REGT_CHECK_ARG(!(fmt & FMT_FWDONLY), "regt_tgcn_backward: the last forward on this workspace ran with REGT_DIMS_FORWARD_ONLY and kept no "
+                   "activations; run the forward without that flag on a workspace of regt_tgcn_workspace_bytes");
+    const TgcnLayout t = tgcn_layout(d, false, (char*)ws);
+    REGT_CHECK_ARG(ws_bytes >= t.bytes, "regt_tgcn_backward: workspace %zu < required %zu bytes (regt_tgcn_workspace_bytes)", ws_bytes, t.bytes);
+    hipStream_t hs = (hipStream_t)st;
+    regt_params p = *params;
+    p.attention = t.logit;
+    regt_grads g = *grads;
+    g.attention = nullptr;                           // the logit is no parameter: its gradient is not formed
+    // (h_in == NULL: the forward's zero hidden input is still in the workspace; dh_in == NULL: the data gradients still need the array)
+    TRY(backward_impl(d, *graph, p, g, nullptr, dh_out, h_out, nullptr, t.L, hs, fmt, h_in ? h_in : t.h0, dh_in ? dh_in : t.L.dh));
+    if (!dx) return REGT_OK;
+    {
+        PROF("cell_dx", hs);
+        TRY(launch_cell_dx(t.L.dzr, t.L.dhp, t.L.Gzr, t.L.Gh, t.dAx, d.N, d.C, d.F, hs));
+    }
+    PROF("spmm_dx", hs);
+    return launch_spmm_csr(t_rowptr, t_col, t_val, t.dAx, dx, d.N, d.N, d.F, 1, hs);
+}
+
 /* ---- streaming inference: attention-weighted window sum over cached cell outputs + head (regtgcn.h) ---- */
 // workspace: the T attention probabilities (a fixed 255-float region: the size does not depend on T), then the head's (rows x H1) activation
 static const size_t WINDOW_PROBS_BYTES = 1024;

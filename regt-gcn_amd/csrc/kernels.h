@@ -374,6 +374,9 @@ struct CellBwdArgs {
     int in_bf16 = 0;    // ZR, h and Ht hold bf16 elements (all three together; needs out_bf16 and C % 8 == 0)
 };
 int launch_cell_bwd(const CellBwdArgs& a, hipStream_t st);
+// the cell's input gradient in front of the transposed aggregation (cell_dx.hip): dAx (N, F) = [dzp | drp] [Gz; Gr] + dhp Gh, one pass over
+// dzr (N, 2C) and dhp (N, C); C % 4 == 0, F % 4 == 0, F <= 64, 16-byte aligned pointers
+int launch_cell_dx(const float* dzr, const float* dhp, const float* Gzr, const float* Gh, float* dAx, int N, int C, int F, hipStream_t st);
 int cell_bwd_blocks(int num_nodes, int nodes_per_block);
 int launch_att_bwd(const float* dp_partial, int nblocks, const float* probs, float* datt, int T, hipStream_t st);
 // zero-hidden cell: hidden[n, :] = sum_t probs[t] * (1 - Z[n*T+t, :]) * Ht[n*T+t, :]

@@ -608,6 +608,107 @@ class CellFunction(torch.autograd.Function):
         return (None, dh_in, None) + tuple(grads[n_] for n_ in names)
 
 
+# ---- one TGCN cell step: TGCN.forward(X, edge_index, edge_weight, H), differentiable in X and H -----------------------------------------
+
+# conv_{z,r,h}.lin.weight, conv_{z,r,h}.bias, linear_{z,r,h}.weight, linear_{z,r,h}.bias under the prefix the structs are filled by
+PARAM_NAMES_TGCN = [n_ for n_ in PARAM_NAMES_COMMON if n_.startswith("tgnn._base_tgcn.")]
+F_WIDE_TGCN = tuple(n_ for n_ in PARAM_NAMES_TGCN if n_ in F_WIDE_PARAMS)
+
+
+def _tgcn_forward_call(x, h_in, op, params, forward_only: bool):
+    """regt_tgcn_forward behind :class:`TGCNStepFunction` and :func:`tgcn_run`: returns ``(h_out, state)``; ``state`` is None for a
+    forward-only call (its workspace block is back in the pool)."""
+    from . import ops
+    if not x.is_cuda:
+        raise _lib.RegtError("the TGCN cell needs CUDA/HIP tensors: there is no CPU path in this package")
+    names = PARAM_NAMES_TGCN
+    if len(params) != len(names):
+        raise ValueError(f"expected {len(names)} parameter tensors, got {len(params)}")
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"x must be float32 (N, F), got {x.dtype} {tuple(x.shape)}")
+    for n_, p_ in zip(names, params):
+        if p_.dtype != torch.float32 or not p_.is_cuda:
+            raise ValueError(f"parameter {n_} must be a float32 CUDA tensor")
+    N, f_real = x.shape
+    if N != op.num_nodes:
+        raise ValueError(f"x has {N} nodes but the prepared operator has {op.num_nodes}")
+    # (16-byte feature rows: zero feature columns and zero weight columns, as _regt_forward_call pads them; a strided view -- the
+    # reference passes X[:, :, period] -- is staged contiguous on the way)
+    f_pad = (-f_real) % 4
+    x = torch.nn.functional.pad(x, (0, f_pad)).contiguous() if f_pad else x.contiguous()
+    params = tuple((torch.nn.functional.pad(p_, (0, f_pad)) if (f_pad and n_ in F_WIDE_TGCN) else p_).contiguous()
+                   for n_, p_ in zip(names, params))
+    tens = dict(zip(names, params))
+    Cdim = tens["tgnn._base_tgcn.conv_z.bias"].numel()
+    F = f_real + f_pad
+    for k in GATES:
+        for n_, shp in ((f"tgnn._base_tgcn.conv_{k}.lin.weight", (Cdim, F)), (f"tgnn._base_tgcn.linear_{k}.weight", (Cdim, 2 * Cdim))):
+            if tuple(tens[n_].shape) != shp:
+                raise ValueError(f"parameter {n_} has shape {tuple(tens[n_].shape)}, expected {shp}")
+    if h_in is not None:
+        if tuple(h_in.shape) != (N, Cdim) or h_in.dtype != torch.float32 or h_in.device != x.device:
+            raise ValueError(f"H must be float32 ({N}, {Cdim}) on {x.device}, got {h_in.dtype} {tuple(h_in.shape)}")
+        h_in = h_in.contiguous()
+    dims = ops.tgcn_dims(N, F, Cdim, 0, _lib.DIMS_FORWARD_ONLY if forward_only else 0)
+    gs = _gcn_graph_struct(op)
+    wsb = _workspace_bytes("regt_tgcn_workspace_bytes", C.byref(dims))
+    handle = _WsHandle(wsb, x.device)
+    ps = _fill(_lib.Params(), tens, False)
+    h_out = ops.tgcn_forward(dims, gs, ps, x, h_in, torch.empty(N, Cdim, dtype=torch.float32, device=x.device), handle.ws)
+    if forward_only:
+        handle.release_now()
+        return h_out, None
+    return h_out, _FwdState(graph=op, dims=dims, handle=handle, wsb=wsb, saved=(h_in, *params), ps=ps, gs=gs, names=names, f_real=f_real,
+                            f_pad=f_pad)
+
+
+def tgcn_run(x, h_in, op, *params):
+    """:class:`TGCNStepFunction` where a gradient may be asked for, the forward-only library call where none can
+    (:func:`wants_forward_only`); ``(x (N, F), h_in (N, C) | None, op: GcnOperator, *PARAM_NAMES_TGCN tensors) -> h_out (N, C)``."""
+    if wants_forward_only(x, h_in, *params):
+        return _tgcn_forward_call(x, h_in, op, params, True)[0]
+    return TGCNStepFunction.apply(x, h_in, op, *params)
+
+
+class TGCNStepFunction(torch.autograd.Function):
+    """(x (N, F), h_in (N, C) | None, op, *12 cell params) -> h_out (N, C): regt_tgcn_forward / regt_tgcn_backward.  The backward
+    returns dx only when x requires a gradient and dh_in only when h_in does (the library launches nothing for a gradient nobody asked
+    for).  Honours :func:`set_grad_accumulation_in_backward`."""
+
+    @staticmethod
+    def forward(ctx, x, h_in, op, *params):
+        ctx.leaf_params = params
+        h_out, ctx.st = _tgcn_forward_call(x, h_in, op, params, False)
+        ctx.has_h = h_in is not None
+        ctx.save_for_backward(h_out, *(t_ for t_ in ctx.st.saved if t_ is not None))
+        return h_out
+
+    @staticmethod
+    def backward(ctx, dh_out):
+        from . import ops
+        h_out, *rest = ctx.saved_tensors
+        h_in = rest.pop(0) if ctx.has_h else None
+        params, st = rest, ctx.st
+        names, dims = st.names, st.dims
+        dev = h_out.device
+        sizes = [(p_.numel() + 3) & ~3 for p_ in params]             # one allocation, 16-byte aligned views
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        grads, off = {}, 0
+        for n_, p_, sz in zip(names, params, sizes):
+            grads[n_] = flat[off:off + p_.numel()].view_as(p_)
+            off += sz
+        gr = _fill(_lib.Grads(), grads, False)
+        dx = torch.empty(dims.N, dims.F, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        dh_in = torch.empty_like(h_out) if (ctx.has_h and ctx.needs_input_grad[1]) else None
+        ops.tgcn_backward(dims, st.gs, st.ps, gr, dh_out.contiguous(), h_in, h_out, st.graph, dx, dh_in, st.handle.ws)
+        if st.f_pad:
+            for n_ in F_WIDE_TGCN:
+                grads[n_] = grads[n_][:, :st.f_real].contiguous()
+            if dx is not None:
+                dx = dx[:, :st.f_real]
+        return (dx, dh_in, None) + _deliver_grads(ctx.leaf_params, [grads[n_] for n_ in names])
+
+
 class AggregateFunction(torch.autograd.Function):
     """Y = A_hat @ H for a learned H (N, W): forward pulls over the CSR of A_hat, backward over the CSR of A_hat^T."""
 

@@ -7,7 +7,8 @@ unchanged:
 * :class:`RegionalTemporalGCN`  <-> models/RegionalTemporalGCN.py:9-39  (+ RegionalA3TGCN :42-149)
 * :class:`TemporalGCN`          <-> models/TemporalGCN.py:7-32          (+ A3TGCN :35-91)
 * :class:`ConvStackedTemporalGCN` <-> models/ConvStackedTemporalGCN.py:8-33 (+ ConvStackedA3TGCN :35-126)
-* :class:`TGCN`                 <-> models/utils.py:69-203 (parameter container of the GRU cell)
+* :class:`TGCN`                 <-> models/utils.py:69-203 (the GRU cell: ``forward(X, edge_index, edge_weight, H)``, differentiable in X and H)
+* :class:`A3TGCN`, :class:`RegionalA3TGCN` <-> the inner modules above, callable on their own (``model.tgnn(...)`` -> hidden)
 * :class:`SpatialGCN`           <-> models/SpatialGCN.py:8-49
 * :class:`STNorm`               <-> models/STNorm.py:6-185
 * :class:`STID`                 <-> models/STID.py:5-157
@@ -33,7 +34,7 @@ from . import ops
 from .functional import (HEAD_HIDDEN, PARAM_NAMES_CELL, AggregateFunction, Cell0Function, CellFunction, GatAggregateFunction,
                          GRUFunction, LinearFunction, MLPHeadFunction, RegTGCNFunction, SpatialEmbedFunction, STAEAddLayerNormFunction,
                          STAEDropAddLayerNormFunction, STAEEmbedFunction, STAEOutputProjFunction, STAEPackedAttentionFunction, STIDFunction, STNormFunction, ZeroGradAnchor, _regt_forward_call, cell_run, param_names,
-                         regt_period_gradients, regt_run)
+                         regt_period_gradients, regt_run, tgcn_run)
 from .graph import (AttentionPattern, GcnOperator, MeanOperator, PreparedGraph, fingerprint, prepare_attention_pattern,
                     prepare_cheb_operator, prepare_gcn_operator, prepare_graph, prepare_mean_operator)
 
@@ -113,6 +114,33 @@ class TGCN(nn.Module):
         self.linear_r = nn.Linear(2 * out_channels, out_channels)
         self.conv_h = conv(in_channels, out_channels)
         self.linear_h = nn.Linear(2 * out_channels, out_channels)
+        self._graphs = _GraphCache()
+
+    def _cell_params(self) -> List[torch.Tensor]:
+        """The twelve tensors in functional.PARAM_NAMES_TGCN order."""
+        convs, lins = (self.conv_z, self.conv_r, self.conv_h), (self.linear_z, self.linear_r, self.linear_h)
+        return [c.lin.weight for c in convs] + [c.bias for c in convs] + [m.weight for m in lins] + [m.bias for m in lins]
+
+    def _gcn_only(self):
+        if self.baseblock != "gcn":
+            raise NotImplementedError(f"TGCN.forward runs baseblock='gcn'; the '{self.baseblock}' block runs inside "
+                                      "GraphSAGETemporalGCN / GATTemporal (zero hidden state, all periods at once)")
+
+    def forward_prepared(self, X: torch.Tensor, op: GcnOperator, H: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One cell step on a prepared operator (:func:`prepare_gcn_operator`): H' (N, C).  Differentiable in the parameters, in ``X``
+        and in ``H`` (regt_tgcn_forward / regt_tgcn_backward); ``X`` may be a strided view such as ``X[:, :, period]``."""
+        self._gcn_only()
+        _need_cuda(X)
+        return tgcn_run(X, H, op, *self._cell_params())
+
+    def forward(self, X: torch.Tensor, edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor] = None,
+                H: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The reference's ``TGCN.forward(X, edge_index, edge_weight, H)`` (models/utils.py:190-203): X (N, F), H (N, C) or None = zeros."""
+        self._gcn_only()
+        _need_cuda(X)
+        n = X.shape[0]
+        op = self._graphs.get([edge_index, edge_weight], n, lambda: prepare_gcn_operator(edge_index, edge_weight, n))
+        return self.forward_prepared(X, op, H)
 
 
 class _GraphCache:
@@ -155,8 +183,25 @@ def _need_cuda(x: torch.Tensor):
                              "(use oracle/ for CPU checks)")
 
 
+def _inner_hidden(mod: nn.Module, regional: bool, x: torch.Tensor, graph: PreparedGraph) -> torch.Tensor:
+    """``hidden`` (N, C) of an inner module (A3TGCN / RegionalA3TGCN) called on its own: the whole-model entry points without the head
+    (DIMS_NO_HEAD) -- the bits the owning model returns as ``hidden``.  The head tensors the parameter structs name are stand-ins that
+    the library neither reads nor writes under that flag."""
+    _need_cuda(x)
+    named = dict(mod.named_parameters())
+    names = param_names(regional)
+    dev = named["_attention"].device
+    head = mod.__dict__.get("_no_head_tensors")
+    if head is None or head[0].device != dev:
+        c = mod.out_channels
+        head = mod.__dict__["_no_head_tensors"] = [torch.zeros(s, dtype=torch.float32, device=dev) for s in ((4, c), (4,), (1, 4), (1,))]
+    params = [named[n_[len("tgnn."):]] for n_ in names[:-4]] + head
+    return regt_run(x, graph, regional, LEAKY_SLOPE, (False, _lib.arith_code(getattr(mod, "arithmetic", None)), _lib.DIMS_NO_HEAD), *params)[1]
+
+
 class RegionalA3TGCN(nn.Module):
-    """Parameter layout of models/RegionalTemporalGCN.py:42-88 (attention over periods + regional ChebConv + TGCN)."""
+    """models/RegionalTemporalGCN.py:42-149 (attention over periods + regional ChebConv + TGCN): the parameter layout, and ``forward``
+    with the reference's argument list, returning the attention-weighted hidden state (N, C)."""
 
     def __init__(self, in_channels: int, out_channels: int, num_nodes: int, periods: int, improved: bool = False,
                  cached: bool = False, add_self_loops: bool = True, num_regions: int = 5):
@@ -173,6 +218,28 @@ class RegionalA3TGCN(nn.Module):
         self.conv = _ChebConvParams(in_channels, out_channels)
         self.linear = nn.Linear(out_channels * num_regions, out_channels)
         nn.init.uniform_(self._attention)
+        self._graphs = _GraphCache()
+
+    def forward(self, X: torch.Tensor, edge_index: torch.Tensor, *regions, edge_weight: Optional[torch.Tensor] = None,
+                H: Optional[torch.Tensor] = None, C: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``forward(X, edge_index, idx_1..idx_R, weight_1..weight_R, edge_weight=None, H=None, C=None)`` -> hidden (N, C)
+        (models/RegionalTemporalGCN.py:114-149; ``edge_weight``, ``H``, ``C`` may also follow positionally).  ``H`` and ``C`` are
+        accepted and ignored, as the reference ignores them: every period's cell starts from the regional embedding."""
+        r = self.num_regions
+        extra = list(regions[2 * r:])
+        if len(regions) < 2 * r or len(extra) > 3:
+            raise TypeError(f"forward() expects {r} regional edge_index tensors followed by {r} edge weight tensors "
+                            f"(then optionally edge_weight, H, C), got {len(regions)} tensors")
+        if extra:
+            edge_weight = extra[0]
+        idx, attr = list(regions[:r]), list(regions[r:2 * r])
+        _need_cuda(X)
+        n = X.shape[0]
+        flat: List[Optional[torch.Tensor]] = [edge_index, edge_weight]
+        for i, a in zip(idx, attr):
+            flat += [i, a]
+        graph = self._graphs.get(flat, n, lambda: prepare_graph(edge_index, edge_weight, idx, attr, n))
+        return _inner_hidden(self, True, X, graph)
 
 
 class A3TGCN(nn.Module):
@@ -187,6 +254,17 @@ class A3TGCN(nn.Module):
         self.linear = nn.Linear(64, out_channels)
         self._attention = nn.Parameter(torch.empty(periods))
         nn.init.uniform_(self._attention)
+        self._graphs = _GraphCache()
+
+    def forward(self, X: torch.Tensor, edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor] = None,
+                H: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``forward(X (N, F, T), edge_index, edge_weight, H)`` -> hidden (N, C) (models/TemporalGCN.py:75-91).  ``H`` is accepted and
+        ignored, as the reference ignores it: every period's cell starts from the Chebyshev embedding."""
+        _need_cuda(X)
+        n = X.shape[0]
+        graph = self._graphs.get([edge_index, edge_weight], n,
+                                 lambda: prepare_graph(edge_index, edge_weight, [edge_index], [edge_weight], n))
+        return _inner_hidden(self, False, X, graph)
 
 
 class _FusedModel(nn.Module):

@@ -983,3 +983,27 @@ def stae_drop_add_layernorm_backward(residual: torch.Tensor, y: torch.Tensor, ke
                                                          m, d, _lib.ptr(dz), _lib.ptr(dy), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(scratch),
                                                          _stream()), "regt_stae_drop_add_layernorm_backward")
     return dz, (dz if keep is None else dy), dgamma, dbeta
+
+
+# ---- one TGCN cell step (regt_tgcn_*; functional.TGCNStepFunction builds the structs and owns the workspace) ---------------------------
+
+def tgcn_dims(n: int, f: int, c: int, arith: int = 0, flags: int = 0) -> _lib.Dims:
+    """regt_dims of one cell step: T = 1, regional = 0; R, O and H1 are ignored by the cell-only entry points."""
+    return _lib.Dims(n, 1, f, c, 1, 1, 1, 0, 0.0, int(arith), int(flags))
+
+
+def tgcn_forward(dims: _lib.Dims, gs: _lib.Graph, ps: _lib.Params, x: torch.Tensor, h_in: Optional[torch.Tensor], h_out: torch.Tensor,
+                 ws: torch.Tensor) -> torch.Tensor:
+    """h_out (N, C) = TGCN(x (N, F), A_hat, h_in (N, C) or None = zeros); ``ws``: regt_tgcn_workspace_bytes(dims) bytes."""
+    _lib.check(_lib.load().regt_tgcn_forward(ctypes.byref(dims), ctypes.byref(gs), ctypes.byref(ps), _lib.ptr(x), _lib.ptr(h_in),
+                                             _lib.ptr(h_out), _lib.ptr(ws), ws.numel(), _stream()), "regt_tgcn_forward")
+    return h_out
+
+
+def tgcn_backward(dims: _lib.Dims, gs: _lib.Graph, ps: _lib.Params, gr: _lib.Grads, dh_out: torch.Tensor, h_in: Optional[torch.Tensor],
+                  h_out: torch.Tensor, op, dx: Optional[torch.Tensor], dh_in: Optional[torch.Tensor], ws: torch.Tensor) -> None:
+    """Parameter gradients into ``gr``; ``dx`` (N, F) / ``dh_in`` (N, C) are written where given (None = not wanted).  ``op``: the
+    GcnOperator, whose transposed CSR carries dAx back to x."""
+    _lib.check(_lib.load().regt_tgcn_backward(ctypes.byref(dims), ctypes.byref(gs), ctypes.byref(ps), ctypes.byref(gr), _lib.ptr(dh_out),
+                                              _lib.ptr(h_in), _lib.ptr(h_out), _lib.ptr(op.t_rowptr), _lib.ptr(op.t_col), _lib.ptr(op.t_val),
+                                              _lib.ptr(dx), _lib.ptr(dh_in), _lib.ptr(ws), ws.numel(), _stream()), "regt_tgcn_backward")
