@@ -338,6 +338,33 @@ int32_t regt_tgcn_backward(const regt_dims* dims, const regt_graph* graph, const
                            const float* t_val, float* dx, float* dh_in, void* workspace, size_t workspace_bytes, regt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The whole model's input gradient dL/dx (N, F, T) of RegionalTemporalGCN / TemporalGCN (additive entries: REGT_ABI_VERSION is unchanged).
+ * regt_input_gradient must follow regt_backward (and its regt_forward) on the same workspace with the same dims, graph and params;
+ * REGT_DIMS_NO_HEAD is allowed.  It reads what regt_backward left there -- dzr = [dp_z | dp_r] (M, 2C), dhp (M, C) and ds (M, C), the
+ * embedding's pre-activation gradient; rows m = node T + t -- and the composed weights of the forward, writes nothing into the workspace and
+ * changes no output of regt_backward:
+ *     dAX (M, F) = dzr [Gz; Gr] + dhp Gh      dXd = ds A0      dLX = ds A_region(node)      (csrc/model_dx.hip: one pass over the rows,
+ *                                                                                            4 M C floats in, 3 M F floats out)
+ *     collapsed TemporalGCN form:             dXd = dzr P0zr + dh W0      dLX = dzr P1zr + dh W1
+ *     dx (N, F, T) = unpack(dXd + A_hat^T dAX + L~^T dLX)                                   (csrc/spmm_dual_t.hip)
+ * t_rowptr (N + 1), t_col, t_val_a, t_val_l: the CSR of the TRANSPOSE of the merged operator (graph->m_*), both weights per entry; the
+ * entries of a row ordered by their original row id.  L~ is not symmetric for asymmetric edge weights: the forward's operator does not do.
+ * scratch: regt_input_gradient_scratch_bytes(dims) bytes of the caller's, 16-byte aligned (0 = refused dims); the workspace layout and
+ * regt_workspace_bytes are unchanged.  Covers fp32 and bf16x3, node-disjoint regions in any node order, R = 1, TemporalGCN in both forms,
+ * T <= 255, block-diagonal (snapshot-batched) graphs.  Every sum has a fixed order: bit-reproducible.  All launches go on `stream`.
+ * graph->node_region is read on the device and not validated: an id outside [0, R) is clamped into that range (the gradient of such a
+ * row is then wrong; no memory outside the region blocks is read).
+ * Refused before anything is launched (message in regt_last_error): NULL dims / graph / params / dx / workspace / scratch; dx, workspace,
+ * scratch or the Chebyshev weights not 16-byte aligned; workspace_bytes below regt_workspace_bytes or scratch_bytes below
+ * regt_input_gradient_scratch_bytes; the bf16 arithmetic; graph->overlap = 1; a workspace whose last forward ran with
+ * REGT_DIMS_FORWARD_ONLY or read packed rows (regt_forward_packed*: halo gradients need an exchange); F > 64; a NULL transposed operator.
+ * ---------------------------------------------------------------------------------------------- */
+size_t regt_input_gradient_scratch_bytes(const regt_dims* dims);
+int32_t regt_input_gradient(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const int32_t* t_rowptr,
+                            const int32_t* t_col, const float* t_val_a, const float* t_val_l, float* dx, void* workspace,
+                            size_t workspace_bytes, void* scratch, size_t scratch_bytes, regt_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Streaming inference: the attention-weighted sum over a RING of cached per-time-step cell outputs, then the head.
  *
  * RegionalA3TGCN.forward / A3TGCN.forward call the cell with H = None in every period (models/RegionalTemporalGCN.py:134-146,

@@ -112,6 +112,9 @@ SIGNATURES = {
     "regt_tgcn_forward": (C.c_int32, [C.POINTER(Dims), C.POINTER(Graph), C.POINTER(Params), vp, vp, vp, vp, C.c_size_t, vp]),
     "regt_tgcn_backward": (C.c_int32, [C.POINTER(Dims), C.POINTER(Graph), C.POINTER(Params), C.POINTER(Grads), vp, vp, vp, vp, vp, vp,
                                        vp, vp, vp, C.c_size_t, vp]),
+    "regt_input_gradient_scratch_bytes": (C.c_size_t, [C.POINTER(Dims)]),
+    "regt_input_gradient": (C.c_int32, [C.POINTER(Dims), C.POINTER(Graph), C.POINTER(Params), vp, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t,
+                                        vp]),
     "regt_last_error": (C.c_char_p, []),
     "regt_graph_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "regt_gcn_csr": (C.c_int32, [vp, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, C.c_size_t, vp]),

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.environ.get("REGT_LIB_DIR") or os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libregtgcn_hip.so")
-SOURCES = ["api_runtime.hip", "api_layout.hip", "api_step.hip", "api_model.hip", "api_cell0.hip", "api_ops.hip", "api_baselines.hip", "options.hip", "gemm_fwd.hip", "gemm_cell.hip", "gemm_dispatch.hip", "gemm_small.hip", "wgrad_dispatch.hip", "wgrad_fp32.hip", "wgrad_bf16.hip", "wgrad_reduce.hip", "pack.hip", "spmm_dispatch.hip", "spmm_csr.hip", "spmm_panel.hip", "graph.hip", "cell.hip", "cell_dx.hip", "window.hip", "window_bwd.hip", "gat.hip", "fused.hip", "fused_rows.hip", "embed.hip", "spatial.hip", "stnorm.hip", "stid.hip", "gru.hip", "staeformer.hip", "staeformer_bwd.hip", "staeformer_train.hip"]
+SOURCES = ["api_runtime.hip", "api_layout.hip", "api_step.hip", "api_model.hip", "api_cell0.hip", "api_ops.hip", "api_baselines.hip", "options.hip", "gemm_fwd.hip", "gemm_cell.hip", "gemm_dispatch.hip", "gemm_small.hip", "wgrad_dispatch.hip", "wgrad_fp32.hip", "wgrad_bf16.hip", "wgrad_reduce.hip", "pack.hip", "spmm_dispatch.hip", "spmm_csr.hip", "spmm_panel.hip", "graph.hip", "cell.hip", "cell_dx.hip", "model_dx.hip", "spmm_dual_t.hip", "window.hip", "window_bwd.hip", "gat.hip", "fused.hip", "fused_rows.hip", "embed.hip", "spatial.hip", "stnorm.hip", "stid.hip", "gru.hip", "staeformer.hip", "staeformer_bwd.hip", "staeformer_train.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "regtgcn.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # developer switches, e.g. REGT_HIPCC_FLAGS=-DREGT_WG_TRACE (workgroup phase trace, tools/wg_trace.py)

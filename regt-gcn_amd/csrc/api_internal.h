@@ -119,7 +119,8 @@ HeadChunks head_chunks(long N, int H1, int C);
 // workspace formats remembered between forward and backward (note_q_format): bit 0 = bf16 intermediates, bit 1 = bf16 rows of
 // x / A_hat x / L~ x, bit 2 = the packed input was the CALLER's bf16 buffer (else the rounded copy lives in the workspace)
 // bit 4 = the forward ran with REGT_DIMS_FORWARD_ONLY: the workspace has the forward-only layout and holds nothing a backward could read
-enum : int { FMT_QBF = 1, FMT_XBF = 2, FMT_XCALLER = 4, FMT_TCOLLAPSE = 8, FMT_FWDONLY = 16 };
+// bit 5 = the forward read the caller's packed rows (regt_forward_packed*): only the note of the workspace carries it, for regt_input_gradient
+enum : int { FMT_QBF = 1, FMT_XBF = 2, FMT_XCALLER = 4, FMT_TCOLLAPSE = 8, FMT_FWDONLY = 16, FMT_PACKED = 32 };
 bool bf16_intermediates(const regt_dims& d);
 int forward_format(const regt_dims& d, const regt_graph& g, int x_rows, bool packed_fp32, bool xp_is_bf16);
 

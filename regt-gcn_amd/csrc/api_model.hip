@@ -61,7 +61,7 @@ static int32_t forward_common(const regt_dims* dims, const regt_graph* graph, co
         L = make_layout(*dims, graph->n_chunks, graph->overlap, (char*)ws);
         REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_forward: workspace %zu < required %zu bytes", ws_bytes, L.bytes);
     }
-    note_q_format(ws, fmt);
+    note_q_format(ws, fmt | (xp_ext ? FMT_PACKED : 0));
     if (!graphs_wanted((long)dims->N * dims->T))
         return forward_impl(*dims, *graph, *params, x, xp_ext, x_rows, pred, hidden, L, hs, false, nullptr, fmt);
     // the snapshot changes every step: pack it with a plain launch, replay everything behind it
@@ -311,6 +311,89 @@ int32_t regt_tgcn_backward(const regt_dims* dims, const regt_graph* graph, const
     }
     PROF("spmm_dx", hs);
     return launch_spmm_csr(t_rowptr, t_col, t_val, t.dAx, dx, d.N, d.N, d.F, 1, hs);
+}
+
+/* ---- whole-model input gradient dL/dx behind regt_backward (regtgcn.h) ------------------------------------------------- */
+namespace {
+// the call's own scratch: dAX, dXd, dLX, (M, F) each -- the step's workspace layout is not touched
+struct InputGradLayout { float *dAX, *dXd, *dLX; size_t bytes; };
+InputGradLayout input_grad_layout(const regt_dims& d, char* base) {
+    InputGradLayout s{};
+    const size_t piece = ((size_t)d.N * d.T * d.F * 4 + 255) & ~(size_t)255;
+    s.dAX = base ? reinterpret_cast<float*>(base) : nullptr;
+    s.dXd = base ? reinterpret_cast<float*>(base + piece) : nullptr;
+    s.dLX = base ? reinterpret_cast<float*>(base + 2 * piece) : nullptr;
+    s.bytes = 3 * piece;
+    return s;
+}
+// what both entry points refuse from the dims alone (inside a CallScope)
+int input_grad_dims(const regt_dims* dims, const char* what) {
+    REGT_CHECK_ARG(gemm_mode() != 2, "%s: the bf16 arithmetic is not covered (fp32 and bf16x3 are); pass dims.arith = REGT_ARITH_FP32 or "
+                   "REGT_ARITH_BF16X3", what);
+    REGT_CHECK_ARG(!(dims->flags & REGT_DIMS_FORWARD_ONLY), "%s: REGT_DIMS_FORWARD_ONLY is for the forward", what);
+    REGT_CHECK_ARG(dims->F <= 64, "%s: dx covers a (padded) feature width F <= 64 (F=%d)", what, dims->F);
+    return REGT_OK;
+}
+}  // namespace
+
+size_t regt_input_gradient_scratch_bytes(const regt_dims* dims) {
+    if (check_dims(dims)) return 0;
+    CallScope call(dims);
+    if (input_grad_dims(dims, "regt_input_gradient_scratch_bytes")) return 0;
+    return input_grad_layout(*dims, nullptr).bytes;
+}
+
+int32_t regt_input_gradient(const regt_dims* dims, const regt_graph* graph, const regt_params* params, const int32_t* t_rowptr,
+                            const int32_t* t_col, const float* t_val_a, const float* t_val_l, float* dx, void* ws, size_t ws_bytes,
+                            void* scratch, size_t scratch_bytes, regt_stream_t st) {
+    TRY(check_dims(dims));
+    CallScope call(dims);
+    const regt_dims& d = *dims;
+    TRY(input_grad_dims(dims, "regt_input_gradient"));
+    REGT_CHECK_ARG(graph != nullptr, "regt_input_gradient: graph is NULL");
+    REGT_CHECK_ARG(!graph->overlap, "regt_input_gradient: overlapping regions (graph.overlap = 1) are not covered: one Laplacian per region has no "
+                   "merged transposed operator");
+    const int fmt = q_format(ws);
+    REGT_CHECK_ARG(!(fmt & FMT_FWDONLY), "regt_input_gradient: the last forward on this workspace ran with REGT_DIMS_FORWARD_ONLY and kept no "
+                   "activations; run regt_forward without that flag and regt_backward first");
+    REGT_CHECK_ARG(!(fmt & FMT_PACKED), "regt_input_gradient: the last forward on this workspace read packed rows (regt_forward_packed): the gradient "
+                   "of halo rows needs an exchange that is not covered");
+    REGT_CHECK_ARG(!(fmt & (FMT_QBF | FMT_XBF)), "regt_input_gradient: the last forward on this workspace ran in the bf16 arithmetic, which is not covered");
+    REGT_CHECK_ARG(!d.regional || d.R == 1 || graph->node_region, "regt_input_gradient: graph.node_region is NULL");
+    TRY(check_ptrs(params, d));
+    REGT_CHECK_ARG(t_rowptr && t_col && t_val_a && t_val_l, "regt_input_gradient: dx needs the transposed merged operator (t_rowptr, t_col, t_val_a, "
+                   "t_val_l)");
+    REGT_CHECK_ARG(dx && ws && scratch, "regt_input_gradient: NULL pointer");
+    REGT_CHECK_ARG(al16(dx) && al16(ws) && al16(scratch) && al16(params->cheb_w0) && al16(params->cheb_w1),
+                   "regt_input_gradient: dx, workspace, scratch and the Chebyshev weights must be 16-byte aligned");
+    const Layout L = make_layout(d, graph->n_chunks, 0, (char*)ws);
+    REGT_CHECK_ARG(ws_bytes >= L.bytes, "regt_input_gradient: workspace %zu < required %zu bytes (regt_workspace_bytes)", ws_bytes, L.bytes);
+    const InputGradLayout s = input_grad_layout(d, (char*)scratch);
+    REGT_CHECK_ARG(scratch_bytes >= s.bytes, "regt_input_gradient: scratch %zu < required %zu bytes (regt_input_gradient_scratch_bytes)", scratch_bytes,
+                   s.bytes);
+    hipStream_t hs = (hipStream_t)st;
+    const int C = d.C, F = d.F;
+    const bool tcol = (fmt & FMT_TCOLLAPSE) != 0;
+    // (regt_backward's last writers of dzr, dhp and dh are its data gradients; the weight gradients, the slab reduction and the
+    // compositions behind them only read the three, so they are still what the data gradients left)
+    ModelDxArgs a{};
+    a.A[0] = L.dzr; a.K[0] = 2 * C;
+    a.A[1] = L.dhp; a.K[1] = C;
+    a.A[2] = L.dh;  a.K[2] = C;          // ds, the embedding's pre-activation gradient; collapsed TemporalGCN: dh without the gates' term
+    a.B[0][0] = L.Gzr;
+    a.B[1][0] = L.Gh;
+    if (tcol) { a.B[0][1] = L.P0zr; a.B[0][2] = L.P1zr; }
+    a.B[2][1] = d.regional ? L.A0 : params->cheb_w0;
+    a.B[2][2] = d.regional ? L.Aall : params->cheb_w1;
+    if (d.regional && d.R > 1) { a.node_region = graph->node_region; a.Breg = L.Aall; a.breg_stride = (long)C * F; }
+    a.out[0] = s.dAX; a.out[1] = s.dXd; a.out[2] = s.dLX;
+    a.M = (long)d.N * d.T; a.F = F; a.T = d.T; a.R = d.R;
+    {
+        PROF("model_dx", hs);
+        TRY(launch_model_dx(a, hs));
+    }
+    PROF("spmm_dx", hs);
+    return launch_spmm_dual_t(t_rowptr, t_col, t_val_a, t_val_l, s.dAX, s.dLX, s.dXd, dx, d.N, F, d.T, hs);
 }
 
 /* ---- streaming inference: attention-weighted window sum over cached cell outputs + head (regtgcn.h) ---- */

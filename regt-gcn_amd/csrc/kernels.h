@@ -377,6 +377,20 @@ int launch_cell_bwd(const CellBwdArgs& a, hipStream_t st);
 // the cell's input gradient in front of the transposed aggregation (cell_dx.hip): dAx (N, F) = [dzp | drp] [Gz; Gr] + dhp Gh, one pass over
 // dzr (N, 2C) and dhp (N, C); C % 4 == 0, F % 4 == 0, F <= 64, 16-byte aligned pointers
 int launch_cell_dx(const float* dzr, const float* dhp, const float* Gzr, const float* Gh, float* dAx, int N, int C, int F, hipStream_t st);
+// the whole model's input gradient in front of the transposed aggregation (model_dx.hip): three (M, F) outputs from three row segments in one
+// pass.  Segment s streams A[s] (M, K[s]) once; B[s][o] (K[s], F) multiplies it into out[o] (NULL: not).  node_region != NULL: B[2][2] is
+// ignored and row m takes the block Breg + node_region[m / T] * breg_stride (ids clamped to [0, R)); regions need not be sorted.
+struct ModelDxArgs {
+    const float* A[3]; int K[3];
+    const float* B[3][3];
+    const float* Breg; long breg_stride; const int* node_region;
+    float* out[3];
+    long M; int F, T, R;
+};
+int launch_model_dx(const ModelDxArgs& a, hipStream_t st);
+// dx (nrows, F, T) = unpack(init + A^T P + L^T Q) over the transposed merged CSR (spmm_dual_t.hip); P, Q, init (nrows, T F) packed rows
+int launch_spmm_dual_t(const int* rowptr, const int* col, const float* val_a, const float* val_l, const float* P, const float* Q,
+                       const float* init, float* dx, int nrows, int F, int T, hipStream_t st);
 int cell_bwd_blocks(int num_nodes, int nodes_per_block);
 int launch_att_bwd(const float* dp_partial, int nblocks, const float* probs, float* datt, int T, hipStream_t st);
 // zero-hidden cell: hidden[n, :] = sum_t probs[t] * (1 - Z[n*T+t, :]) * Ht[n*T+t, :]

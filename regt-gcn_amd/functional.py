@@ -364,11 +364,26 @@ class RegTGCNFunction(torch.autograd.Function):
         gr = _fill(_lib.Grads(), grads, regional)
         _lib.check(lib.regt_backward(C.byref(dims), C.byref(st.gs), C.byref(st.ps), C.byref(gr), _lib.ptr(dpred), _lib.ptr(dhid),
                                      _lib.ptr(hidden), _lib.ptr(st.xp), _lib.ptr(st.handle.ws), st.wsb, _stream()), "regt_backward")
+        # dL/dx only where x asked for it (nothing is launched or allocated otherwise); a form the library does not cover raises
+        dx = _input_gradient(st, dev) if ctx.needs_input_grad[0] else None
         if st.f_pad:
             for n_ in F_WIDE_PARAMS:
                 if n_ in grads:
                     grads[n_] = grads[n_][:, :st.f_real].contiguous()
-        return (None, None, None, None, None) + _deliver_grads(ctx.leaf_params, [grads[n_] for n_ in names])
+        return (dx, None, None, None, None) + _deliver_grads(ctx.leaf_params, [grads[n_] for n_ in names])
+
+
+def _input_gradient(st: _FwdState, dev) -> torch.Tensor:
+    """regt_input_gradient behind :class:`RegTGCNFunction`: dL/dx (N, F, T) from what regt_backward just left in the workspace of ``st``
+    (DESIGN.md 4e).  Padded feature columns are sliced off.  The bf16 arithmetic, overlapping regions and the packed (sharded) input are
+    refused by the library: RegtError with its message."""
+    from . import ops
+    dims = st.dims
+    dx = torch.empty(dims.N, dims.F, dims.T, dtype=torch.float32, device=dev)
+    # (a packed input is refused on the workspace's record; its shard's operator has halo columns and no square transpose to build)
+    t = None if st.xp is not None else st.graph.transposed_merged
+    ops.input_gradient(dims, st.gs, st.ps, t, dx, st.handle.ws)
+    return dx[:, :st.f_real] if st.f_pad else dx
 
 
 def regt_period_gradients(x: torch.Tensor, graph: PreparedGraph, regional: bool, slope: float, arith: int, flags: int, leaf_params,

@@ -54,6 +54,18 @@ class PreparedGraph:
             self.__dict__["_region_sorted"] = bool(len(nr) < 2 or np.all(nr[1:] >= nr[:-1]))
         return self.__dict__["_region_sorted"]
 
+    @property
+    def transposed_merged(self):
+        """(t_rowptr, t_col, t_val_a, t_val_l): the CSR of the TRANSPOSE of the merged operator, both weights per entry -- what the input
+        gradient aggregates over (regt_input_gradient: dx = dXd + A_hat^T dAX + L~^T dLX; L~ is not symmetric for asymmetric edge
+        weights).  Built on first use and cached; None for overlapping regions, which have no merged operator."""
+        if "_transposed_merged" not in self.__dict__:
+            t = None
+            if self.m_rowptr is not None:
+                t = transpose_csr(self.m_rowptr, self.m_col, self.m_val_a, self.num_nodes, self.num_nodes, self.m_val_l)
+            self.__dict__["_transposed_merged"] = t
+        return self.__dict__["_transposed_merged"]
+
     def chunks_for(self, periods: int):
         """(chunk_tab (n,2) int32, chunk_region (n,) int32, n): row ranges of (node*T+t) rows inside one region."""
         if periods not in self._chunks:
@@ -312,9 +324,10 @@ class GcnOperator:
     t_val: torch.Tensor
 
 
-def transpose_csr(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, num_rows: int, num_cols: int):
+def transpose_csr(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, num_rows: int, num_cols: int, *more_vals: torch.Tensor):
     """CSR of the transposed operator (index bookkeeping on the device, once per graph).  Entries of one output row
-    are ordered by their original row id, so the summation order of the transposed SpMM is fixed too."""
+    are ordered by their original row id, so the summation order of the transposed SpMM is fixed too.  ``more_vals``: further value
+    arrays of the same entries (the second weight of a merged operator); each comes back permuted alike, after ``t_val``."""
     dev = rowptr.device
     rows = torch.repeat_interleave(torch.arange(num_rows, device=dev), (rowptr[1:] - rowptr[:-1]).long())
     key = col.long() * num_rows + rows                       # sort by (col, row)
@@ -324,7 +337,7 @@ def transpose_csr(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, nu
     counts = torch.bincount(col.long(), minlength=num_cols)
     t_rowptr = torch.zeros(num_cols + 1, dtype=torch.int32, device=dev)
     t_rowptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
-    return t_rowptr.contiguous(), t_col.contiguous(), t_val
+    return (t_rowptr.contiguous(), t_col.contiguous(), t_val) + tuple(v[order].contiguous() for v in more_vals)
 
 
 def prepare_gcn_operator(edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor], num_nodes: int, copies: int = 1) -> GcnOperator:

@@ -1007,3 +1007,21 @@ def tgcn_backward(dims: _lib.Dims, gs: _lib.Graph, ps: _lib.Params, gr: _lib.Gra
     _lib.check(_lib.load().regt_tgcn_backward(ctypes.byref(dims), ctypes.byref(gs), ctypes.byref(ps), ctypes.byref(gr), _lib.ptr(dh_out),
                                               _lib.ptr(h_in), _lib.ptr(h_out), _lib.ptr(op.t_rowptr), _lib.ptr(op.t_col), _lib.ptr(op.t_val),
                                               _lib.ptr(dx), _lib.ptr(dh_in), _lib.ptr(ws), ws.numel(), _stream()), "regt_tgcn_backward")
+
+
+def input_gradient(dims: _lib.Dims, gs: _lib.Graph, ps: _lib.Params, t_op, dx: torch.Tensor, ws: torch.Tensor,
+                   scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """regt_input_gradient: dL/dx (N, F, T) into ``dx`` from what regt_backward left in ``ws``.  ``t_op``: (t_rowptr, t_col, t_val_a,
+    t_val_l) of ``PreparedGraph.transposed_merged`` (None: the library refuses the call with its reason).  ``scratch``: a uint8 tensor of
+    at least regt_input_gradient_scratch_bytes (default: allocated here)."""
+    lib = _lib.load()
+    if scratch is None:
+        nbytes = lib.regt_input_gradient_scratch_bytes(ctypes.byref(dims))
+        if nbytes == 0:
+            _lib.check(1, "regt_input_gradient_scratch_bytes")
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dx.device)
+    t = t_op if t_op is not None else (None, None, None, None)
+    _lib.check(lib.regt_input_gradient(ctypes.byref(dims), ctypes.byref(gs), ctypes.byref(ps), _lib.ptr(t[0]), _lib.ptr(t[1]), _lib.ptr(t[2]),
+                                       _lib.ptr(t[3]), _lib.ptr(dx), _lib.ptr(ws), ws.numel(), _lib.ptr(scratch), scratch.numel(), _stream()),
+               "regt_input_gradient")
+    return dx
